@@ -7,7 +7,7 @@ update + L1 over the model tables.  Workload (default) = config c3 of BASELINE.j
 100M hashed features, k = 16, 256K rows per mini-batch (per GPU), 39 active entries per
 row (Criteo-shaped synthetic data); stepSize 0.1, regParam 1e-6.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 
 N = 1 runs the single-table path (fused step: the forward updates the rows whose feature has one
@@ -17,6 +17,12 @@ libfm_hip (weak scaling: every rank steps its own 256K-row batch each iteration)
 launcher, --gpus N drives N GPUs from this one process through one multi-GPU fm_ctx (the Spark
 driver's path); under torch.distributed.run each process drives its own GPU.  Asking for more GPUs
 than are visible exits non-zero.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step).
+--full adds everything else the line can carry, as separate work around the timed steps: HIP-event
+timing of the kernel phases and the rooflines made from it, the host-path and estimator-loop legs
+and the CPU baseline.  --dump-outputs DIR writes what the last timed step left (the loss history and
+a fixed sample of the model's rows) as DIR/<name>.npy, so two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -60,9 +66,17 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     p.add_argument("--batches", type=int, default=4, help="distinct resident mini-batches cycled through")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: HIP-event timing of the kernel phases (--profile-kernels) and the "
+                        "rooflines, the host-path leg (--host-path-steps), the estimator-loop leg (--fit-iters) and "
+                        "the CPU baseline (--no-cpu-baseline); without it none of them runs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last of them left as DIR/<name>.npy (float64): "
+                        "loss_history (every executed step's loss sum, the last timed step's last) and ids / w / V of "
+                        "a fixed, seeded sample of the model's rows; one process only")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--cpu-steps", type=int, default=2)
-    p.add_argument("--profile-kernels", type=int, default=1, help="HIP-event timing of each kernel phase")
+    p.add_argument("--profile-kernels", type=int, default=1, help="--full: HIP-event timing of each kernel phase")
     p.add_argument("--profile-every", type=int, default=4,
                    help="time the kernel phases of every n-th timed step (HIP events cost ~2 %% of a c3 step, "
                         "~12 %% of a c5 step when every step carries them)")
@@ -97,14 +111,20 @@ def parse():
                         "C-ABI path); 'torch' (torch.distributed.run only) = the torch.distributed test harness "
                         "(fm_spark_amd/distributed.py) driving the fm_shard_* phases")
     p.add_argument("--fit-iters", type=int, default=16,
-                   help="N = 1: after the timed region, run the estimator's resident mini-batch loop "
+                   help="--full, N = 1: after the timed region, run the estimator's resident mini-batch loop "
                         "(fm_spark_amd.ml.run_minibatch_sgd_resident, what FactorizationMachinesSGD.fit runs after its "
                         "randomSplit replay) over a resident synthetic dataset of this many batches' rows, split by "
                         "the randomSplit replay into as many iterations, for fit_ms_per_iter; 0 = skip")
     p.add_argument("--host-path-steps", type=int, default=12,
-                   help="N = 1: after the timed region, time this many fm_step calls with the host CSR "
+                   help="--full, N = 1: after the timed region, time this many fm_step calls with the host CSR "
                         "(PCIe-inclusive, what a JNI caller gets) for host_path_ms_per_step; 0 = skip")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if not args.full:  # a plain run: the headline's setup, warmup and timed steps only
+        args.profile_kernels = args.fit_iters = args.host_path_steps = 0
+        args.no_cpu_baseline = True
+    return args
 
 
 def median_step_ms(events):
@@ -488,6 +508,28 @@ def concat_batches(parts):
                  val=np.concatenate([p.val for p in parts]), label=np.concatenate([p.label for p in parts]))
 
 
+DUMP_ROWS = 262_144          # model rows sampled by --dump-outputs (fewer when k is large)
+DUMP_BYTES = 48 << 20        # ceiling of ids + w + V together, in float64
+
+
+def dump_outputs(out_dir, ctx, losses, last_batch, F, k):
+    """What a caller holds after the last timed step, as <out_dir>/<name>.npy in float64:
+    loss_history (the loss sum of every executed step, warmup included; the last timed step's is the
+    last) and the model rows of a fixed sample of ids -- half drawn from the ids the last timed
+    batch touched (the rows that step wrote), half uniformly from [0, F) -- as ids [n], present [n]
+    (1.0 where the model holds the row), w [n] and V [n, k] (fm_export_rows: pending L1 applied).
+    The sample depends on the arguments alone."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(min(DUMP_ROWS, DUMP_BYTES // (8 * (k + 2))))
+    rng = np.random.default_rng(20261015)
+    touched = np.unique(last_batch.col)
+    hot = rng.choice(touched, size=min(n // 2, len(touched)), replace=False)
+    ids = np.concatenate([np.sort(hot), np.sort(rng.integers(0, F, size=n - len(hot)))]).astype(np.int32)
+    w, V, present = ctx.export_rows(ids)
+    for name, a in (("loss_history", losses), ("ids", ids), ("present", present), ("w", w), ("V", V)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 class ProfileSampler:
     """Per-phase HIP-event timing (fm_profile_*) on every n-th timed step only: each phase's start
     and stop events sit on its launch stream inside the timed region, and the kernels' average
@@ -515,6 +557,8 @@ def main():
 
     pl = plan_run(args, os.environ, torch.cuda.device_count())
     world, rank, local_rank, mode = pl["world"], pl["rank"], pl["local_rank"], pl["mode"]
+    if args.dump_outputs and mode == "procs":
+        raise PlanError("--dump-outputs needs the whole model in one process (run without a launcher)")
     torch.cuda.set_device(local_rank)
     dist = None
     if mode == "procs":
@@ -571,7 +615,7 @@ def main():
         ctx.reserve(B, max(b.nnz for b in host_batches))
         nb = len(dbatches)
         # U and the singleton share of every batch, counted on the host (the device's n_unique)
-        ids_stats = [batch_ids(b) for b in host_batches]
+        ids_stats = [batch_ids(b) for b in host_batches] if args.full else None
         t = 0
         prefetch = not args.no_prefetch and not args.host_path
         depth = max(1, min(args.prefetch_depth or 1, nb - 1))
@@ -622,6 +666,8 @@ def main():
         prof_on.off()
         losses = ctx.loss_history()
         assert np.all(np.isfinite(losses)), "non-finite loss"
+        if args.dump_outputs:  # before the legs below step the model further
+            dump_outputs(args.dump_outputs, ctx, losses, host_batches[(g0 + args.steps - 1) % nb], F, k)
         if args.host_path_steps > 0 and not args.host_path:
             hmed, hmean, t = host_path_leg(ctx, host_batches, t, args.host_path_steps, torch)
             host_path = {"median_ms_per_step": hmed, "mean_ms_per_step": hmean, "steps": args.host_path_steps,
@@ -632,11 +678,13 @@ def main():
         if args.fit_iters > 0 and not args.host_path:
             fit = fit_leg(ctx, F, B, zipf_s, lab, args.fit_iters)
         timed_b = [(g0 + i) % nb for i in range(args.steps)]
-        U_mean = float(np.mean([ids_stats[j][0] for j in timed_b]))
         # the step variant from the context itself (fm_fuse_active), not from which phases were profiled
         fused = ctx.fuse_active and prefetch
-        # the singleton rows' share of the rows updated, weighted by each timed batch's U
-        single_frac = float(np.sum([ids_stats[j][0] * ids_stats[j][1] for j in timed_b])) / max(U_mean * len(timed_b), 1.0)
+        U_mean = single_frac = None
+        if ids_stats:
+            U_mean = float(np.mean([ids_stats[j][0] for j in timed_b]))
+            # the singleton rows' share of the rows updated, weighted by each timed batch's U
+            single_frac = float(np.sum([ids_stats[j][0] * ids_stats[j][1] for j in timed_b])) / max(U_mean * len(timed_b), 1.0)
         parallelism = "single table" + (", fused step (singleton rows updated by the forward)" if fused else "") + \
             ((", next batch sorted during the current step" if depth == 1 else
               f", batches sorted {depth} steps ahead on the side stream") if prefetch else "")
@@ -725,6 +773,8 @@ def main():
         prof_on.off()
         losses = ctx.loss_history()
         assert np.all(np.isfinite(losses)), "non-finite loss"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, ctx, losses, host_batches[(args.steps - 1) % nb], F, k)
         R = world
         fused = False  # multi-GPU contexts never fuse (fm_fuse_active; selects the matching PMC file)
         # rows one rank updates: sharded, the global distinct ids over the owners; replicated, every
@@ -798,7 +848,8 @@ def main():
     if rank == 0:
         ms_per_step = 1000.0 * elapsed / args.steps
         value = world * B * args.steps / elapsed
-        fwd_b, upd_b = algorithmic_bytes(F, k, B, z, U_mean)
+        # the rooflines' bytes need U, which a plain single-table run does not count
+        fwd_b, upd_b = algorithmic_bytes(F, k, B, z, U_mean) if U_mean is not None else (None, None)
         line = {
             "metric": "FM SGD train samples/sec at k=16, 1/8 GPUs; % of HBM roofline" if k == 16 else
                       f"FM SGD train samples/sec at k={k}",
@@ -807,6 +858,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_per_step,
             "median_ms_per_step": median_ms,
             "higher_is_better": True,

@@ -1165,6 +1165,10 @@ fm_batch* dataset_replica(Group& g, GroupBatch& dg, int l, const std::vector<int
       e += ne;
       row += nr;
     }
+    // copies between device buffers are queued on the null stream and return before they land; the
+    // gathers that read this copy run on the members' non-blocking streams, which the null stream
+    // does not order: wait here (once per dataset)
+    FM_HIP_CHECK(hipDeviceSynchronize());
   });
   f->host_rp.swap(rp);
   dg.full[l] = f.release();

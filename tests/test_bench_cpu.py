@@ -163,3 +163,58 @@ def test_step_traffic_covers_every_kernel_of_the_default_steps():
         t, r, src = bench.step_traffic(F, k, B, fused)
         assert t and r and src, cfg
         assert 1e8 < t < 1e10 and 1e6 < r < 1e8
+
+
+def _parse(monkeypatch, *argv):
+    monkeypatch.setattr("sys.argv", ["bench.py", *argv])
+    return bench.parse()
+
+
+def test_plain_run_drops_every_leg_and_full_keeps_them(monkeypatch):
+    """A plain run does what the headline needs; the kernel-phase timing, the host-path and fit
+    legs and the CPU baseline run under --full, with the defaults they always had."""
+    a = _parse(monkeypatch, "--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.profile_kernels == 0 and a.fit_iters == 0 and a.host_path_steps == 0 and a.no_cpu_baseline
+    a = _parse(monkeypatch, "--fit-iters", "4", "--host-path-steps", "3")  # asked for, but not --full
+    assert a.fit_iters == 0 and a.host_path_steps == 0
+    f = _parse(monkeypatch, "--full")
+    assert f.profile_kernels == 1 and f.fit_iters == 16 and f.host_path_steps == 12 and not f.no_cpu_baseline
+    f = _parse(monkeypatch, "--full", "--no-cpu-baseline", "--fit-iters", "0")
+    assert f.no_cpu_baseline and f.fit_iters == 0 and f.host_path_steps == 12
+    with pytest.raises(SystemExit):
+        _parse(monkeypatch, "--steps", "0")
+
+
+@pytest.mark.parametrize("k", [8, 16, 32])
+def test_dump_outputs_writes_a_fixed_sample_in_float64(tmp_path, k):
+    """--dump-outputs: loss history, ids, present, w, V as float64 .npy, at most 64 MB together at
+    any k; half of the ids from those the last batch touched; the sample is the same each time."""
+    from fm_spark_amd.data import synthetic_batch
+
+    F = 3_000_000
+    last = synthetic_batch(4096, F, batch_index=3)
+
+    class Ctx:
+        def export_rows(self, ids):
+            assert ids.dtype == np.int32 and ids.min() >= 0 and ids.max() < F
+            return ids * 0.5, np.outer(ids, np.ones(k)) + np.arange(k), np.ones(len(ids), bool)
+
+    losses = np.array([3.0, 2.0, 1.0])
+    outs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), Ctx(), losses, last, F, k)
+        outs.append({f.stem: np.load(f) for f in sorted((tmp_path / d).iterdir())})
+    a, b = outs
+    assert sorted(a) == ["V", "ids", "loss_history", "present", "w"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    n = len(a["ids"])
+    assert n == min(bench.DUMP_ROWS, bench.DUMP_BYTES // (8 * (k + 2))) and a["V"].shape == (n, k)
+    np.testing.assert_array_equal(a["loss_history"], losses)
+    np.testing.assert_array_equal(a["w"], a["ids"] * 0.5)  # rows in the order of ids
+    np.testing.assert_array_equal(a["V"][:, k - 1], a["ids"] + (k - 1))
+    touched = np.unique(last.col)
+    assert np.isin(a["ids"][:min(n // 2, len(touched))], touched).all()
+    for name in a:
+        np.testing.assert_array_equal(a[name], b[name])

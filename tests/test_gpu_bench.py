@@ -5,6 +5,8 @@ The single-table step (fused and unfused), the one-process multi-GPU group conte
 createMulti gives a Spark driver) and its replicated layout must train the same model: the sum of
 every executed step's loss agrees to 1e-6 (different but fixed summation orders).  Asking for more
 GPUs than the box has must exit non-zero without a JSON line (no silent downgrade to one rank).
+These read the line's kernel phases and host trace, so they run the benchmark with --full.  A plain
+run times its steps and nothing else, and --dump-outputs writes the same arrays from run to run.
 """
 
 import json
@@ -17,14 +19,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--features", "200000", "--rows", "16384", "--steps", "6", "--warmup", "2", "--batches", "2",
-         "--no-cpu-baseline", "--host-path-steps", "0"]
+SHAPE = ["--features", "200000", "--rows", "16384", "--steps", "6", "--warmup", "2", "--batches", "2"]
+SMALL = [*SHAPE, "--full", "--no-cpu-baseline", "--host-path-steps", "0"]
 
 
-def _bench(*extra, check=True):
+def _bench(*extra, check=True, base=SMALL):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, *extra], capture_output=True,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *base, *extra], capture_output=True,
                        text=True, timeout=100, env=env, cwd=ROOT)
     if not check:
         return p
@@ -64,3 +66,33 @@ def test_more_gpus_than_visible_exits_nonzero(gpu):
     p = _bench("--gpus", str(n + 1), check=False)
     assert p.returncode != 0
     assert f"needs {n + 1} visible GPUs" in p.stderr and '"metric"' not in p.stdout
+
+
+def test_plain_run_times_its_steps_only_and_dumps_the_same_outputs(single, tmp_path):
+    """Without --full the line carries the headline and none of the legs; --dump-outputs writes the
+    loss history and a fixed sample of the model's rows in float64, under 64 MB, the same from run to
+    run (same ids; the values to fp32 rounding of fixed-order sums), and the same training as --full."""
+    import numpy as np
+
+    runs = []
+    for d in ("a", "b"):
+        line = _bench("--fuse", "off", "--dump-outputs", str(tmp_path / d), base=SHAPE)
+        assert line["steps"] == 6 and line["warmup"] == 2 and line["ms_per_step"] > 0
+        assert line["value"] == pytest.approx(16384 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+        for leg in ("kernels", "roofline", "step_roofline", "host_path", "fit", "cpu_baseline"):
+            assert leg not in line, leg
+        out = {f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))}
+        assert sorted(out) == ["V", "ids", "loss_history", "present", "w"]
+        assert all(a.dtype == np.float64 for a in out.values())
+        assert sum(a.nbytes for a in out.values()) <= 64 << 20
+        n = len(out["ids"])
+        assert out["w"].shape == (n,) and out["V"].shape == (n, 16) and out["present"].all()
+        assert len(out["loss_history"]) == 8  # warmup + timed steps
+        assert float(out["loss_history"].sum()) == pytest.approx(line["loss_sum_all_steps"], rel=1e-12)
+        assert line["loss_sum_all_steps"] == pytest.approx(single["loss_sum_all_steps"], rel=1e-6)
+        assert np.abs(out["V"]).max() > 0 and np.isfinite(out["V"]).all()
+        runs.append(out)
+    a, b = runs
+    np.testing.assert_array_equal(a["ids"], b["ids"])
+    for name in ("loss_history", "w", "V"):
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-6, atol=1e-9)

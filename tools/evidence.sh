@@ -12,16 +12,16 @@ out=gpurun_out/${1:-evidence}; mkdir -p $out
 if [ "${2:-}" != skip-suite ]; then
   OUT=$out/suite bash tools/gpu_suite.sh || exit $?
 fi
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $out/bench_default.log 2>&1 || exit $?
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $out/bench_default.log 2>&1 || exit $?
 grep '^{' $out/bench_default.log | cut -c1-300 >&2
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/prof_leg -o run --output-format csv -- \
-    python bench.py --steps 20 --warmup 5 --fit-iters 0 --host-path-steps 0 --no-cpu-baseline > $out/prof_leg.log 2>&1 || exit $?
+    python bench.py --full --steps 20 --warmup 5 --fit-iters 0 --host-path-steps 0 --no-cpu-baseline > $out/prof_leg.log 2>&1 || exit $?
 grep '^{' $out/prof_leg.log | cut -c1-200 >&2
 for c in c2 c5; do
-  timeout -k 10 300 python bench.py --config $c --steps 40 --warmup 5 --fit-iters 0 --host-path-steps 0 --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --config $c --steps 40 --warmup 5 --fit-iters 0 --host-path-steps 0 --no-cpu-baseline \
       > $out/bench_$c.log 2>&1 || exit $?
 done
-timeout -k 10 300 python bench.py --force-sharded --steps 20 --warmup 5 --fit-iters 0 --host-path-steps 0 --no-cpu-baseline \
+timeout -k 10 300 python bench.py --full --force-sharded --steps 20 --warmup 5 --fit-iters 0 --host-path-steps 0 --no-cpu-baseline \
     > $out/bench_sh1.log 2>&1 || exit $?
 timeout -k 10 300 python tools/shard_sim_bench.py --ranks 8 --reps 2 > $out/sim8.log 2>&1 || exit $?
 grep -h -o '"config": {"workload": "[^"]*\|"ms_per_step": [0-9.]*' $out/bench_c2.log $out/bench_c5.log $out/bench_sh1.log >&2
