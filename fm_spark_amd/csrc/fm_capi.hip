@@ -72,6 +72,41 @@ static void parallel_chunks(int64_t n, int64_t min_per_thread, F&& f) {
   parallel_chunks_t(n, chunk_count(n, min_per_thread), [&](int64_t, int64_t lo, int64_t hi) { f(lo, hi); });
 }
 
+// rows[n] of a dataset of Bd rows (hrp: its host row_ptr) -> hrows[n] (the rows, copied) and rp[n + 1],
+// the selection's own row_ptr; false when a row is outside [0, Bd).  Random reads of the dataset's
+// row_ptr, about 2 ms for 256K rows on one thread -- longer than the GPU step -- so on the pool's
+// threads: each chunk's running lengths, then the chunks' offsets.
+static bool selection_row_ptr(const int64_t* hrp, int64_t Bd, const int64_t* rows, int64_t n, int64_t* hrows,
+                              int64_t* rp) {
+  rp[0] = 0;
+  const int64_t T = chunk_count(n, 8192);
+  std::vector<int64_t> tot(T + 1, 0);
+  std::atomic<int> bad{0};
+  parallel_chunks_t(n, T, [&](int64_t t, int64_t lo, int64_t hi) {
+    int64_t acc = 0;
+    for (int64_t i = lo; i < hi; ++i) {
+      const int64_t r = rows[i];
+      if (r < 0 || r >= Bd) {
+        bad.store(1);
+        return;
+      }
+      hrows[i] = r;
+      acc += hrp[r + 1] - hrp[r];
+      rp[i + 1] = acc;
+    }
+    tot[t + 1] = acc;
+  });
+  if (bad.load()) return false;
+  for (int64_t t = 0; t < T; ++t) tot[t + 1] += tot[t];  // the chunks' offsets
+  if (T > 1)
+    parallel_chunks_t(n, T, [&](int64_t t, int64_t lo, int64_t hi) {
+      const int64_t add = tot[t];
+      if (add)
+        for (int64_t i = lo; i < hi; ++i) rp[i + 1] += add;
+    });
+  return true;
+}
+
 // Host CSR -> pinned staging [row_ptr int64 B+1][label f64 B][xoff int32 B][col u32 N][x f32 N]:
 // values that round to 1.0f (one-hot / categorical fields) are not sent -- the id's bit 31 (free:
 // ids are non-negative int32) marks an entry whose fp32 value follows in the x area, and xoff[i]
@@ -84,11 +119,12 @@ static void parallel_chunks(int64_t n, int64_t min_per_thread, F&& f) {
 struct Staged {
   int64_t B = 0, N = 0, M = 0, max_id = -1, max_len = 0;
   size_t o_lab = 0, o_xoff = 0, o_col = 0, o_x = 0, bytes = 0;  // bytes: the image through col
+  size_t o_extra = 0;  // the caller's `extra` bytes of staging, behind the x area
   int nruns = 0;
   int64_t run_at[16] = {0}, run_n[16] = {0};  // packed value runs in the x area (floats)
 };
 
-static Staged stage_csr(fm_ctx* ctx, const fm_csr* c, bool check_range, Pinned& pin) {
+static Staged stage_csr(fm_ctx* ctx, const fm_csr* c, bool check_range, Pinned& pin, size_t extra = 0) {
   FM_REQUIRE(c != nullptr, "null fm_csr");
   FM_REQUIRE(c->n_rows >= 0 && c->nnz >= 0, "negative n_rows / nnz");
   FM_REQUIRE(c->n_rows < (int64_t(1) << 31), "n_rows must be < 2^31");
@@ -110,7 +146,8 @@ static Staged stage_csr(fm_ctx* ctx, const fm_csr* c, bool check_range, Pinned& 
   g.o_xoff = g.o_lab + sizeof(double) * B;
   g.o_col = (g.o_xoff + sizeof(int32_t) * B + 15) / 16 * 16;
   g.o_x = (g.o_col + sizeof(uint32_t) * N + 15) / 16 * 16;
-  pin.ensure_slack(g.o_x + sizeof(float) * N + 16);  // M <= N
+  g.o_extra = (g.o_x + sizeof(float) * N + 16 + 15) / 16 * 16;  // M <= N
+  pin.ensure_slack(g.o_extra + extra);
   char* base = reinterpret_cast<char*>(pin.p);
   int64_t* rp = reinterpret_cast<int64_t*>(base);
   double* lab = reinterpret_cast<double*>(base + g.o_lab);
@@ -703,36 +740,8 @@ int fm_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows, i
     int64_t* hrows = reinterpret_cast<int64_t*>(b->sel_pin.p);
     int64_t* rp = hrows + n;
     // the rows and their result row_ptr straight into the pinned staging, from the dataset's row_ptr
-    // (validated on the way): random reads of the dataset's row_ptr, about 2 ms for 256K rows on one
-    // thread -- longer than the GPU step -- so on the pool's threads, each chunk's running lengths,
-    // then the chunks' offsets
-    rp[0] = 0;
-    const int64_t* hrp = data->host_rp.data();
-    const int64_t T = chunk_count(n, 8192);
-    std::vector<int64_t> tot(T + 1, 0);
-    std::atomic<int> bad{0};
-    parallel_chunks_t(n, T, [&](int64_t t, int64_t lo, int64_t hi) {
-      int64_t acc = 0;
-      for (int64_t i = lo; i < hi; ++i) {
-        const int64_t r = rows[i];
-        if (r < 0 || r >= Bd) {
-          bad.store(1);
-          return;
-        }
-        hrows[i] = r;
-        acc += hrp[r + 1] - hrp[r];
-        rp[i + 1] = acc;
-      }
-      tot[t + 1] = acc;
-    });
-    FM_REQUIRE(!bad.load(), "row index out of [0, rows of data)");
-    for (int64_t t = 0; t < T; ++t) tot[t + 1] += tot[t];  // the chunks' offsets
-    if (T > 1)
-      parallel_chunks_t(n, T, [&](int64_t t, int64_t lo, int64_t hi) {
-        const int64_t add = tot[t];
-        if (add)
-          for (int64_t i = lo; i < hi; ++i) rp[i + 1] += add;
-      });
+    // (validated on the way)
+    FM_REQUIRE(selection_row_ptr(data->host_rp.data(), Bd, rows, n, hrows, rp), "row index out of [0, rows of data)");
     const int64_t N = rp[n];
     FM_REQUIRE(N < (int64_t(1) << 31), "nnz must be < 2^31 per batch");
     // batch-only work on the copy stream, behind every queued step that reads this batch: the copy
@@ -791,6 +800,67 @@ int fm_batch_create_splits(fm_ctx* ctx, const fm_csr* csr, int32_t n_splits, con
     launch_split_rebase(b->dev, dsr.as<int64_t>(), n_splits, b->split_rp.as<int64_t>(), ctx->stream);
     FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     dsr.release();
+    *out = b.release();
+    return FM_OK;
+  });
+}
+
+int fm_batch_layout_splits(fm_ctx* ctx, const fm_csr* csr, int32_t n_splits, const int64_t* split_rows,
+                           const int64_t* order, fm_batch** out) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(out != nullptr && csr != nullptr, "null argument");
+    FM_REQUIRE(n_splits >= 1 && split_rows != nullptr, "n_splits must be >= 1");
+    FM_REQUIRE(split_rows[0] == 0, "split_rows must start at 0");
+    for (int32_t i = 0; i < n_splits; ++i) FM_REQUIRE(split_rows[i] <= split_rows[i + 1], "split_rows must be non-decreasing");
+    const int64_t n = split_rows[n_splits];  // laid-out rows
+    FM_REQUIRE(n < (int64_t(1) << 31), "laid-out rows must be < 2^31");
+    FM_REQUIRE(n == 0 || order != nullptr, "null order");
+    if (ctx->group) return group_batch_layout_splits(ctx, csr, n_splits, split_rows, order, out);
+    std::unique_ptr<fm_batch> b(new fm_batch());
+    FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the staging may still feed queued work
+    // the source in its own row order, staged as any upload (validated on the way), and behind it
+    // {order [n], the laid-out row_ptr [n + 1], split_rows [n_splits + 1]}
+    const size_t extra = sizeof(int64_t) * (2 * (size_t)n + 1 + (size_t)n_splits + 1);
+    const Staged g = stage_csr(ctx, csr, true, ctx->up_pin, extra);
+    const int64_t D = g.B;
+    int64_t* hord = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ctx->up_pin.p) + g.o_extra);
+    int64_t* rp = hord + n;
+    int64_t* hsr = rp + n + 1;
+    FM_REQUIRE(selection_row_ptr(csr->row_ptr, D, order, n, hord, rp), "row index out of [0, n_rows of csr)");
+    const int64_t N = rp[n];  // laid-out entries
+    FM_REQUIRE(N < (int64_t(1) << 31), "nnz must be < 2^31 per batch");
+    std::copy(split_rows, split_rows + n_splits + 1, hsr);
+    hipStream_t st = ctx->stream;
+    b->owner = ctx;
+    b->device = ctx->cfg.device;
+    b->max_id = g.max_id;
+    b->dev.n_rows = n;
+    b->dev.nnz = N;
+    b->dev.row_ptr.ensure_slack(sizeof(int64_t) * (n + 1));
+    b->dev.col.ensure_slack(sizeof(uint32_t) * std::max<int64_t>(N, 4) + 16);
+    b->dev.ent.ensure_slack(sizeof(uint32_t) * 2 * std::max<int64_t>(N, 4) + 16);
+    b->dev.xs.ensure_slack(sizeof(float) * std::max<int64_t>(N, 4) + 16);
+    b->dev.label.ensure_slack(sizeof(double) * std::max<int64_t>(n, 4) + 16);
+    b->split_rp.ensure(sizeof(int64_t) * (n + n_splits));
+    // the image's copies as copy_staged makes them: through col, then the packed value runs
+    b->up.ensure(g.o_extra + extra);
+    char* up = b->up.as<char>();
+    const char* pin = reinterpret_cast<const char*>(ctx->up_pin.p);
+    FM_HIP_CHECK(hipMemcpyAsync(up, pin, g.bytes, hipMemcpyHostToDevice, st));
+    for (int r = 0; r < g.nruns; ++r)
+      if (g.run_n[r] > 0)
+        FM_HIP_CHECK(hipMemcpyAsync(up + g.o_x + sizeof(float) * g.run_at[r], pin + g.o_x + sizeof(float) * g.run_at[r],
+                                    sizeof(float) * g.run_n[r], hipMemcpyHostToDevice, st));
+    FM_HIP_CHECK(hipMemcpyAsync(up + g.o_extra, pin + g.o_extra, extra, hipMemcpyHostToDevice, st));
+    const int64_t* dord = reinterpret_cast<const int64_t*>(up + g.o_extra);
+    launch_layout_splits(reinterpret_cast<const int64_t*>(up), reinterpret_cast<const double*>(up + g.o_lab),
+                         reinterpret_cast<const int32_t*>(up + g.o_xoff), reinterpret_cast<const uint32_t*>(up + g.o_col),
+                         reinterpret_cast<const float*>(up + g.o_x), dord, dord + n, dord + 2 * n + 1, n_splits, n, b->dev,
+                         b->split_rp.as<int64_t>(), st);
+    b->host_rp.assign(rp, rp + n + 1);
+    b->split_rows.assign(split_rows, split_rows + n_splits + 1);
+    FM_HIP_CHECK(hipStreamSynchronize(st));
+    b->up.release();  // the source's image: the laid-out dataset alone stays resident
     *out = b.release();
     return FM_OK;
   });

@@ -431,6 +431,8 @@ int group_batch_prepare(fm_ctx* ctx, fm_batch* b);
 int group_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows, int64_t n, fm_batch** out);
 int group_batch_create_splits(fm_ctx* ctx, const fm_csr* csr, int32_t n_splits, const int64_t* split_rows,
                               fm_batch** out);
+int group_batch_layout_splits(fm_ctx* ctx, const fm_csr* csr, int32_t n_splits, const int64_t* split_rows,
+                              const int64_t* order, fm_batch** out);
 int group_batch_split_view(fm_ctx* ctx, const fm_batch* data, int32_t split, fm_batch** out);
 int group_step(fm_ctx* ctx, const fm_csr* csr, int32_t t, double step_size, double reg_param, fm_step_out* out);
 int group_step_batch(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_param, fm_step_out* out);

@@ -1292,6 +1292,47 @@ int group_batch_create_splits(fm_ctx* ctx, const fm_csr* c, int32_t n_splits, co
   return FM_OK;
 }
 
+// fm_batch_layout_splits: the same dataset from the source in its own row order.  Local rank l's share
+// of every split, cut as group_batch_create_splits cuts it, is a row list of its own (the shares of
+// `order`) with its own split offsets: the member lays it out on its device from the whole source,
+// so no per-rank sub-CSR is assembled on the host.  Every member stages the source itself (DESIGN.md
+// section 6).
+int group_batch_layout_splits(fm_ctx* ctx, const fm_csr* c, int32_t n_splits, const int64_t* split_rows,
+                              const int64_t* order, fm_batch** out) {
+  Group& g = grp(ctx);
+  std::unique_ptr<fm_batch> b(new_group_batch(ctx));
+  GroupBatch& gb = *b->grp;
+  gb.parts.resize(g.L);
+  gb.rows = split_rows[n_splits];
+  gb.nnz = 0;
+  std::vector<std::vector<int64_t>> rows(g.L, std::vector<int64_t>(1));
+  std::vector<int64_t> ord, msr;
+  for (int l = 0; l < g.L; ++l) {
+    ord.clear();
+    msr.assign(1, 0);
+    for (int32_t s = 0; s < n_splits; ++s) {
+      const int64_t ns = split_rows[s + 1] - split_rows[s];
+      const int64_t a = split_rows[s] + ns * l / g.L, z = split_rows[s] + ns * (l + 1) / g.L;
+      ord.insert(ord.end(), order + a, order + z);
+      msr.push_back((int64_t)ord.size());
+    }
+    GPart& p = gb.parts[l];
+    mcheck(fm_batch_layout_splits(g.ranks[l].m, c, n_splits, msr.data(), ord.data(), &p.b), "fm_batch_layout_splits");
+    p.device = g.ranks[l].device;
+    p.rows = (int64_t)ord.size();
+    p.row0 = 0;  // its rows are not one range of the dataset (the dataset is not predicted as a whole)
+    p.nnz = fm_batch_nnz(p.b);
+    gb.nnz += p.nnz;
+    rows[l][0] = p.rows;
+  }
+  const std::vector<int64_t> all = allgather(g, rows, 1);
+  gb.global_rows = std::accumulate(all.begin(), all.end(), int64_t(0));
+  b->split_rows.assign(split_rows, split_rows + n_splits + 1);
+  sync_group_batch_view(b.get());
+  *out = b.release();
+  return FM_OK;
+}
+
 // Split s of a group dataset: every local rank's view of its own share (fm_batch_split_view); no copy.
 int group_batch_split_view(fm_ctx* ctx, const fm_batch* data, int32_t split, fm_batch** out) {
   Group& g = grp(ctx);

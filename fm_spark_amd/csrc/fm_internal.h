@@ -238,6 +238,13 @@ void launch_count_present(const TableView& T, int64_t* out, hipStream_t st);
 void launch_explode(const int64_t* row_ptr_in, const double* label_in, const int32_t* xoff, const uint32_t* col_in,
                     const float* x_in, int64_t B, int64_t N, int64_t* row_ptr, double* label, uint32_t* col, uint2* ent,
                     float* xs, hipStream_t st);
+// fm_batch_layout_splits: the uploaded CSR image of the source (as launch_explode takes it) -> dst
+// row s = source row order[s] (device order[B]), laid out split after split: row_ptr_in[B + 1]
+// (device) is the result's row_ptr, computed by the host; split_rows [n_splits + 1] (device);
+// split_rp [B + n_splits] and the entries' sample indices as launch_split_rebase leaves them
+void launch_layout_splits(const int64_t* src_row_ptr, const double* src_label, const int32_t* xoff, const uint32_t* col_in,
+                          const float* x_in, const int64_t* order, const int64_t* row_ptr_in, const int64_t* split_rows,
+                          int32_t n_splits, int64_t B, BatchDev& dst, int64_t* split_rp, hipStream_t st);
 
 // fm_batch_from_rows: dst row s = src row rows[s] (device rows[B]); row_ptr_in[B + 1] (device) is the
 // result's row_ptr, computed by the host from the source's

@@ -1648,6 +1648,65 @@ __global__ __launch_bounds__(kBlock) void k_explode(const int64_t* __restrict__ 
   }
 }
 
+// fm_batch_layout_splits: the cached dfData in its own row order (the uploaded image, as k_explode
+// reads it) -> the dataset laid out split after split (FactorizationMachinesSGD.scala:93, 111-112),
+// in one pass: laid-out row s is source row order[s].  One team of 16 lanes per laid-out row finds
+// its split (the binary search of k_split_rebase), reads the source row's ids straight from the
+// image -- a valued entry's x at xoff[row] + its rank among the row's valued entries (team ballot,
+// carried across the row's 16-entry trips, as k_explode) -- and writes col, xs, ent = {s - its
+// split's first row, x bits}, label, row_ptr (rp_in, computed by the host) and the split's rebased
+// row_ptr slots in split_rp (zeroed beforehand: an empty split's one slot stays 0).  What
+// k_explode + k_select_rows + k_split_rebase would write, without the exploded source between them.
+__global__ __launch_bounds__(kBlock) void k_layout_splits(const int64_t* __restrict__ src_rp, const double* __restrict__ src_lab,
+                                                         const int32_t* __restrict__ xoff, const uint32_t* __restrict__ col_in,
+                                                         const float* __restrict__ x_in, const int64_t* __restrict__ order,
+                                                         const int64_t* __restrict__ rp_in,
+                                                         const int64_t* __restrict__ split_rows, int32_t n_splits, int64_t B,
+                                                         int64_t* __restrict__ rp, double* __restrict__ lab,
+                                                         uint32_t* __restrict__ col, uint2* __restrict__ ent,
+                                                         float* __restrict__ xs, int64_t* __restrict__ split_rp) {
+  constexpr int T = 16;
+  const int tl = threadIdx.x % T;
+  const int lane = threadIdx.x & 63;
+  const uint64_t team_bits = 0xFFFFull << (lane & ~(T - 1));
+  const uint64_t below = team_bits & ((1ull << lane) - 1ull);
+  const int64_t gtid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t nthreads = (int64_t)gridDim.x * kBlock;
+  if (gtid == 0) rp[B] = rp_in[B];
+  for (int64_t s = gtid / T; s < B; s += nthreads / T) {
+    int lo = 0, hi = n_splits;  // the split holding row s: split_rows[lo] <= s < split_rows[lo + 1]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) / 2;
+      if (split_rows[mid] <= s) lo = mid;
+      else hi = mid;
+    }
+    const int64_t r0 = split_rows[lo], eb = rp_in[r0];
+    const int64_t e0 = rp_in[s], e1 = rp_in[s + 1];
+    const int64_t src = order[s];
+    const int64_t d = src_rp[src] - e0;  // source entry of laid-out entry e: e + d
+    int64_t xo = xoff[src];
+    if (tl == 0) {
+      rp[s] = e0;
+      lab[s] = src_lab[src];
+      split_rp[s + lo] = e0 - eb;
+      if (s + 1 == split_rows[lo + 1]) split_rp[s + 1 + lo] = e1 - eb;
+    }
+    for (int64_t eb16 = e0; eb16 < e1; eb16 += T) {  // the team's lanes take the same trips
+      const int64_t e = eb16 + tl;
+      const uint32_t c = e < e1 ? col_in[e + d] : 0u;
+      const bool valued = (c >> 31) != 0u;
+      const uint64_t m = __ballot(valued);
+      const float x = valued ? x_in[xo + __popcll(m & below)] : 1.0f;
+      xo += __popcll(m & team_bits);
+      if (e < e1) {
+        col[e] = c & 0x7FFFFFFFu;
+        ent[e] = make_uint2((uint32_t)(s - r0), __float_as_uint(x));
+        xs[e] = x;
+      }
+    }
+  }
+}
+
 // fm_batch_from_rows: output row s is row rows[s] of a resident dataset (the randomSplit split of
 // the cached dfData, FactorizationMachinesSGD.scala:93, 111-112).  One team of 16 lanes per output
 // row copies the source row's ids and fp32 x (8 B per entry, contiguous) and writes the exploded
@@ -1912,6 +1971,17 @@ void launch_explode(const int64_t* row_ptr_in, const double* label_in, const int
   (void)N;
   hipLaunchKernelGGL(k_explode, dim3(grid_for(std::max<int64_t>(B, 1) * 16, kBlock, 256 * 8)), dim3(kBlock), 0, st,
                      row_ptr_in, label_in, xoff, col_in, x_in, B, row_ptr, label, col, ent, xs);
+  FM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_layout_splits(const int64_t* src_row_ptr, const double* src_label, const int32_t* xoff, const uint32_t* col_in,
+                          const float* x_in, const int64_t* order, const int64_t* row_ptr_in, const int64_t* split_rows,
+                          int32_t n_splits, int64_t B, BatchDev& dst, int64_t* split_rp, hipStream_t st) {
+  FM_HIP_CHECK(hipMemsetAsync(split_rp, 0, sizeof(int64_t) * (B + n_splits), st));
+  hipLaunchKernelGGL(k_layout_splits, dim3(grid_for(std::max<int64_t>(B, 1) * 16, kBlock, 256 * 8)), dim3(kBlock), 0, st,
+                     src_row_ptr, src_label, xoff, col_in, x_in, order, row_ptr_in, split_rows, n_splits, B,
+                     dst.row_ptr.as<int64_t>(), dst.label.as<double>(), dst.col.as<uint32_t>(), dst.ent.as<uint2>(),
+                     dst.xs.as<float>(), split_rp);
   FM_HIP_CHECK(hipGetLastError());
 }
 

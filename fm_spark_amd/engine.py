@@ -229,6 +229,24 @@ class FMContext:
         b.split_rows = sr
         return b
 
+    def batch_layout_splits(self, csr: N.CSRHost, split_rows, order) -> DeviceBatch:
+        """The dataset batch_splits makes of rows `order` of csr, laid out on the device from csr in its
+        own row order (fm_batch_layout_splits): laid-out row i = row order[i] of csr, split s = laid-out
+        rows [split_rows[s], split_rows[s + 1]); no permuted host copy is built."""
+        sr = np.ascontiguousarray(split_rows, dtype=np.int64)
+        od = np.ascontiguousarray(order, dtype=np.int64)
+        if len(sr) < 2 or len(od) != sr[-1]:
+            raise ValueError("order must hold split_rows[-1] row indices")
+        b = DeviceBatch(self, None)
+        h = C.c_void_p()
+        N.check(self._lib.fm_batch_layout_splits(self.handle, C.byref(csr.c), len(sr) - 1, N.ptr(sr, C.c_int64),
+                                                 N.ptr(od, C.c_int64), C.byref(h)), "fm_batch_layout_splits")
+        b.handle = h
+        b.n_rows = int(self._lib.fm_batch_rows(h))
+        b.nnz = int(self._lib.fm_batch_nnz(h))
+        b.split_rows = sr
+        return b
+
     def split_view(self, data: DeviceBatch, split: int, into: DeviceBatch | None = None) -> DeviceBatch:
         """Split `split` of a dataset made by batch_splits as a mini-batch, in place (fm_batch_split_view);
         `into` (a view of this context) is re-pointed instead of creating one."""

@@ -393,11 +393,12 @@ class FactorizationMachinesSGD:
         if pipelined and len(labels):
             # dfData.cache() (:93): the exploded dataset uploaded once, laid out split after split (the
             # rows no split samples last, for createInitialModel), so every iteration's mini-batch is a
-            # contiguous range of it, stepped in place (fm_batch_split_view)
+            # contiguous range of it, stepped in place (fm_batch_split_view); it crosses PCIe in its own
+            # row order and the device lays it out (fm_batch_layout_splits): no permuted host copy
             rest = order[split_of[order] < 0]
             lay = np.concatenate(splits + [rest]).astype(np.int64)
             split_rows = np.concatenate([[0], np.cumsum([len(r) for r in splits] + [len(rest)])])
-            data = ctx.batch_splits(_select_csr(rp, col, val, labels, lay), split_rows)
+            data = ctx.batch_layout_splits(N.CSRHost(rp, col, val, labels), split_rows, lay)
         elif initial_tables is None and len(labels):
             data = ctx.batch(N.CSRHost(rp, col, val, labels))
         if initial_tables is not None:

@@ -219,6 +219,21 @@ int fm_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows, i
  * dataset is on the device). */
 int fm_batch_create_splits(fm_ctx* ctx, const fm_csr* csr, int32_t n_splits, const int64_t* split_rows,
                            fm_batch** out);
+/* The same dataset built from the cached dfData in its own row order
+ * (FactorizationMachinesSGD.scala:93, 111-112): csr holds the D = csr->n_rows rows as they were
+ * collected, order [n_out] the source row of every laid-out row (row i = row order[i] of csr; any order, repeats allowed, rows may be left out,
+ * as the rows of fm_batch_from_rows) and split_rows [n_splits + 1] the split offsets over the laid-out
+ * rows (non-decreasing from 0; n_out = split_rows[n_splits] < 2^31, laid-out entries < 2^31).  The
+ * source crosses PCIe once in the compact upload form and the device lays it out in one pass (no
+ * permuted host copy is made); the result is the dataset fm_batch_create_splits makes of the host CSR
+ * of rows order[0 .. n_out) -- the same device arrays bit for bit -- under the same rules (stepped
+ * through fm_batch_split_view; accepted by fm_init_from_batch and by fm_batch_from_rows, where row i
+ * is laid-out row i).  csr is validated as fm_batch_create validates it; an index of order outside
+ * [0, D) is FM_ERR_ARG ("row index out of ...").  A multi-GPU context hands every local rank the
+ * source and that rank's share of every split's rows, cut as fm_batch_create_splits cuts them.
+ * Synchronous (returns when the dataset is on the device; the source's image is freed by then). */
+int fm_batch_layout_splits(fm_ctx* ctx, const fm_csr* csr, int32_t n_splits, const int64_t* split_rows,
+                           const int64_t* order, fm_batch** out);
 /* Split `split` of a dataset made by fm_batch_create_splits as a mini-batch: its rows, entries and
  * labels where they lie in data (borrowed -- data must outlive the view and every step queued on
  * it).  *out == NULL: a new batch; otherwise *out is re-pointed in place.  Re-pointing a view is
