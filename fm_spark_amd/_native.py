@@ -20,6 +20,7 @@ FM_PARALLEL_NONE, FM_PARALLEL_SHARDED, FM_PARALLEL_REPLICATED = 0, 1, 2
 FM_TRANSPORT_AUTO, FM_TRANSPORT_RCCL, FM_TRANSPORT_COPY = 0, 1, 2
 FM_MAX_LOCAL = 16
 FM_FUSE_DEFAULT, FM_FUSE_ON, FM_FUSE_OFF = 0, 1, -1
+FM_WIRE_FP32, FM_WIRE_FP64 = 0, 1
 
 
 class FMError(RuntimeError):
@@ -45,6 +46,7 @@ class fm_config(C.Structure):
         ("comm_id", C.c_uint8 * 128),
         ("fuse_single", C.c_int32),
         ("xchg_chunks", C.c_int32),
+        ("wire", C.c_int32),
     ]
 
 

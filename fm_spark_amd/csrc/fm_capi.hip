@@ -397,6 +397,9 @@ const char* fm_last_error(void) { return g_last_error.c_str(); }
 int fm_create(const fm_config* cfg, fm_ctx** out) {
   return guarded_free([&]() -> int {
     FM_REQUIRE(cfg && out, "null argument");
+    FM_REQUIRE(cfg->wire == FM_WIRE_FP32 || cfg->wire == FM_WIRE_FP64, "wire must be FM_WIRE_FP32 or FM_WIRE_FP64");
+    FM_REQUIRE(cfg->wire != FM_WIRE_FP64 || cfg->parallel != FM_PARALLEL_REPLICATED,
+               "wire = FM_WIRE_FP64 applies to the sharded step only: the replicated gradient all-reduce is fp32");
     if (cfg->parallel != FM_PARALLEL_NONE) return group_create(cfg, out);  // several ranks (fm_group.hip)
     FM_REQUIRE(cfg->num_features >= 1 && cfg->num_features <= (int64_t(1) << 31), "num_features must be in [1, 2^31]");
     FM_REQUIRE(cfg->k >= 1 && cfg->k <= 256, "dimFactorization must be in [1, 256]");

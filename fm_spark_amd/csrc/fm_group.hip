@@ -355,6 +355,7 @@ struct A2APlan {
 // All-to-all-v of one or more segments with the same plan between the job's ranks, on `lane`;
 // with RCCL every segment's sends and receives go in one group.
 void a2a_plan(Group& g, int lane, const std::vector<A2ASeg>& segs, const A2APlan& pl) {
+  for (const A2ASeg& s : segs) FM_REQUIRE(s.esize % 4 == 0, "a2a: element size must be a multiple of 4 bytes (k_copy_list)");
   if (g.rccl) {
     // the block a rank keeps for itself is a device copy on its own stream, not a send to itself
     // through RCCL's channel buffers
@@ -690,9 +691,10 @@ void prefetch(Group& g, GroupBatch& gb) {
   finish_routes(g, gb);
 }
 
-// the pair buffers of one direction in the wire layout: [P][kp] fp32 vectors, then [P][2] fp32
-// scalars -- two all-to-alls with the same pair counts
-void a2a_pairs(Group& g, int kp, const std::vector<DevBuf*>& send, const std::vector<int64_t>& sendP,
+// the pair buffers of one direction in the wire layout: [P][kp] vectors, then [P][2] scalars, words
+// of esz bytes (the S direction fp32; the partial direction the context's wire, wire_bytes) -- two
+// all-to-alls with the same pair counts
+void a2a_pairs(Group& g, int kp, size_t esz, const std::vector<DevBuf*>& send, const std::vector<int64_t>& sendP,
                const std::vector<DevBuf*>& recv, const std::vector<int64_t>& recvP,
                const std::vector<const int64_t*>& out, const std::vector<const int64_t*>& in) {
   const int L = g.L;
@@ -700,11 +702,11 @@ void a2a_pairs(Group& g, int kp, const std::vector<DevBuf*>& send, const std::ve
   std::vector<char*> rv(L), rc(L);
   for (int l = 0; l < L; ++l) {
     sv[l] = send[l]->as<char>();
-    sc[l] = send[l]->as<char>() + sizeof(float) * sendP[l] * kp;
+    sc[l] = send[l]->as<char>() + esz * sendP[l] * kp;
     rv[l] = recv[l]->as<char>();
-    rc[l] = recv[l]->as<char>() + sizeof(float) * recvP[l] * kp;
+    rc[l] = recv[l]->as<char>() + esz * recvP[l] * kp;
   }
-  a2a_multi(g, false, {A2ASeg{sv, rv, sizeof(float) * kp}, A2ASeg{sc, rc, sizeof(float) * 2}}, out, in);
+  a2a_multi(g, false, {A2ASeg{sv, rv, esz * kp}, A2ASeg{sc, rc, esz * 2}}, out, in);
 }
 
 // per-step stats rows of the members (loss, loss rows, distinct ids) at epoch index e -> the job's
@@ -748,6 +750,10 @@ void fill_out(Group& g, fm_ctx* ctx, int64_t e, int64_t global_rows, fm_step_out
 }
 
 
+// Bytes per word of the partial direction (owner -> requester): fm_config.wire, which the members
+// were created with too (their partial pass and combine read it from their own configuration).
+size_t wire_bytes(const fm_ctx* ctx) { return ctx->cfg.wire == FM_WIRE_FP64 ? sizeof(double) : sizeof(float); }
+
 // Chunks of the owners' partial pass whose exchange overlaps the next chunk's compute
 // (fm_config.xchg_chunks, default 4; 1 = one pass, then one all-to-all).  Only with R > 1.
 int xchg_chunks(const Group& g) {
@@ -767,7 +773,7 @@ void ensure_xchg(Group& g) {
 // The owners' partial pass in C chunks, each chunk's partial rows sent to their requesters on the
 // exchange stream while the next chunk is computed.  Chunk c of the P pairs of a (owner, requester)
 // block is [P c / C, P (c + 1) / C) on both sides (the owner's pair_in[p] = the requester's pair_out[o]).
-void forward_exchange_chunked(Group& g, GroupBatch& gb, int kp, int C, const std::vector<int64_t>& Pin,
+void forward_exchange_chunked(Group& g, GroupBatch& gb, int kp, size_t esz, int C, const std::vector<int64_t>& Pin,
                               const std::vector<int64_t>& Pout) {
   const int L = g.L, R = g.R;
   ensure_xchg(g);
@@ -776,9 +782,9 @@ void forward_exchange_chunked(Group& g, GroupBatch& gb, int kp, int C, const std
   for (int l = 0; l < L; ++l) {
     Rank& r = g.ranks[l];
     sv[l] = r.partials.as<char>();
-    sc[l] = r.partials.as<char>() + sizeof(float) * Pin[l] * kp;
+    sc[l] = r.partials.as<char>() + esz * Pin[l] * kp;
     rv[l] = r.part_in.as<char>();
-    rc[l] = r.part_in.as<char>() + sizeof(float) * Pout[l] * kp;
+    rc[l] = r.part_in.as<char>() + esz * Pout[l] * kp;
   }
   for (int c = 0; c < C; ++c) {
     A2APlan pl;
@@ -791,7 +797,7 @@ void forward_exchange_chunked(Group& g, GroupBatch& gb, int kp, int C, const std
         FM_HIP_CHECK(hipStreamWaitEvent(r.xstream, r.ev_fwd, 0));
       });
     });
-    a2a_plan(g, kLaneXchg, {A2ASeg{sv, rv, sizeof(float) * kp}, A2ASeg{sc, rc, sizeof(float) * 2}}, pl);
+    a2a_plan(g, kLaneXchg, {A2ASeg{sv, rv, esz * kp}, A2ASeg{sc, rc, esz * 2}}, pl);
   }
   for (auto& r : g.ranks) {  // the combine reads what the exchange stream received
     FM_HIP_CHECK(hipSetDevice(r.device));
@@ -803,6 +809,7 @@ void forward_exchange_chunked(Group& g, GroupBatch& gb, int kp, int C, const std
 int step_sharded(fm_ctx* ctx, Group& g, GroupBatch& gb, int32_t t, double step_size, double reg_param,
                  fm_step_out* out) {
   const int L = g.L, kp = ctx->kp, W = kp + 2;
+  const size_t pw = wire_bytes(ctx);  // the partial direction's word; the S direction is fp32
   prefetch(g, gb);
   std::vector<int64_t> Pin(L), Pout(L);
   std::vector<DevBuf*> parts(L), part_in(L), s_send(L), s_recv(L);
@@ -812,11 +819,11 @@ int step_sharded(fm_ctx* ctx, Group& g, GroupBatch& gb, int32_t t, double step_s
     GPart& p = gb.parts[l];
     Pin[l] = std::accumulate(p.pair_in.begin(), p.pair_in.end(), int64_t(0));
     Pout[l] = std::accumulate(p.pair_out.begin(), p.pair_out.end(), int64_t(0));
-    ensure_on(r.device, r.partials, sizeof(float) * Pin[l] * W);
+    ensure_on(r.device, r.partials, pw * Pin[l] * W);
     ensure_on(r.device, r.s_send, sizeof(float) * Pout[l] * W);
     if (g.R > 1) {  // a one-rank job keeps its pairs where they were written (below)
       ensure_on(r.device, r.s_recv, sizeof(float) * Pin[l] * W);
-      ensure_on(r.device, r.part_in, sizeof(float) * Pout[l] * W);
+      ensure_on(r.device, r.part_in, pw * Pout[l] * W);
     }
     parts[l] = &r.partials;
     part_in[l] = &r.part_in;
@@ -834,14 +841,14 @@ int step_sharded(fm_ctx* ctx, Group& g, GroupBatch& gb, int32_t t, double step_s
   {
     HostClock hc(g, "host_forward_xchg");
     if (C > 1) {
-      forward_exchange_chunked(g, gb, kp, C, Pin, Pout);
+      forward_exchange_chunked(g, gb, kp, pw, C, Pin, Pout);
     } else {
       // owners: partial sums per received pair
       g.each([&](int l) {
         mcheck(fm_shard_owner_forward(g.ranks[l].m, gb.parts[l].b, g.ranks[l].partials.p), "fm_shard_owner_forward");
       });
       // back to the requesters (owner l -> requester p: the pair_in[l][p] pairs it got from p)
-      if (!self) a2a_pairs(g, kp, parts, Pin, part_in, Pout, pin, pout);
+      if (!self) a2a_pairs(g, kp, pw, parts, Pin, part_in, Pout, pin, pout);
     }
   }
   {
@@ -854,7 +861,7 @@ int step_sharded(fm_ctx* ctx, Group& g, GroupBatch& gb, int32_t t, double step_s
   // S rows to the owners
   if (!self) {
     HostClock hc(g, "host_s_xchg");
-    a2a_pairs(g, kp, s_send, Pout, s_recv, Pin, pout, pin);
+    a2a_pairs(g, kp, sizeof(float), s_send, Pout, s_recv, Pin, pout, pin);
   }
   {
     HostClock hc(g, "host_update");
@@ -940,6 +947,7 @@ int step_group_batch(fm_ctx* ctx, GroupBatch& gb, int32_t t, double step_size, d
 // predict epilogue per sample.  pred: host [gb.rows].
 void predict_sharded(fm_ctx* ctx, Group& g, GroupBatch& gb, double lo, double hi, double* pred) {
   const int L = g.L, kp = ctx->kp, W = kp + 2;
+  const size_t pw = wire_bytes(ctx);
   gb.prefetched = false;  // the route below replaces any pending training plan of this batch
   prefetch(g, gb);
   gb.prefetched = false;
@@ -953,8 +961,8 @@ void predict_sharded(fm_ctx* ctx, Group& g, GroupBatch& gb, double lo, double hi
     GPart& p = gb.parts[l];
     Pin[l] = std::accumulate(p.pair_in.begin(), p.pair_in.end(), int64_t(0));
     Pout[l] = std::accumulate(p.pair_out.begin(), p.pair_out.end(), int64_t(0));
-    ensure_on(r.device, r.partials, sizeof(float) * Pin[l] * W);
-    ensure_on(r.device, r.part_in, sizeof(float) * Pout[l] * W);
+    ensure_on(r.device, r.partials, pw * Pin[l] * W);
+    ensure_on(r.device, r.part_in, pw * Pout[l] * W);
     ensure_on(r.device, r.pc_out, sizeof(uint32_t) * Pin[l]);
     ensure_on(r.device, r.pc_in, sizeof(uint32_t) * Pout[l]);
     ensure_on(r.device, r.pred, sizeof(double) * p.rows);
@@ -966,7 +974,7 @@ void predict_sharded(fm_ctx* ctx, Group& g, GroupBatch& gb, double lo, double hi
     cr[l] = r.pc_in.as<char>();
     on(r, [&] { shard_owner_partials(r.m, p.b, r.partials.p, r.pc_out.as<uint32_t>()); });
   }
-  a2a_pairs(g, kp, parts, Pin, part_in, Pout, pin, pout);
+  a2a_pairs(g, kp, pw, parts, Pin, part_in, Pout, pin, pout);
   a2a(g, false, cs, cr, pin, pout, sizeof(uint32_t));
   for (int l = 0; l < L; ++l) {
     Rank& r = g.ranks[l];

@@ -174,11 +174,12 @@ struct FwdOut {
 };
 constexpr int kMaxChunkSources = 64;  // sources a chunked partial pass can split
 // partial_out != nullptr: the sharded owner's partial pass (fm_shard.hip): [pairs][kp] fp32 vectors
-// followed by [pairs] float2 scalars (pred->pcount, if given: present rows per pair);
+// followed by [pairs] float2 scalars (pred->pcount, if given: present rows per pair); partial_wide:
+// the fp64 wire, [pairs][kp] doubles followed by [pairs] double2, at the same address;
 // else pred != nullptr: FactorizationMachinesModel.predict / calcLossGrad (p.w0, p.cumE used)
 void launch_forward(const TableView& T, const BatchDev& b, StepWork& w, const StepParams& p,
                     hipStream_t st, int64_t* n_fwd_blocks, float* partial_out = nullptr,
-                    const FwdOut* pred = nullptr);
+                    const FwdOut* pred = nullptr, bool partial_wide = false);
 // per-sample inputs of the segmented update: S rows of s_stride floats, {yhat, y} at yl[s * yl_stride]
 struct SegSource {
   const float* S;

@@ -81,6 +81,8 @@ __device__ __forceinline__ float gauss_draw(uint64_t seed, int64_t id, int f, do
 // MODE kPartial: the sharded owner's pass (fm_shard.hip).  "Samples" are (source rank, sample)
 // pairs of the entries this owner received; the output per pair is the partial vector
 // sum v*x (kp fp32, S_out) and the scalars {sum v^2 x^2, sum w*x} (yl_out) instead of S / yhat / loss.
+// MODE kPartial64: kPartial with the fp64 wire (fm_config.wire = FM_WIRE_FP64): the same sums stored
+// unrounded, S_out as [pair][kp] doubles and yl_out as [pair] double2 (strides in those elements).
 // MODE kPredict: FactorizationMachinesModel.predict (Model.scala:90-133): ids outside the table
 // or absent from the model are dropped (the inner joins, :103-112), a row left without a learned
 // feature scores globalBias unclamped (na.fill, :86), every other row
@@ -91,7 +93,7 @@ __device__ __forceinline__ float gauss_draw(uint64_t seed, int64_t id, int f, do
 // MODE kTrainFused: kTrain, and every row whose feature has exactly one entry in the batch (a
 // singleton: 92 % of a c3 batch's distinct rows) is updated here, by the sample that holds that
 // entry, instead of by the segmented update (see "Singleton rows" below).
-constexpr int kTrain = 0, kPartial = 1, kPredict = 2, kLossGrad = 3, kTrainFused = 4;
+constexpr int kTrain = 0, kPartial = 1, kPredict = 2, kLossGrad = 3, kTrainFused = 4, kPartial64 = 5;
 constexpr int kFuseNS = 5;    // kTrainFused: singleton rows per lane group and sample that wait in LDS
 constexpr int kPartialU = 4;  // sharded partial pass: passes (entries per lane) whose rows are in flight together
 // The step's forward (and predict / loss-grad): 32 lanes per sample, 2 passes in flight -- the
@@ -150,7 +152,7 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr,
                                                     float2* __restrict__ yl_out, int64_t sstr, int64_t ystr,
                                                     double2* __restrict__ loss_part,
                                                     FwdOut xo) {
-  constexpr bool PARTIAL = MODE == kPartial;
+  constexpr bool PARTIAL = MODE == kPartial || MODE == kPartial64;
   constexpr int RPP = TEAM / GS;  // entries per pass
   constexpr int TPB = kBlock / TEAM;
   const int tid = threadIdx.x;
@@ -352,10 +354,19 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr,
       if (MODE == kPredict || PARTIAL) npres += __shfl_xor(npres, o);
     }
     if (PARTIAL) {  // vectors [pair][kp] in S_out, scalars {sum v^2 x^2, sum w x} in yl_out
-      if (rs == 0 && qok)
-        *reinterpret_cast<float4*>(S_out + s * sstr + g * 4) = make_float4((float)a0, (float)a1, (float)a2, (float)a3);
+      if constexpr (MODE == kPartial64) {  // the fp64 wire: two 16-B stores per lane, one for the scalars
+        if (rs == 0 && qok) {
+          double2* so = reinterpret_cast<double2*>(reinterpret_cast<double*>(S_out) + s * sstr + g * 4);
+          so[0] = make_double2(a0, a1);
+          so[1] = make_double2(a2, a3);
+        }
+        if (tl == 0) reinterpret_cast<double2*>(yl_out)[s * ystr] = make_double2(vv, wx);
+      } else {
+        if (rs == 0 && qok)
+          *reinterpret_cast<float4*>(S_out + s * sstr + g * 4) = make_float4((float)a0, (float)a1, (float)a2, (float)a3);
+        if (tl == 0) yl_out[s * ystr] = make_float2((float)vv, (float)wx);
+      }
       if (tl == 0) {
-        yl_out[s * ystr] = make_float2((float)vv, (float)wx);
         if (xo.pcount) xo.pcount[s] = npres;
       }
       continue;
@@ -1358,7 +1369,7 @@ inline unsigned grid_for(int64_t n, int block, int64_t cap = 256 * 16) {
 
 template <int GS, int TEAM, int U>
 void launch_fwd_t(const TableView& T, const BatchDev& b, StepWork& w, const StepParams& p, hipStream_t st,
-                  int64_t* nblk, float* partial_out, const FwdOut* xo) {
+                  int64_t* nblk, float* partial_out, const FwdOut* xo, bool wide = false) {
   constexpr int TPB = kBlock / TEAM;
   int64_t blocks = (b.n_rows + TPB - 1) / TPB;
   if (blocks > kFwdGrid) blocks = kFwdGrid;
@@ -1366,6 +1377,17 @@ void launch_fwd_t(const TableView& T, const BatchDev& b, StepWork& w, const Step
   *nblk = blocks;
   const dim3 grid((unsigned)blocks), blk(kBlock);
   const FwdOut none{};
+  if (partial_out && wide) {  // the fp64 wire: [n_rows][kp] doubles, then [n_rows] double2
+    // (only the partial pass's own shapes carry the wide store: the step's U never reaches here)
+    if constexpr (U == kPartialU)
+      hipLaunchKernelGGL((k_forward<GS, TEAM, kPartial64, U>), grid, blk, 0, st, T, b.row_ptr.as<int64_t>(),
+                         b.col.as<uint32_t>(), b.ent.as<uint2>(), nullptr, nullptr, b.n_rows, p.w0, p.cumE, partial_out,
+                         reinterpret_cast<float2*>(reinterpret_cast<double*>(partial_out) + b.n_rows * T.kp), (int64_t)T.kp,
+                         (int64_t)1, nullptr, xo ? *xo : none);
+    else
+      FM_REQUIRE(false, "the fp64 partial store serves the partial pass only");
+    return;
+  }
   if (partial_out) {  // [n_rows][kp] fp32 vectors, then [n_rows] float2 scalars (xo: the present counts)
     hipLaunchKernelGGL((k_forward<GS, TEAM, kPartial, U>), grid, blk, 0, st, T, b.row_ptr.as<int64_t>(),
                        b.col.as<uint32_t>(), b.ent.as<uint2>(), nullptr, nullptr, b.n_rows, p.w0, p.cumE, partial_out,
@@ -1409,24 +1431,24 @@ void launch_fwd_t(const TableView& T, const BatchDev& b, StepWork& w, const Step
 // is sized so one round of U = 4 passes covers a segment, instead of 16 lanes per segment.
 template <int GS>
 void launch_partial_t(const TableView& T, const BatchDev& b, StepWork& w, const StepParams& p, hipStream_t st,
-                      int64_t* nblk, float* partial_out, const FwdOut* xo) {
+                      int64_t* nblk, float* partial_out, const FwdOut* xo, bool wide) {
   const double avg = b.n_rows > 0 ? (double)b.nnz / (double)b.n_rows : 0.0;
-  if (GS <= 16 && avg <= 4.0) launch_fwd_t<GS, GS, kPartialU>(T, b, w, p, st, nblk, partial_out, xo);
-  else if (GS <= 16 && avg <= 8.0) launch_fwd_t<GS, (2 * GS > 16 ? 16 : 2 * GS), kPartialU>(T, b, w, p, st, nblk, partial_out, xo);
-  else launch_fwd_t<GS, (GS > 16 ? GS : 16), kPartialU>(T, b, w, p, st, nblk, partial_out, xo);
+  if (GS <= 16 && avg <= 4.0) launch_fwd_t<GS, GS, kPartialU>(T, b, w, p, st, nblk, partial_out, xo, wide);
+  else if (GS <= 16 && avg <= 8.0) launch_fwd_t<GS, (2 * GS > 16 ? 16 : 2 * GS), kPartialU>(T, b, w, p, st, nblk, partial_out, xo, wide);
+  else launch_fwd_t<GS, (GS > 16 ? GS : 16), kPartialU>(T, b, w, p, st, nblk, partial_out, xo, wide);
 }
 
 void launch_forward(const TableView& T, const BatchDev& b, StepWork& w, const StepParams& p, hipStream_t st,
-                    int64_t* nblk, float* partial_out, const FwdOut* pred) {
+                    int64_t* nblk, float* partial_out, const FwdOut* pred, bool partial_wide) {
   const int nq = T.kp / 4;
   if (partial_out) {
-    if (nq <= 1) launch_partial_t<1>(T, b, w, p, st, nblk, partial_out, pred);
-    else if (nq <= 2) launch_partial_t<2>(T, b, w, p, st, nblk, partial_out, pred);
-    else if (nq <= 4) launch_partial_t<4>(T, b, w, p, st, nblk, partial_out, pred);
-    else if (nq <= 8) launch_partial_t<8>(T, b, w, p, st, nblk, partial_out, pred);
-    else if (nq <= 16) launch_partial_t<16>(T, b, w, p, st, nblk, partial_out, pred);
-    else if (nq <= 32) launch_fwd_t<32, 32, kPartialU>(T, b, w, p, st, nblk, partial_out, pred);
-    else if (nq <= 64) launch_fwd_t<64, 64, kPartialU>(T, b, w, p, st, nblk, partial_out, pred);
+    if (nq <= 1) launch_partial_t<1>(T, b, w, p, st, nblk, partial_out, pred, partial_wide);
+    else if (nq <= 2) launch_partial_t<2>(T, b, w, p, st, nblk, partial_out, pred, partial_wide);
+    else if (nq <= 4) launch_partial_t<4>(T, b, w, p, st, nblk, partial_out, pred, partial_wide);
+    else if (nq <= 8) launch_partial_t<8>(T, b, w, p, st, nblk, partial_out, pred, partial_wide);
+    else if (nq <= 16) launch_partial_t<16>(T, b, w, p, st, nblk, partial_out, pred, partial_wide);
+    else if (nq <= 32) launch_fwd_t<32, 32, kPartialU>(T, b, w, p, st, nblk, partial_out, pred, partial_wide);
+    else if (nq <= 64) launch_fwd_t<64, 64, kPartialU>(T, b, w, p, st, nblk, partial_out, pred, partial_wide);
     else FM_REQUIRE(false, "dimFactorization > 256 is not supported");
     FM_HIP_CHECK(hipGetLastError());
     return;

@@ -23,8 +23,9 @@
 //
 // Semantics equal the single-table step over the ranks' batches concatenated in rank order
 // (global miniBatchSize m = sum of the ranks' rows), up to fp summation order: the forward
-// sums are split per owner (fp32 on the wire), the per-feature gradient sums run over the
-// same entries in the same order.  Deterministic for a given R.
+// sums are split per owner (fp32 on the wire; with fm_config.wire = FM_WIRE_FP64 the shares cross
+// unrounded, so a sample's sums are fp64 over all of its entries, as the single table's), the
+// per-feature gradient sums run over the same entries in the same order.  Deterministic for a given R.
 // Traffic per rank and step (k = 16, z = 39, R = 8): entries 12 B each (off the critical path:
 // exchanged during the previous iteration), partials and S (kp + 2) * 4 B per (sample, owner)
 // pair -- about 2 x 150 MB, against about 1 GB when rows and gradients of every distinct id
@@ -32,10 +33,12 @@
 // Wire buffers are structures of arrays over the pairs, so every k-vector is 16-B aligned and a
 // 64-B row at k = 16: partials [P][kp] fp32 sum v*x then [P] fp32 {sum v^2 x^2, sum w x}; S [P][kp]
 // fp32 vfxiSum then [P] fp32 {r, yhat} (r = yhat - y formed in fp64 by the requester, then rounded).
+// FM_WIRE_FP64: the partials' words are fp64 (a 128-B row at k = 16, the scalars a double2); S is unchanged.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "fm_context.h"
 #include "fm_device.h"
@@ -281,6 +284,20 @@ __global__ __launch_bounds__(kBlock) void k_pair_table(const uint2* __restrict__
 }
 
 // ------------------------------------------------------------------ requester: combine
+// The partial direction's element type W: float (FM_WIRE_FP32) or double (FM_WIRE_FP64).
+template <typename W>
+using wire2 = std::conditional_t<std::is_same<W, double>::value, double2, float2>;
+// quad q of a partial row added to the lane's four fp64 column sums (fp64 words: two 16-B halves)
+__device__ __forceinline__ void add_quad(const float* __restrict__ row, int q, double& a0, double& a1, double& a2,
+                                         double& a3) {
+  const float4 t = reinterpret_cast<const float4*>(row)[q];
+  a0 += (double)t.x; a1 += (double)t.y; a2 += (double)t.z; a3 += (double)t.w;
+}
+__device__ __forceinline__ void add_quad(const double* __restrict__ row, int q, double& a0, double& a1, double& a2,
+                                         double& a3) {
+  const double2 lo = reinterpret_cast<const double2*>(row)[2 * q], hi = reinterpret_cast<const double2*>(row)[2 * q + 1];
+  a0 += lo.x; a1 += lo.y; a2 += hi.x; a3 += hi.y;
+}
 // Team of GS lanes per sample (one quad each): the owners' partials summed in owner order
 // in fp64 -> S = vfxiSum, yhat = 0.5 (|S|^2 - sum v^2 x^2) + sum w x + w0
 // (FactorizationMachinesModel.scala:221, :260-262), the loss partial (:230), and the S rows
@@ -288,13 +305,16 @@ __global__ __launch_bounds__(kBlock) void k_pair_table(const uint2* __restrict__
 // part_vec / s_vec [pair][kp], part_sc / s_sc [pair] float2 ({sum v^2 x^2, sum w x} / {yhat, y}).
 // OW > 0 (R <= OW owners): the sample's pair slots live in registers and every owner's loads of a
 // pass are issued before any is used (clamped owner indices; a pair the sample lacks reads poff's
-// first bytes and is masked out) -- as guarded loads, one per owner, each waited out its round trip
+// first bytes and is masked out; poff is allocated at least 32 B so every masked load, 16 B at the
+// most, stays inside it) -- as guarded loads, one per owner, each waited out its round trip
 // before the next: 2R + R round trips per sample.  OW = 0: any R up to kMaxR, owner by owner.
-template <int GS, int OW>
+// W = double: an owner's quad is loaded as two double2 halves, one half of every owner at a time, so
+// the loads in flight take the registers the fp32 quads take.
+template <int GS, int OW, typename W>
 __global__ __launch_bounds__(kBlock) void k_shard_combine(const int32_t* __restrict__ pairidx,
                                                           const int64_t* __restrict__ poff, int R, int64_t B,
-                                                          const float* __restrict__ part_vec,
-                                                          const float2* __restrict__ part_sc,
+                                                          const W* __restrict__ part_vec,
+                                                          const wire2<W>* __restrict__ part_sc,
                                                           const double* __restrict__ label, int kp, double w0,
                                                           float* __restrict__ s_vec, float2* __restrict__ s_sc,
                                                           double2* __restrict__ loss_part) {
@@ -315,11 +335,11 @@ __global__ __launch_bounds__(kBlock) void k_shard_combine(const int32_t* __restr
         ix[o] = pi[oc];
         pj[o] = poff[oc];
       }
-      float2 t[OW];
+      wire2<W> t[OW];
 #pragma unroll
       for (int o = 0; o < OW; ++o) {
         pj[o] = o < R && ix[o] >= 0 ? pj[o] + ix[o] : -1;
-        t[o] = *(pj[o] >= 0 ? part_sc + pj[o] : reinterpret_cast<const float2*>(poff));
+        t[o] = *(pj[o] >= 0 ? part_sc + pj[o] : reinterpret_cast<const wire2<W>*>(poff));
       }
 #pragma unroll
       for (int o = 0; o < OW; ++o) {  // owner order, as the loop below
@@ -330,17 +350,35 @@ __global__ __launch_bounds__(kBlock) void k_shard_combine(const int32_t* __restr
       for (int qc = 0; qc < nq; qc += GS) {
         const int q = qc + g;
         if (q >= nq) break;  // (q grows with qc)
-        float4 tv[OW];
-#pragma unroll
-        for (int o = 0; o < OW; ++o)
-          tv[o] = pj[o] >= 0 ? reinterpret_cast<const float4*>(part_vec + pj[o] * kp)[q]
-                             : *reinterpret_cast<const float4*>(poff);
         double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        if constexpr (std::is_same<W, double>::value) {
 #pragma unroll
-        for (int o = 0; o < OW; ++o) {
-          const bool ok = pj[o] >= 0;
-          a0 += ok ? (double)tv[o].x : 0.0; a1 += ok ? (double)tv[o].y : 0.0;
-          a2 += ok ? (double)tv[o].z : 0.0; a3 += ok ? (double)tv[o].w : 0.0;
+          for (int h = 0; h < 2; ++h) {  // columns 4q + 2h, 4q + 2h + 1 of every owner, owner order
+            double2 tv[OW];
+#pragma unroll
+            for (int o = 0; o < OW; ++o)
+              tv[o] = pj[o] >= 0 ? reinterpret_cast<const double2*>(part_vec + pj[o] * kp)[2 * q + h]
+                                 : *reinterpret_cast<const double2*>(poff);
+            double b0 = 0.0, b1 = 0.0;
+#pragma unroll
+            for (int o = 0; o < OW; ++o) {
+              const bool ok = pj[o] >= 0;
+              b0 += ok ? tv[o].x : 0.0; b1 += ok ? tv[o].y : 0.0;
+            }
+            if (h == 0) { a0 = b0; a1 = b1; } else { a2 = b0; a3 = b1; }
+          }
+        } else {
+          float4 tv[OW];
+#pragma unroll
+          for (int o = 0; o < OW; ++o)
+            tv[o] = pj[o] >= 0 ? reinterpret_cast<const float4*>(part_vec + pj[o] * kp)[q]
+                               : *reinterpret_cast<const float4*>(poff);
+#pragma unroll
+          for (int o = 0; o < OW; ++o) {
+            const bool ok = pj[o] >= 0;
+            a0 += ok ? (double)tv[o].x : 0.0; a1 += ok ? (double)tv[o].y : 0.0;
+            a2 += ok ? (double)tv[o].z : 0.0; a3 += ok ? (double)tv[o].w : 0.0;
+          }
         }
         ss += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
         const float4 sq = make_float4((float)a0, (float)a1, (float)a2, (float)a3);
@@ -367,7 +405,7 @@ __global__ __launch_bounds__(kBlock) void k_shard_combine(const int32_t* __restr
     for (int o = 0; o < R; ++o) {
       const int32_t ix = pi[o];
       if (ix >= 0) {
-        const float2 t = part_sc[poff[o] + ix];
+        const wire2<W> t = part_sc[poff[o] + ix];
         vv += (double)t.x;
         wx += (double)t.y;
         any = true;
@@ -379,10 +417,7 @@ __global__ __launch_bounds__(kBlock) void k_shard_combine(const int32_t* __restr
       if (q < nq) {
         for (int o = 0; o < R; ++o) {
           const int32_t ix = pi[o];
-          if (ix >= 0) {
-            const float4 t = reinterpret_cast<const float4*>(part_vec + (poff[o] + ix) * kp)[q];
-            a0 += (double)t.x; a1 += (double)t.y; a2 += (double)t.z; a3 += (double)t.w;
-          }
+          if (ix >= 0) add_quad(part_vec + (poff[o] + ix) * kp, q, a0, a1, a2, a3);
         }
         ss += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
         const float4 sq = make_float4((float)a0, (float)a1, (float)a2, (float)a3);
@@ -433,11 +468,11 @@ __global__ __launch_bounds__(kBlock) void k_shard_combine(const int32_t* __restr
 // pcnt[pair] = the owner's present rows among the pair's entries (absent ids drop out, :103-112);
 // a sample with none scores globalBias unclamped (na.fill, :78-86), every other
 // least(greatest(yhat, minLabel), maxLabel) (:129-132).
-template <int GS>
+template <int GS, typename W>
 __global__ __launch_bounds__(kBlock) void k_shard_predict(const int32_t* __restrict__ pairidx,
                                                           const int64_t* __restrict__ poff, int R, int64_t B,
-                                                          const float* __restrict__ part_vec,
-                                                          const float2* __restrict__ part_sc,
+                                                          const W* __restrict__ part_vec,
+                                                          const wire2<W>* __restrict__ part_sc,
                                                           const uint32_t* __restrict__ pcnt, int kp, double w0,
                                                           double lo, double hi, double* __restrict__ pred) {
   constexpr int TPB = kBlock / GS;
@@ -450,7 +485,7 @@ __global__ __launch_bounds__(kBlock) void k_shard_predict(const int32_t* __restr
     for (int o = 0; o < R; ++o) {
       const int32_t ix = pi[o];
       if (ix >= 0) {
-        const float2 t = part_sc[poff[o] + ix];
+        const wire2<W> t = part_sc[poff[o] + ix];
         vv += (double)t.x;
         wx += (double)t.y;
         cnt += pcnt[poff[o] + ix];
@@ -462,10 +497,7 @@ __global__ __launch_bounds__(kBlock) void k_shard_predict(const int32_t* __restr
       double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
       for (int o = 0; o < R; ++o) {
         const int32_t ix = pi[o];
-        if (ix >= 0) {
-          const float4 t = reinterpret_cast<const float4*>(part_vec + (poff[o] + ix) * kp)[q];
-          a0 += (double)t.x; a1 += (double)t.y; a2 += (double)t.z; a3 += (double)t.w;
-        }
+        if (ix >= 0) add_quad(part_vec + (poff[o] + ix) * kp, q, a0, a1, a2, a3);
       }
       ss += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
     }
@@ -513,6 +545,33 @@ void shard_owner_partials(fm_ctx* ctx, fm_batch* b, void* partials_out, uint32_t
 using namespace fmhip;
 
 namespace {
+
+// R <= 8: the owners' pair slots in registers (OW = 8), else owner by owner
+template <typename W>
+void launch_shard_combine(int GS, dim3 grid, hipStream_t st, const int32_t* pi, const int64_t* poff, int R, int64_t B,
+                          const void* partials_in, int64_t Ps, const double* lab, int kp, double w0, float* so,
+                          float2* ssc, double2* lp) {
+  const W* pin = reinterpret_cast<const W*>(partials_in);
+  const wire2<W>* psc = reinterpret_cast<const wire2<W>*>(pin ? pin + Ps * kp : nullptr);
+  const dim3 blk(kBlock);
+  if (R <= 8) {
+    switch (GS) {
+      case 1: hipLaunchKernelGGL((k_shard_combine<1, 8, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
+      case 2: hipLaunchKernelGGL((k_shard_combine<2, 8, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
+      case 4: hipLaunchKernelGGL((k_shard_combine<4, 8, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
+      case 8: hipLaunchKernelGGL((k_shard_combine<8, 8, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
+      default: hipLaunchKernelGGL((k_shard_combine<16, 8, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
+    }
+  } else {
+    switch (GS) {
+      case 1: hipLaunchKernelGGL((k_shard_combine<1, 0, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
+      case 2: hipLaunchKernelGGL((k_shard_combine<2, 0, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
+      case 4: hipLaunchKernelGGL((k_shard_combine<4, 0, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
+      case 8: hipLaunchKernelGGL((k_shard_combine<8, 0, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
+      default: hipLaunchKernelGGL((k_shard_combine<16, 0, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
+    }
+  }
+}
 
 // Owner-side step parameters (SGD.scala:121-124 with the global miniBatchSize).
 StepParams shard_params(fm_ctx* ctx, int32_t t, double step_size, double reg_param, int64_t global_rows) {
@@ -591,7 +650,8 @@ void shard_route_launch(fm_ctx* ctx, fm_batch* b, void* send_slot, void* send_en
     ctx->sh_tcnt.ensure(sizeof(uint32_t) * R * ntiles);
     ctx->sh_tot.ensure(sizeof(unsigned long long) * 2 * R);
     S.pairidx.ensure(sizeof(int32_t) * std::max<int64_t>(B, 1) * R);
-    S.poff.ensure(sizeof(int64_t) * (R + 1));
+    // at least 32 B: the combine's masked loads read poff's first bytes (k_shard_combine, OW > 0)
+    S.poff.ensure(sizeof(int64_t) * std::max(R + 1, 4));
     unsigned long long* tot = ctx->sh_tot.as<unsigned long long>();  // [R] pairs, [R] entries
     FM_HIP_CHECK(hipMemsetAsync(tot, 0, sizeof(unsigned long long) * 2 * R, st));
     const uint64_t F = (uint64_t)ctx->cfg.num_features;
@@ -771,13 +831,31 @@ void shard_owner_partials(fm_ctx* ctx, fm_batch* b, void* partials_out, uint32_t
       xo.ch_c = chunk;
       xo.ch_C = chunks;
     }
-    launch_forward(ctx->view(), view, ctx->work, p, st, &nblk, reinterpret_cast<float*>(partials_out), &xo);
+    launch_forward(ctx->view(), view, ctx->work, p, st, &nblk, reinterpret_cast<float*>(partials_out), &xo,
+                   ctx->cfg.wire == FM_WIRE_FP64);
     view.row_ptr.p = view.col.p = view.ent.p = nullptr;  // borrowed
     FM_HIP_CHECK(hipGetLastError());
   }
   if (chunk + 1 == chunks) {
     ctx->prof_end("owner_forward", S.fwd_e0, st);
     S.fwd_e0 = nullptr;
+  }
+}
+
+// the combine / predict kernels of the context's wire (GS = team_for(kp / 4))
+template <typename W>
+void launch_shard_predict(int GS, dim3 grid, hipStream_t st, const int32_t* pi, const int64_t* poff, int R, int64_t B,
+                          const void* partials_in, int64_t Ps, const uint32_t* present_in, int kp, double w0, double lo,
+                          double hi, double* pred_dev) {
+  const W* pv = reinterpret_cast<const W*>(partials_in);
+  const wire2<W>* ps = reinterpret_cast<const wire2<W>*>(pv ? pv + Ps * kp : nullptr);
+  const dim3 blk(kBlock);
+  switch (GS) {
+    case 1: hipLaunchKernelGGL((k_shard_predict<1, W>), grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
+    case 2: hipLaunchKernelGGL((k_shard_predict<2, W>), grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
+    case 4: hipLaunchKernelGGL((k_shard_predict<4, W>), grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
+    case 8: hipLaunchKernelGGL((k_shard_predict<8, W>), grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
+    default: hipLaunchKernelGGL((k_shard_predict<16, W>), grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
   }
 }
 
@@ -796,20 +874,15 @@ void shard_combine_predict(fm_ctx* ctx, fm_batch* b, const void* partials_in, co
   const int GS = team_for(kp / 4);
   int64_t blocks = std::max<int64_t>((B + kBlock / GS - 1) / (kBlock / GS), 1);
   if (blocks > 256 * 8) blocks = 256 * 8;
-  const float* pv = reinterpret_cast<const float*>(partials_in);
-  const float2* ps = reinterpret_cast<const float2*>(pv ? pv + Ps * kp : nullptr);
   const int32_t* pi = S.pairidx.as<int32_t>();
   const int64_t* poff = S.poff.as<int64_t>();
   const double w0 = ctx->cfg.w0;
   hipStream_t st = ctx->stream;
-  const dim3 grid((unsigned)blocks), blk(kBlock);
-  switch (GS) {
-    case 1: hipLaunchKernelGGL(k_shard_predict<1>, grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
-    case 2: hipLaunchKernelGGL(k_shard_predict<2>, grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
-    case 4: hipLaunchKernelGGL(k_shard_predict<4>, grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
-    case 8: hipLaunchKernelGGL(k_shard_predict<8>, grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
-    default: hipLaunchKernelGGL(k_shard_predict<16>, grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
-  }
+  const dim3 grid((unsigned)blocks);
+  if (ctx->cfg.wire == FM_WIRE_FP64)
+    launch_shard_predict<double>(GS, grid, st, pi, poff, R, B, partials_in, Ps, present_in, kp, w0, lo, hi, pred_dev);
+  else
+    launch_shard_predict<float>(GS, grid, st, pi, poff, R, B, partials_in, Ps, present_in, kp, w0, lo, hi, pred_dev);
   FM_HIP_CHECK(hipGetLastError());
 }
 
@@ -838,31 +911,16 @@ int fm_shard_combine(fm_ctx* ctx, fm_batch* b, const void* partials_in, void* s_
     const int32_t* pi = S.pairidx.as<int32_t>();
     const int64_t* poff = S.poff.as<int64_t>();
     const int kp = ctx->kp;
-    const float* pin = reinterpret_cast<const float*>(partials_in);
-    const float2* psc = reinterpret_cast<const float2*>(pin ? pin + Ps * kp : nullptr);
     float* so = reinterpret_cast<float*>(s_send);
     float2* ssc = reinterpret_cast<float2*>(so ? so + Ps * kp : nullptr);
     const double* lab = b->dev.label.as<double>();
     double2* lp = ctx->work.loss_part.as<double2>();
     const double w0 = ctx->cfg.w0;
-    const dim3 grid((unsigned)blocks), blk(kBlock);
-    if (R <= 8) {
-      switch (GS) {
-        case 1: hipLaunchKernelGGL((k_shard_combine<1, 8>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-        case 2: hipLaunchKernelGGL((k_shard_combine<2, 8>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-        case 4: hipLaunchKernelGGL((k_shard_combine<4, 8>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-        case 8: hipLaunchKernelGGL((k_shard_combine<8, 8>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-        default: hipLaunchKernelGGL((k_shard_combine<16, 8>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-      }
-    } else {
-      switch (GS) {
-        case 1: hipLaunchKernelGGL((k_shard_combine<1, 0>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-        case 2: hipLaunchKernelGGL((k_shard_combine<2, 0>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-        case 4: hipLaunchKernelGGL((k_shard_combine<4, 0>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-        case 8: hipLaunchKernelGGL((k_shard_combine<8, 0>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-        default: hipLaunchKernelGGL((k_shard_combine<16, 0>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-      }
-    }
+    const dim3 grid((unsigned)blocks);
+    if (ctx->cfg.wire == FM_WIRE_FP64)
+      launch_shard_combine<double>(GS, grid, st, pi, poff, R, B, partials_in, Ps, lab, kp, w0, so, ssc, lp);
+    else
+      launch_shard_combine<float>(GS, grid, st, pi, poff, R, B, partials_in, Ps, lab, kp, w0, so, ssc, lp);
     FM_HIP_CHECK(hipGetLastError());
     ctx->prof_end("combine", e0, st);
     S.loss_blocks = blocks;

@@ -36,17 +36,20 @@ from .engine import FMContext, StepOut
 
 
 class HipShardEngine:
-    """The HIP phase functions of one rank (its own fm_ctx with shard_index = rank)."""
+    """The HIP phase functions of one rank (its own fm_ctx with shard_index = rank).  ``wire``
+    "fp32" | "fp64": the format of the partial sums owner_forward writes and combine reads
+    (fm_config.wire; every rank of a job the same); the S rows are fp32 either way."""
 
     def __init__(self, num_features: int, k: int, rank: int, world: int, *, device: int = 0, seed: int = 0,
-                 init_sd: float = 0.01, w0: float = 0.0):
+                 init_sd: float = 0.01, w0: float = 0.0, wire: str = "fp32"):
         import torch
 
         self.torch = torch
         self.device = torch.device("cuda", device)
         self.R = world
         self.ctx = FMContext(num_features, k, device=device, seed=seed, init_sd=init_sd, w0=w0, shard_index=rank,
-                             shard_count=world)
+                             shard_count=world, wire=wire)
+        self.wire_dtype = torch.float64 if wire == "fp64" else torch.float32  # the partial direction's words
         # launch on torch's streams so the C-ABI kernels and the collectives are stream-ordered:
         # the iteration on the current stream, batch-only preparation on a side stream
         self.main_stream = torch.cuda.current_stream(self.device)
@@ -56,7 +59,7 @@ class HipShardEngine:
         N.check(self._lib.fm_set_side_stream(self.ctx.handle, C.c_void_p(self.side_stream.cuda_stream)),
                 "fm_set_side_stream")
         self.kp = (k + 3) // 4 * 4
-        self.width = self.kp + 2  # fp32 words per pair on the wire: [P][kp] vectors, then [P][2] scalars
+        self.width = self.kp + 2  # words per pair on the wire: [P][kp] vectors, then [P][2] scalars
 
     def _empty(self, n, dtype):
         return self.torch.empty(max(int(n), 1), dtype=dtype, device=self.device)[: int(n)]
@@ -90,7 +93,7 @@ class HipShardEngine:
                 "fm_shard_owner_prepare")
 
     def owner_forward(self, b, n_pairs_in: int):
-        out = self._empty(int(n_pairs_in) * self.width, self.torch.float32)
+        out = self._empty(int(n_pairs_in) * self.width, self.wire_dtype)
         N.check(self._lib.fm_shard_owner_forward(self.ctx.handle, b.handle, self._ptr(out)), "fm_shard_owner_forward")
         return out
 
@@ -155,7 +158,7 @@ class ShardedTrainer:
     module the collectives go through (torch.distributed unless a test stages them)."""
 
     def __init__(self, num_features: int, k: int, *, rank: int, world: int, device: int = 0, seed: int = 0,
-                 init_sd: float = 0.01, w0: float = 0.0, group=None, engine=None, comm=None):
+                 init_sd: float = 0.01, w0: float = 0.0, group=None, engine=None, comm=None, wire: str = "fp32"):
         import torch
         import torch.distributed as dist
 
@@ -164,7 +167,7 @@ class ShardedTrainer:
         self.rank, self.world = rank, world
         self.group = group
         self.engine = engine if engine is not None else HipShardEngine(
-            num_features, k, rank, world, device=device, seed=seed, init_sd=init_sd, w0=w0)
+            num_features, k, rank, world, device=device, seed=seed, init_sd=init_sd, w0=w0, wire=wire)
         self.device = self.engine.device
 
     # convenience passthroughs -------------------------------------------------------
@@ -248,7 +251,8 @@ class ShardedTrainer:
         self.prefetch(b)  # no-op when an earlier step already did
         plan, b._fm_plan = b._fm_plan, None
         partials = self.engine.owner_forward(b, int(plan.pair_in.sum()))
-        part_in = self._empty(plan.pair_out.sum() * W, self.torch.float32)
+        # the partial direction's words are the engine's wire format (fp32 unless it says otherwise)
+        part_in = self._empty(plan.pair_out.sum() * W, getattr(self.engine, "wire_dtype", self.torch.float32))
         self._a2a_pairs(part_in, partials, plan.pair_out, plan.pair_in)
         s_send = self.engine.combine(b, part_in, int(plan.pair_out.sum()))
         s_recv = self._empty(plan.pair_in.sum() * W, self.torch.float32)

@@ -91,17 +91,21 @@ class FMContext:
     ranks on ``devices`` (default device, device + 1, ...) of a job of ``n_procs`` processes and runs
     the multi-GPU step itself (include/fm_hip.h); ``transport`` "auto" | "rccl" | "copy".
     ``fuse`` None (the library's default: on) | True | False: the fused step for prepared batches
-    (fm_config.fuse_single); ``xchg_chunks``: 0 = default (fm_config.xchg_chunks)."""
+    (fm_config.fuse_single); ``xchg_chunks``: 0 = default (fm_config.xchg_chunks); ``wire`` "fp32" |
+    "fp64": the format of the sharded step's partial sums on the wire (fm_config.wire)."""
 
     _PAR = {None: N.FM_PARALLEL_NONE, "none": N.FM_PARALLEL_NONE, "sharded": N.FM_PARALLEL_SHARDED,
             "replicated": N.FM_PARALLEL_REPLICATED}
     _TR = {"auto": N.FM_TRANSPORT_AUTO, "rccl": N.FM_TRANSPORT_RCCL, "copy": N.FM_TRANSPORT_COPY}
+    _WIRE = {"fp32": N.FM_WIRE_FP32, "fp64": N.FM_WIRE_FP64}
 
     def __init__(self, num_features: int, k: int, *, device: int = 0, seed: int = 0, init_sd: float = 0.01,
                  w0: float = 0.0, shard_index: int = 0, shard_count: int = 1, parallel: str | None = None,
                  n_gpus: int = 1, devices=None, transport: str = "auto", n_procs: int = 1, proc_rank: int = 0,
-                 comm_id: bytes | None = None, fuse: bool | None = None, xchg_chunks: int = 0):
+                 comm_id: bytes | None = None, fuse: bool | None = None, xchg_chunks: int = 0, wire: str = "fp32"):
         self._lib = N.load()
+        if wire not in self._WIRE:
+            raise ValueError('wire must be "fp32" or "fp64"')
         cfg = N.fm_config(num_features=int(num_features), k=int(k), device=int(device), seed=int(seed) & (2**64 - 1),
                           init_sd=float(init_sd), w0=float(w0), shard_index=int(shard_index),
                           shard_count=int(shard_count))
@@ -117,6 +121,7 @@ class FMContext:
         cfg.transport = self._TR[transport]
         cfg.fuse_single = N.FM_FUSE_DEFAULT if fuse is None else (N.FM_FUSE_ON if fuse else N.FM_FUSE_OFF)
         cfg.xchg_chunks = int(xchg_chunks)
+        cfg.wire = self._WIRE[wire]
         cfg.n_procs = int(n_procs)
         cfg.proc_rank = int(proc_rank)
         if comm_id is not None:
@@ -134,6 +139,7 @@ class FMContext:
         self.w0 = float(w0)
         self.shard_index = int(shard_index)
         self.shard_count = int(shard_count)
+        self.wire = wire
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):

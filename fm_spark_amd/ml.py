@@ -283,7 +283,7 @@ class FactorizationMachinesSGD:
         "seed": 0, "device": 0, "numFeatures": None,
         # not in the reference: the table over several GPUs of this process (include/fm_hip.h
         # fm_config.parallel), in place of Spark's hash-partitioned model Datasets
-        "parallel": None, "nGpus": 1, "devices": None, "transport": "auto",
+        "parallel": None, "nGpus": 1, "devices": None, "transport": "auto", "wire": "fp32",
     }
 
     def __init__(self, uid: str | None = None):
@@ -313,11 +313,16 @@ class FactorizationMachinesSGD:
     def setSeed(self, v): return self._set("seed", int(v))
     def setNumFeatures(self, v): return self._set("numFeatures", int(v))
 
-    def setParallel(self, mode, n_gpus: int = 1, devices=None, transport: str = "auto"):
+    def setParallel(self, mode, n_gpus: int = 1, devices=None, transport: str = "auto", wire: str = "fp32"):
         """Train (and transform) on n_gpus GPUs of this process: mode "sharded" splits the table's
         rows by id % R (owner-computes), "replicated" keeps a copy per GPU (gradient all-reduce);
-        the mini-batches split by rows across the GPUs.  transport "copy" shares one device."""
+        the mini-batches split by rows across the GPUs.  transport "copy" shares one device.
+        wire "fp64" (sharded only): the owners' partial sums cross unrounded, so every sample is
+        summed in fp64 as on one GPU (fm_config.wire); the fitted model transforms with the same wire."""
+        if wire not in ("fp32", "fp64"):
+            raise ValueError('wire must be "fp32" or "fp64"')
         self._set("parallel", mode)
+        self._set("wire", wire)
         self._set("nGpus", int(n_gpus))
         self._set("devices", None if devices is None else [int(d) for d in devices])
         return self._set("transport", transport)
@@ -365,7 +370,8 @@ class FactorizationMachinesSGD:
         rp, col, val = _explode(vectors)
         F = p["numFeatures"] or (int(col.max()) + 1 if len(col) else 1)
         ctx = FMContext(F, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0,
-                        parallel=p["parallel"], n_gpus=p["nGpus"], devices=p["devices"], transport=p["transport"])
+                        parallel=p["parallel"], n_gpus=p["nGpus"], devices=p["devices"], transport=p["transport"],
+                        wire=p["wire"])
         if pipelined is None:
             pipelined = True
         # randomSplit(Array.fill(maxIter)(miniBatchFraction), 1234L) (:111-112)

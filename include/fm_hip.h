@@ -50,6 +50,8 @@ extern "C" {
 #define FM_FUSE_DEFAULT 0 /* fm_config.fuse_single: the library's choice (tables above 256 MB) */
 #define FM_FUSE_ON 1
 #define FM_FUSE_OFF (-1)
+#define FM_WIRE_FP32 0 /* fm_config.wire: the owners' partial sums cross as fp32 (default) */
+#define FM_WIRE_FP64 1 /* ... as fp64: the sharded step sums every sample in fp64, as the single table */
 
 typedef struct fm_ctx fm_ctx;
 typedef struct fm_batch fm_batch;
@@ -85,6 +87,19 @@ typedef struct fm_batch fm_batch;
  * xchg_chunks  : sharded step with R > 1: the owners' partial pass runs in this many chunks, each
  *                sent while the next is computed (0 = the default, 4; 1 = one pass then one
  *                all-to-all; at most 64).  Every process of a job must pass the same value.
+ * wire         : sharded step and predict: the number format in which the owners' partial forward sums
+ *                travel to the requesters (owner -> requester; see the fm_shard_* block).
+ *                FM_WIRE_FP32 (0, default): each owner rounds its share of a sample's sums to fp32.
+ *                FM_WIRE_FP64: the shares stay fp64, so a sample's S, sum v^2 x^2 and sum w x are
+ *                fp64 sums over all of its entries, rounded once -- what the single table computes
+ *                (the reference sums in Double, FactorizationMachinesSGD.scala:145-154); the partial
+ *                direction carries twice the bytes.  The S rows going back are fp32 either way.  Every
+ *                process of a job must pass the same value.  Any other value is FM_ERR_ARG, and so is
+ *                FM_WIRE_FP64 with FM_PARALLEL_REPLICATED (the replicated gradient all-reduce is fp32;
+ *                the flag would change nothing there).  A context that exchanges nothing accepts it
+ *                and its step and predict never read it (FM_PARALLEL_NONE with shard_count 1); a
+ *                caller that drives the fm_shard_* phases itself (FM_PARALLEL_NONE, shard_index /
+ *                shard_count) gets the format of that context's own value.
  * Zero-initialise the struct: every field's 0 is its default. */
 typedef struct fm_config {
   int64_t num_features;
@@ -104,6 +119,7 @@ typedef struct fm_config {
   uint8_t comm_id[128];
   int32_t fuse_single;
   int32_t xchg_chunks;
+  int32_t wire;
 } fm_config;
 
 /* One mini-batch in CSR form: the result of explode(udfVecToMap(features))
@@ -348,12 +364,17 @@ int fm_xorshift_next_doubles(int64_t seed, int64_t n, double* out);
  * between phases with all-to-all (RCCL over xGMI; fm_spark_amd/distributed.py).  Replaces the
  * feature-keyed shuffles S1/S2/S5/S6 and the per-sample window of the reference plan
  * (Model.scala:155-164, :191, SGD.scala:148-166).
- * A "pair" is (sample of a source rank, owner holding some of its entries).  Wire buffers are fp32
- * structures of arrays over P pairs, kp + 2 fp32 words per pair (kp = roundup(k, 4)):
- *   partials = [P][kp] sum v*x, then [P][2] {sum v^2 x^2, sum w*x}
+ * A "pair" is (sample of a source rank, owner holding some of its entries).  Wire buffers are
+ * structures of arrays over P pairs, kp + 2 words per pair (kp = roundup(k, 4)):
+ *   partials = [P][kp] sum v*x, then [P][2] {sum v^2 x^2, sum w*x}; words of the context's
+ *              fm_config.wire: fp32 (FM_WIRE_FP32: 4 (kp + 2) P bytes) or fp64 (FM_WIRE_FP64:
+ *              8 (kp + 2) P bytes, the scalar section at byte 8 kp P).  This is the size of
+ *              partials_out (P = sum src_pairs) and of partials_in (P = sum counts[R..2R)).
  *   S        = [P][kp] vfxiSum, then [P][2] {r, yhat}  (the residual r = yhat - y is formed in fp64
  *              from the fp64 label, as the reference's Double column, SGD.scala:145-146, and rounded
- *              once; the owner forms g_w = x*yhat - y as (x - 1)*yhat + r)
+ *              once; the owner forms g_w = x*yhat - y as (x - 1)*yhat + r); always fp32, 4 (kp + 2) P
+ *              bytes: s_send / s_recv do not depend on fm_config.wire (they are the values the single
+ *              table's update reads)
  * so the exchange is two all-to-alls per direction (the vector section, the scalar section).
  * Every phase is keyed by `batch`, this rank's mini-batch of the iteration; its state lives with
  * the batch.  Phases 1 and 1b depend on the batch alone and run on the side stream
@@ -372,10 +393,12 @@ int fm_shard_route(fm_ctx* ctx, fm_batch* batch, void* send_slot, void* send_ent
 int fm_shard_owner_prepare(fm_ctx* ctx, fm_batch* batch, const void* recv_slot, const void* recv_ent,
                            int64_t n, const int64_t* src_entries, const int64_t* src_pairs);
 /* Phase 2 (owner): partials_out[sum src_pairs] (source-major, sample order): per received pair
- * the partial forward sums over the entries this rank owns, lazy L1 caught up on read. */
+ * the partial forward sums over the entries this rank owns, lazy L1 caught up on read; fp32 or fp64
+ * words as this context's fm_config.wire says (above). */
 int fm_shard_owner_forward(fm_ctx* ctx, fm_batch* batch, void* partials_out);
 /* Phase 3 (requester): the partials received from the owners (owner-major, counts[R + o] rows
- * from owner o) -> per sample S, yhat and the loss; s_send gets the S rows in the same layout. */
+ * from owner o; words of this context's fm_config.wire) -> per sample S, yhat and the loss; s_send
+ * gets the S rows in the same layout, fp32. */
 int fm_shard_combine(fm_ctx* ctx, fm_batch* batch, const void* partials_in, void* s_send);
 /* Phase 4 (owner): the S rows received for its pairs (same order as its partials) -> per-slot
  * gradient sums over the slot-sorted entries, update + L1 with global miniBatchSize global_rows
