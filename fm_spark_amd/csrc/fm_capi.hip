@@ -203,7 +203,7 @@ static Staged stage_csr(fm_ctx* ctx, const fm_csr* c, bool check_range, Pinned& 
   return g;
 }
 
-// The fused step (fm_kernels.hip "Singleton rows") for batches this context prepares: a
+// The fused step (fm_device.h "Singleton rows") for batches this context prepares: a
 // single-table context with kp <= 16; by default (FM_FUSE_DEFAULT) only for a table larger than
 // the 256-MB Infinity Cache, where the update's re-read of the singleton rows goes to HBM -- a
 // cache-resident table re-reads them on-die, and the split and tags would cost more than they save
@@ -281,7 +281,7 @@ void reserve_work(fm_ctx* ctx, int64_t B, int64_t N) {
   w.S.ensure_slack(sizeof(float) * (size_t)std::max<int64_t>(B, 1) * s_rec_floats(ctx->kp));
   w.yl.ensure_slack(sizeof(float2) * (size_t)std::max<int64_t>(B, 1));
   w.sort.ensure(std::max<int64_t>(N, 1));
-  const int64_t nranges = (N + 255) / 256;  // update waves (fm_kernels.hip, kWaveEnt)
+  const int64_t nranges = (N + 255) / 256;  // update waves (fm_update.hip, kWaveEnt)
   w.part.ensure_slack(sizeof(double) * (size_t)std::max<int64_t>(nranges, 1) * 2 * (ctx->kp + 2));
   w.ucnt.ensure_slack(sizeof(uint32_t) * (size_t)std::max<int64_t>((N + 1023) / 1024, 1));
   w.loss_part.ensure(sizeof(double) * 2 * 256 * 8);
@@ -352,7 +352,7 @@ int step_impl(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_
     launch_split(b->fkeys.as<uint32_t>(), b->fents.as<uint2>(), N, ctx->split_work, b->skeys.as<uint32_t>(),
                  b->sents.as<uint2>(), b->split_n.as<int64_t>(), ctx->stream, T, p.epoch);
     ctx->prof_end("split", e0, ctx->stream);
-    fx.fused = true;
+    fx.mode = kTrainFused;
   }
   e0 = ctx->prof_begin(ctx->stream);
   launch_forward(T, b->dev, ctx->work, p, ctx->stream, &nfwd, nullptr, fused ? &fx : nullptr);

@@ -103,7 +103,7 @@ struct fm_batch {
   // feature-major view produced by fm_batch_prepare (consumed once by the next step): the whole
   // sorted view in skeys / sents, or -- split = true, the fused step -- the whole sorted view in
   // fkeys / fents, which the step splits into the runs of two or more entries (skeys / sents) with
-  // split_n = {their count, the number of singleton runs} on the device (fm_kernels.hip)
+  // split_n = {their count, the number of singleton runs} on the device (fm_update.hip)
   DevBuf skeys, sents;
   DevBuf fkeys, fents;
   DevBuf split_n;

@@ -56,8 +56,6 @@ void mcheck(int rc, const char* what) {
   if (rc < 0) throw Error{rc, std::string(what) + ": " + fm_last_error()};
 }
 
-constexpr int kBlock = 256;
-
 __global__ void k_slots_to_ids(const uint32_t* __restrict__ slot, int64_t n, uint32_t R, uint32_t shard,
                                uint32_t* __restrict__ ids) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)

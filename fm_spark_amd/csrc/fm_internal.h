@@ -41,7 +41,7 @@ struct Error {
 //   RowHdr {w, t, cum}   at float offset kp (16-byte aligned)
 //   t   : epoch (executed steps) through which the row is current; -1 = absent
 //   cum : sum of lambda over executed steps 1..t, i.e. the L1 shrink already applied.
-// A row read at epoch E is brought current by S_{cum[E] - cum} (lazy L1, see fm_kernels.hip).
+// A row read at epoch E is brought current by S_{cum[E] - cum} (lazy L1, see fm_device.h).
 struct alignas(16) RowHdr {
   float w;
   int32_t t;
@@ -111,6 +111,7 @@ void radix_sort_pairs64_bits(SortWork& w, const uint32_t* keys_in, const uint2* 
                              int hi_bit, hipStream_t st, uint32_t* final_keys, uint2* final_vals);
 
 // ---------------------------------------------------------------- step kernels
+// (fm_forward.hip, fm_update.hip, fm_table.hip, fm_batch.hip)
 // A device-resident mini-batch: the exploded (sampleId, featureId, featureValue) rows of
 // Model.scala:148-153 kept both as CSR (row_ptr) and as COO entries ent[e] = {sample, x bits}.
 struct BatchDev {
@@ -146,11 +147,13 @@ struct StepParams {
   double w0;
 };
 
-// the forward's inference modes (fm_kernels.hip): 2 = predict (clamp bounds, fp64 score per
-// sample into pred), 3 = calcLossGrad (fp64 pred / loss / dw per entry, dv [entries][k], the
-// absent-id flag)
+// k_forward's modes (fm_forward.hip): the step's forward, plain or with the singleton rows' updates
+// fused in; the sharded owner's partial pass with the fp32 or the fp64 wire; predict (clamp bounds,
+// fp64 score per sample into pred); calcLossGrad (fp64 pred / loss / dw per entry, dv [entries][k],
+// the absent-id flag)
+enum FwdMode : int { kTrain = 0, kPartial = 1, kPredict = 2, kLossGrad = 3, kTrainFused = 4, kPartial64 = 5 };
 struct FwdOut {
-  int mode = 0;
+  int mode = kTrain;  // a FwdMode; launch_forward sets the partial modes itself (partial_out / partial_wide)
   double lo = 0.0, hi = 0.0;
   double* pred = nullptr;
   double* loss = nullptr;
@@ -167,9 +170,8 @@ struct FwdOut {
   // keyed by (fill_seed, entry index, column)
   double fill_sd = 0.0;
   uint64_t fill_seed = 0;
-  // train mode: the forward applies the update of every row whose header carries no multi tag of
-  // this epoch (a singleton; fm_kernels.hip "Singleton rows"), with sp; kp <= 16
-  bool fused = false;
+  // kTrainFused: the forward applies the update of every row whose header carries no multi tag of
+  // this epoch (a singleton; fm_device.h "Singleton rows"), with sp (set by the launch); kp <= 16
   StepParams sp{};
 };
 constexpr int kMaxChunkSources = 64;  // sources a chunked partial pass can split
@@ -195,8 +197,8 @@ struct SegSource {
 void launch_segment_update(const TableView& T, const BatchDev& b, StepWork& w, const StepParams& p,
                            const uint32_t* skeys, const uint2* sents, int64_t n_fwd_blocks,
                            double* stats_out, hipStream_t st, float* emit = nullptr, const int64_t* n_dev = nullptr);
-// the fused step's singleton split of a prepared sorted view, at the step (fm_kernels.hip "Singleton
-// rows"): the entries of runs of two or more, in order, into mkeys / ments (capacity N); n_out[0] =
+// the fused step's singleton split of a prepared sorted view, at the step (fm_update.hip; fm_device.h
+// "Singleton rows"): the entries of runs of two or more, in order, into mkeys / ments (capacity N); n_out[0] =
 // their count, n_out[1] = the number of singleton runs (device); each multi run's row in tag_T gets
 // the epoch's multi tag
 struct SplitWork {

@@ -18,7 +18,7 @@
 //   fm_shard_combine        requester: per sample, the owners' partials summed in owner order
 //                           (fp64) -> vfxiSum S, yhat, loss; S | yhat | y sent back per pair
 //   -- all-to-all S -->
-//   fm_shard_owner_update   owner: the fused segmented gradient + update + L1 of fm_kernels.hip
+//   fm_shard_owner_update   owner: the fused segmented gradient + update + L1 of fm_update.hip
 //                           (SGD.scala:143-181) over the slot-sorted entries, on its own rows
 //
 // Semantics equal the single-table step over the ranks' batches concatenated in rank order
@@ -47,7 +47,6 @@ namespace fmhip {
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kMaxR = 64;     // owner masks are uint64
 
 __device__ __forceinline__ uint32_t incl_scan_u32(uint32_t v, int lane) {
@@ -443,25 +442,7 @@ __global__ __launch_bounds__(kBlock) void k_shard_combine(const int32_t* __restr
       }
     }
   }
-  __shared__ double red[2][kBlock / 64];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    loss_acc += __shfl_xor(loss_acc, o);
-    nloss += __shfl_xor(nloss, o);
-  }
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = loss_acc;
-    red[1][tid >> 6] = nloss;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double l = 0.0, c = 0.0;
-    for (int w = 0; w < kBlock / 64; ++w) {
-      l += red[0][w];
-      c += red[1][w];
-    }
-    loss_part[blockIdx.x] = make_double2(l, c);
-  }
+  block_loss_partial(loss_acc, nloss, loss_part);
 }
 
 // The same sums for FactorizationMachinesModel.predict (Model.scala:90-133) over a sharded table:

@@ -33,14 +33,14 @@ namespace {
 constexpr int kMaxRB = 10;
 // 8 waves x 8 keys per lane; two blocks (16 waves) per CU (8192-key tiles on 1024-thread blocks
 // measured slower in the step: DESIGN.md §5)
-constexpr int kBlock = 512;
-constexpr int kWaves = kBlock / 64;
+constexpr int kSortBlock = 512;
+constexpr int kWaves = kSortBlock / 64;
 constexpr int kMinRB = 9;
 // digits per thread in the block scans (a block wider than the radix: one, on the first R threads)
 template <int R>
-constexpr int digits_per_thread() { return R >= kBlock ? R / kBlock : 1; }
+constexpr int digits_per_thread() { return R >= kSortBlock ? R / kSortBlock : 1; }
 constexpr int kRounds = 8;   // keys per thread per tile
-constexpr int kTile = kBlock * kRounds;  // 4096 keys per tile
+constexpr int kTile = kSortBlock * kRounds;  // 4096 keys per tile
 constexpr int kMaxRadix = 1 << kMaxRB;
 constexpr int kChunk = 16;   // tiles per chunk of the count scan
 
@@ -55,7 +55,7 @@ __device__ __forceinline__ int64_t tile_of_block(int64_t ntiles) {
 
 inline int64_t blocks_for_tiles(int64_t ntiles) { return (ntiles + 7) / 8 * 8; }
 
-static_assert(kTile % (4 * kBlock) == 0, "count block must divide the tile into uint4 rounds");
+static_assert(kTile % (4 * kSortBlock) == 0, "count block must divide the tile into uint4 rounds");
 
 // Tile of a block: keys [base, end) of it, and its row in the per-tile digit counts.
 struct TileGeo {
@@ -71,7 +71,7 @@ __device__ __forceinline__ bool tile_geo(TileGeo& g, int64_t n, int64_t ntiles) 
 }
 
 template <int RB>
-__global__ __launch_bounds__(kBlock) void k_radix_count(const uint32_t* __restrict__ keys, int64_t n, int shift,
+__global__ __launch_bounds__(kSortBlock) void k_radix_count(const uint32_t* __restrict__ keys, int64_t n, int shift,
                                                         uint32_t* __restrict__ counts, int64_t ntiles, bool vec) {
   constexpr int R = 1 << RB;
   constexpr uint32_t M = R - 1;
@@ -83,22 +83,22 @@ __global__ __launch_bounds__(kBlock) void k_radix_count(const uint32_t* __restri
   // out its round trip before the next is issued), and in flight while the histogram is cleared;
   // uint4 reads of whole tiles when the keys are 16-byte aligned (a split view of a dataset starts
   // anywhere)
-  constexpr int NV = kTile / (4 * kBlock), NS = kTile / kBlock;
+  constexpr int NV = kTile / (4 * kSortBlock), NS = kTile / kSortBlock;
   const bool wide = vec && base + kTile <= g.end;  // block-uniform
   uint4 q[NV];
   uint32_t kk[NS];
   if (wide) {
     const uint4* k4 = reinterpret_cast<const uint4*>(keys + base);
 #pragma unroll
-    for (int i = 0; i < NV; ++i) q[i] = k4[i * kBlock + threadIdx.x];
+    for (int i = 0; i < NV; ++i) q[i] = k4[i * kSortBlock + threadIdx.x];
   } else {
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
-      const int64_t idx = base + (int64_t)i * kBlock + threadIdx.x;
+      const int64_t idx = base + (int64_t)i * kSortBlock + threadIdx.x;
       kk[i] = keys[idx < g.end ? idx : g.end - 1];
     }
   }
-  for (int d = threadIdx.x; d < R; d += kBlock) hist[d] = 0;
+  for (int d = threadIdx.x; d < R; d += kSortBlock) hist[d] = 0;
   lds_barrier();
   if (wide) {
 #pragma unroll
@@ -111,10 +111,10 @@ __global__ __launch_bounds__(kBlock) void k_radix_count(const uint32_t* __restri
   } else {
 #pragma unroll
     for (int i = 0; i < NS; ++i)
-      if (base + (int64_t)i * kBlock + threadIdx.x < g.end) atomicAdd(&hist[(kk[i] >> shift) & M], 1u);
+      if (base + (int64_t)i * kSortBlock + threadIdx.x < g.end) atomicAdd(&hist[(kk[i] >> shift) & M], 1u);
   }
   lds_barrier();
-  for (int d = threadIdx.x; d < R; d += kBlock) counts[g.tile * R + d] = hist[d];
+  for (int d = threadIdx.x; d < R; d += kSortBlock) counts[g.tile * R + d] = hist[d];
 }
 
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void k_radix_chunk_top(uint32_t* __restrict__ 
   }
 }
 
-// Block-wide exclusive scan of R values held as D = R / kBlock consecutive values per thread.
+// Block-wide exclusive scan of R values held as D = R / kSortBlock consecutive values per thread.
 template <int D>
 __device__ __forceinline__ void block_excl_scan(uint32_t (&v)[D], uint32_t* wsum, int lane, int wave) {
   uint32_t t = 0;
@@ -237,7 +237,7 @@ __device__ __forceinline__ uint2 implicit_payload<uint2>(int64_t idx) {
 // parameter, so every instantiation issues a fixed number of loads and the block scan waits only
 // for its own
 template <class P, int RB, bool IMPLICIT>
-__global__ __launch_bounds__(kBlock) void k_radix_scatter(const uint32_t* __restrict__ keys_in,
+__global__ __launch_bounds__(kSortBlock) void k_radix_scatter(const uint32_t* __restrict__ keys_in,
                                                           const P* __restrict__ vals_in,
                                                           uint32_t* __restrict__ keys_out,
                                                           P* __restrict__ vals_out, int64_t n,
@@ -248,8 +248,8 @@ __global__ __launch_bounds__(kBlock) void k_radix_scatter(const uint32_t* __rest
   constexpr int R = 1 << RB;
   constexpr uint32_t M = R - 1;
   constexpr int D = digits_per_thread<R>();  // digits per thread in the block scans
-  const bool own = R >= kBlock || (int)threadIdx.x * D < R;  // this thread holds digits in the block scans (all of
-  // them when R >= kBlock: no branch, so the digit loads below are issued where they stand)
+  const bool own = R >= kSortBlock || (int)threadIdx.x * D < R;  // this thread holds digits in the block scans (all of
+  // them when R >= kSortBlock: no branch, so the digit loads below are issued where they stand)
   // per-wave digit counts and their prefixes stay below the 4096-key tile: 16-bit counters for the
   // 10-bit digits keep the block at 74 KB of LDS, two blocks per CU (32-bit: 90 KB, one block)
   using HistT = typename std::conditional<(RB >= 10), uint16_t, uint32_t>::type;
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(kBlock) void k_radix_scatter(const uint32_t* __rest
   __builtin_amdgcn_sched_barrier(0);  // keep the loads above in this order, ahead of the scan
 #pragma unroll
   for (int w = 0; w < kWaves; ++w)
-    for (int d = tid; d < R; d += kBlock) wave_hist[w][d] = 0;
+    for (int d = tid; d < R; d += kSortBlock) wave_hist[w][d] = 0;
 
   // global base of (digit, this tile): exclusive scan of digit totals + the tile's running prefix
   // of the digit (its chunk's prefix + its own prefix within the chunk)
@@ -376,7 +376,7 @@ __global__ __launch_bounds__(kBlock) void k_radix_scatter(const uint32_t* __rest
   const int tile_n = rem < kTile ? (int)rem : kTile;
 #pragma unroll
   for (int r = 0; r < kRounds; ++r) {  // unrolled: the rounds' LDS reads are issued together
-    const int j = r * kBlock + tid;
+    const int j = r * kSortBlock + tid;
     if (j >= tile_n) break;
     const uint32_t key = s_keys[j];
     const uint32_t d = (key >> shift) & M;
@@ -414,7 +414,7 @@ static void radix_pass_impl(const uint32_t* kin, const P* vin, uint32_t* ko, P* 
   // (count and chunk scan fused into one kernel, a block walking its chunk's 16 tiles, measured
   // slower: 0.349 against 0.317 ms standalone)
   const bool vec = (reinterpret_cast<uintptr_t>(kin) & 15u) == 0;
-  hipLaunchKernelGGL(k_radix_count<RB>, dim3((unsigned)blocks_for_tiles(ntiles)), dim3(kBlock), 0, st, kin, n, shift,
+  hipLaunchKernelGGL(k_radix_count<RB>, dim3((unsigned)blocks_for_tiles(ntiles)), dim3(kSortBlock), 0, st, kin, n, shift,
                      counts, ntiles, vec);
   // (one launch for the whole count scan of a small sort -- 32 digits per 256-thread block, 8 slices
   // of the tiles per digit -- measured 0.185-0.188 against 0.170-0.172 ms per c2 step and 0.188-0.190
@@ -425,7 +425,7 @@ static void radix_pass_impl(const uint32_t* kin, const P* vin, uint32_t* ko, P* 
   hipLaunchKernelGGL(k_radix_chunk_top, dim3((1u << RB) / 32), dim3(256), 0, st, csum, nchunks, 1 << RB,
                      w.digit_tot.as<uint32_t>());
   auto scatter = vin ? k_radix_scatter<P, RB, false> : k_radix_scatter<P, RB, true>;
-  hipLaunchKernelGGL(scatter, dim3((unsigned)blocks_for_tiles(ntiles)), dim3(kBlock), 0, st, kin, vin, ko, vo, n,
+  hipLaunchKernelGGL(scatter, dim3((unsigned)blocks_for_tiles(ntiles)), dim3(kSortBlock), 0, st, kin, vin, ko, vo, n,
                      shift, (const uint32_t*)counts, (const uint32_t*)csum,
                      (const uint32_t*)w.digit_tot.as<uint32_t>(), ntiles);
   FM_HIP_CHECK(hipGetLastError());

@@ -396,7 +396,7 @@ def _splitmix64(x):
 def init_draw(ids, k: int, seed: int, sd: float):
     """createInitialModel's N(0, initialSd^2) draw (FactorizationMachinesSGD.scala:234-241)
     made deterministic: a counter-based Box-Muller keyed by (seed, id, factor), f = -1 for
-    w.  Mirrors gauss_draw in fm_spark_amd/csrc/fm_kernels.hip; returns fp32-rounded values."""
+    w.  Mirrors gauss_draw in fm_spark_amd/csrc/fm_device.h; returns fp32-rounded values."""
     ids = np.asarray(ids, dtype=np.int64)
     with np.errstate(over="ignore"):
         f = np.arange(-1, k, dtype=np.int64)

@@ -120,7 +120,7 @@ def test_loss_grad_matches_oracle(gpu, k):
 
 
 def _gauss_draw(seed, e, f, sd):
-    """numpy restatement of the device's keyed N(0, sd^2) draw (fm_kernels.hip gauss_draw)."""
+    """numpy restatement of the device's keyed N(0, sd^2) draw (fm_device.h gauss_draw)."""
     u64 = np.uint64
     e = np.asarray(e, dtype=np.uint64)
 
