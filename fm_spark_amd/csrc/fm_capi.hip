@@ -32,21 +32,32 @@ void report_stale(hipError_t e) {
     fprintf(stderr, "[libfm_hip] cleared a stale HIP error left by an earlier call: %d %s\n", (int)e, hipGetErrorString(e));
 }
 
+// live device memory of the process (fm_device_bytes_live / fm_device_allocs_live): every device
+// allocation of the library is a DevBuf, so these two are exact
+static std::atomic<int64_t> g_dev_bytes_live{0}, g_dev_allocs_live{0};
+
 void DevBuf::ensure(size_t n) {
-  if (n <= bytes && p) return;
+  if (n <= bytes && p && !borrowed) return;
   // growing: work already queued on any stream may still read the old buffer (asynchronous
   // steps), so the device drains before it is freed
-  if (p) FM_HIP_CHECK(hipDeviceSynchronize());
+  if (p && !borrowed) FM_HIP_CHECK(hipDeviceSynchronize());
   release();
   if (n == 0) n = 16;
   FM_HIP_CHECK(hipMalloc(&p, n));
   bytes = n;
+  g_dev_bytes_live.fetch_add((int64_t)n, std::memory_order_relaxed);
+  g_dev_allocs_live.fetch_add(1, std::memory_order_relaxed);
 }
 
 void DevBuf::release() {
-  if (p) (void)hipFree(p);
+  if (p && !borrowed) {
+    (void)hipFree(p);
+    g_dev_bytes_live.fetch_sub((int64_t)bytes, std::memory_order_relaxed);
+    g_dev_allocs_live.fetch_sub(1, std::memory_order_relaxed);
+  }
   p = nullptr;
   bytes = 0;
+  borrowed = false;
 }
 
 // How many contiguous chunks parallel_chunks cuts [0, n) into (one per pool thread, at least
@@ -394,6 +405,9 @@ extern "C" {
 
 const char* fm_last_error(void) { return g_last_error.c_str(); }
 
+int64_t fm_device_bytes_live(void) { return g_dev_bytes_live.load(std::memory_order_relaxed); }
+int64_t fm_device_allocs_live(void) { return g_dev_allocs_live.load(std::memory_order_relaxed); }
+
 int fm_create(const fm_config* cfg, fm_ctx** out) {
   return guarded_free([&]() -> int {
     FM_REQUIRE(cfg && out, "null argument");
@@ -516,9 +530,6 @@ int fm_load_tables(fm_ctx* ctx, const int32_t* ids, int64_t n, const double* w, 
     launch_load_rows(ctx->view(), di.as<int32_t>(), n, dw.as<double>(), dv.as<double>(), ctx->epoch,
                      ctx->cum_host.back(), ctx->stream);
     FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    di.release();
-    dw.release();
-    dv.release();
     return FM_OK;
   });
 }
@@ -537,7 +548,6 @@ int fm_init_random(fm_ctx* ctx, const int32_t* ids, int64_t n) {
     launch_init_random(ctx->view(), di.as<int32_t>(), n, 0, ctx->cfg.seed, ctx->cfg.init_sd, ctx->epoch,
                        ctx->cum_host.back(), ctx->stream);
     FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    di.release();
     return FM_OK;
   });
 }
@@ -565,7 +575,6 @@ int64_t fm_num_present(fm_ctx* ctx) {
     launch_count_present(ctx->view(), d.as<int64_t>(), ctx->stream);
     FM_HIP_CHECK(hipMemcpyAsync(&n, d.p, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    d.release();
     return FM_OK;
   });
   return rc == FM_OK ? n : rc;
@@ -802,7 +811,6 @@ int fm_batch_create_splits(fm_ctx* ctx, const fm_csr* csr, int32_t n_splits, con
     b->split_rp.ensure(sizeof(int64_t) * (csr->n_rows + n_splits));
     launch_split_rebase(b->dev, dsr.as<int64_t>(), n_splits, b->split_rp.as<int64_t>(), ctx->stream);
     FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    dsr.release();
     *out = b.release();
     return FM_OK;
   });
@@ -906,16 +914,11 @@ int fm_batch_split_view(fm_ctx* ctx, const fm_batch* data, int32_t split, fm_bat
     b->view_of = data;
     b->dev.n_rows = r1 - r0;
     b->dev.nnz = e1 - e0;
-    b->dev.row_ptr.p = data->split_rp.as<int64_t>() + r0 + split;
-    b->dev.row_ptr.bytes = sizeof(int64_t) * (r1 - r0 + 1);
-    b->dev.col.p = data->dev.col.as<uint32_t>() + e0;
-    b->dev.col.bytes = sizeof(uint32_t) * (e1 - e0);
-    b->dev.ent.p = data->dev.ent.as<uint2>() + e0;
-    b->dev.ent.bytes = sizeof(uint2) * (e1 - e0);
-    b->dev.xs.p = data->dev.xs.as<float>() + e0;
-    b->dev.xs.bytes = sizeof(float) * (e1 - e0);
-    b->dev.label.p = data->dev.label.as<double>() + r0;
-    b->dev.label.bytes = sizeof(double) * (r1 - r0);
+    b->dev.row_ptr.borrow(data->split_rp.as<int64_t>() + r0 + split, sizeof(int64_t) * (r1 - r0 + 1));
+    b->dev.col.borrow(data->dev.col.as<uint32_t>() + e0, sizeof(uint32_t) * (e1 - e0));
+    b->dev.ent.borrow(data->dev.ent.as<uint2>() + e0, sizeof(uint2) * (e1 - e0));
+    b->dev.xs.borrow(data->dev.xs.as<float>() + e0, sizeof(float) * (e1 - e0));
+    b->dev.label.borrow(data->dev.label.as<double>() + r0, sizeof(double) * (r1 - r0));
     b->max_id = data->max_id;
     b->prepared = false;
     b->host_rp.clear();
@@ -1009,7 +1012,6 @@ int fm_predict(fm_ctx* ctx, const fm_csr* csr, double lo, double hi, double* pre
     launch_predict(ctx->view(), b->dev, ctx->cum_host.back(), ctx->cfg.w0, lo, hi, dp.as<double>(), ctx->stream);
     FM_HIP_CHECK(hipMemcpyAsync(pred, dp.p, sizeof(double) * csr->n_rows, hipMemcpyDeviceToHost, ctx->stream));
     FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    dp.release();
     return FM_OK;
   });
 }
@@ -1029,7 +1031,6 @@ int fm_predict_batch(fm_ctx* ctx, fm_batch* b, double lo, double hi, double* pre
     ctx->prof_end("predict", e0, ctx->stream);
     FM_HIP_CHECK(hipMemcpyAsync(pred, dp.p, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
     FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    dp.release();
     return FM_OK;
   });
 }
@@ -1047,7 +1048,6 @@ int fm_init_from_batch(fm_ctx* ctx, fm_batch* b, int64_t* n_present) {
       launch_count_present(ctx->view(), d.as<int64_t>(), ctx->stream);
       FM_HIP_CHECK(hipMemcpyAsync(n_present, d.p, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
       FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      d.release();
     } else {
       FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
@@ -1145,9 +1145,6 @@ int fm_vector_sum_by_key(fm_ctx* ctx, const int32_t* keys, int64_t n, const doub
     FM_HIP_CHECK(hipMemcpy(out_keys, dok.p, sizeof(int32_t) * nu, hipMemcpyDeviceToHost));
     FM_HIP_CHECK(hipMemcpy(out_sums, dos.p, sizeof(double) * nu * k, hipMemcpyDeviceToHost));
     *n_out = nu;
-    DevBuf* bufs[] = {&dk, &dvec, &dok, &dos, &drun, &dn, &sw.keys_a, &sw.keys_b, &sw.vals_a, &sw.vals_b,
-                      &sw.counts, &sw.digit_tot};
-    for (auto* bb : bufs) bb->release();
     return FM_OK;
   });
 }

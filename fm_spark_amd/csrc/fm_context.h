@@ -75,6 +75,7 @@ struct ShardBatchState {
     for (hipEvent_t e : {ready_fwd, ready_upd, last_use})
       if (e) (void)hipEventDestroy(e);
     ready_fwd = ready_upd = last_use = nullptr;
+    // (each DevBuf frees itself; released here only for the order: device set, events waited for)
     for (DevBuf* b : {&pairidx, &poff, &src_off, &pair_ptr, &skeys, &sents}) b->release();
   }
 };
@@ -129,10 +130,7 @@ struct fm_batch {
   // a view's borrowed pointers dropped (before the batch frees or grows its own)
   void detach_view() {
     if (!view_of) return;
-    for (DevBuf* d : {&dev.row_ptr, &dev.col, &dev.ent, &dev.xs, &dev.label}) {
-      d->p = nullptr;
-      d->bytes = 0;
-    }
+    for (DevBuf* d : {&dev.row_ptr, &dev.col, &dev.ent, &dev.xs, &dev.label}) d->release();  // borrowed: not freed
     view_of = nullptr;
   }
   std::unique_ptr<ShardBatchState> sh;  // sharded contexts only
@@ -146,6 +144,9 @@ struct fm_batch {
     for (hipEvent_t e : {ready, last_use, sel_copied, built})
       if (e) (void)hipEventDestroy(e);
     detach_view();
+    // The buffers would free themselves (DevBuf's destructor): the list below stays only for the order --
+    // on the batch's device, after the events above were waited for.  A buffer missing from it is freed
+    // a moment later by its own destructor, not leaked.
     split_rp.release();
     skeys.release();
     sents.release();
@@ -289,9 +290,7 @@ struct fm_ctx {
     FM_HIP_CHECK(hipMemset(nb.p, 0, sizeof(double) * 3 * c));
     if (hist_cap > 0)
       FM_HIP_CHECK(hipMemcpy(nb.p, loss_hist.p, sizeof(double) * 3 * hist_cap, hipMemcpyDeviceToDevice));
-    loss_hist.release();
-    loss_hist = nb;
-    nb.p = nullptr;
+    loss_hist = std::move(nb);  // the old history is freed (the stream was drained above)
     hist_cap = c;
   }
 
@@ -316,6 +315,8 @@ struct fm_ctx {
     if (ev_upd_done) (void)hipEventDestroy(ev_upd_done);
     if (side_own) (void)hipStreamSynchronize(side_own);
     if (side_own) (void)hipStreamDestroy(side_own);
+    // The buffers would free themselves (DevBuf's destructor): released here only for the order -- on
+    // the context's device, after its streams drained and before the main stream is destroyed.
     rec.release();
     loss_hist.release();
     DevBuf* bufs[] = {&work.S, &work.yl, &work.loss_part, &work.part, &work.ucnt,

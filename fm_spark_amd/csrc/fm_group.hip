@@ -149,7 +149,9 @@ struct GroupBatch {
   bool routed = false;
   Pinned cnt_pin;
   std::vector<hipEvent_t> ev_cnt;  // per local rank: its side-stream work of phase 1 is done
-  Group* g = nullptr;              // the group while this batch is its pending phase 2
+  // the group while this batch is its pending phase 2, and only then: set and cleared together with
+  // Group::pending (set_pending / clear_pending), so a batch that outlives its group holds no pointer to it
+  Group* g = nullptr;
   // fm_batch_from_rows with this batch as the dataset: every local rank's full copy of it (member
   // batches on each rank's device, made at the first selection), from which each rank gathers its
   // share of a split's rows
@@ -253,8 +255,18 @@ struct Group {
   bool sharded() const { return mode == FM_PARALLEL_SHARDED; }
   // f(l) for every local rank, in parallel on the rank workers
   void each(const std::function<void(int)>& f) { workers.each(L, f); }
-  ~Group() {
+  // pending and its back pointer GroupBatch::g change only here: gb.g == this exactly while pending == &gb
+  void set_pending(GroupBatch& gb) {
+    clear_pending();
+    gb.g = this;
+    pending = &gb;
+  }
+  void clear_pending() {
     if (pending) pending->g = nullptr;
+    pending = nullptr;
+  }
+  ~Group() {
+    clear_pending();
     for (auto& h : host_b) h.reset();
     for (auto& r : ranks) {
       if (!r.m) continue;
@@ -263,6 +275,8 @@ struct Group {
       if (r.comm_x) (void)ncclCommDestroy(r.comm_x);
       if (r.comm_side) (void)ncclCommDestroy(r.comm_side);
       if (r.comm_main) (void)ncclCommDestroy(r.comm_main);
+      // (each DevBuf frees itself; released here only for the order: device set and drained, before
+      // the rank's events and exchange stream go)
       for (DevBuf* d : {&r.partials, &r.part_in, &r.s_send, &r.s_recv, &r.pc_out, &r.pc_in, &r.pred, &r.grad, &r.gtmp,
                         &r.xg_send, &r.xg_recv})
         d->release();
@@ -278,7 +292,7 @@ struct Group {
 };
 
 GroupBatch::~GroupBatch() {
-  if (g && g->pending == this) g->pending = nullptr;
+  if (g) g->clear_pending();  // g is non-null only while this batch is the live group's pending one
   for (size_t l = 0; l < ev_cnt.size(); ++l) {
     (void)hipSetDevice(parts[l].device);
     (void)hipEventSynchronize(ev_cnt[l]);
@@ -286,6 +300,7 @@ GroupBatch::~GroupBatch() {
   }
   for (auto& p : parts) {
     (void)hipSetDevice(p.device);
+    // (each DevBuf frees itself; released here only to do it on the part's device)
     for (DevBuf* d : {&p.send_slot, &p.send_ent, &p.recv_slot, &p.recv_ent}) d->release();
     if (p.b) fm_batch_destroy(p.b);
     p.b = nullptr;
@@ -625,7 +640,7 @@ void drop_route(Group& g, GroupBatch& gb) {
     FM_HIP_CHECK(hipEventSynchronize(gb.ev_cnt[l]));
   }
   gb.routed = false;
-  if (g.pending == &gb) g.pending = nullptr;
+  if (g.pending == &gb) g.clear_pending();
 }
 
 // Sharded prepare, phase 2 (fm_shard.hip phase 1b): the host reads the job's counts (the one host
@@ -640,7 +655,7 @@ void finish_routes(Group& g, GroupBatch& gb) {
       FM_HIP_CHECK(hipEventSynchronize(gb.ev_cnt[l]));
     }
   }
-  if (g.pending == &gb) g.pending = nullptr;
+  if (g.pending == &gb) g.clear_pending();
   gb.routed = false;
   const unsigned long long* rc = reinterpret_cast<const unsigned long long*>(gb.cnt_pin.p);  // [source][pairs | entries]
   std::vector<const char*> ss(L), se(L);
@@ -1399,8 +1414,7 @@ int group_batch_prepare(fm_ctx* ctx, fm_batch* b) {
     if (!gb.prefetched && !gb.routed) {
       HostClock hc(g, "host_prepare_route");
       launch_routes(g, gb);
-      gb.g = &g;
-      g.pending = &gb;
+      g.set_pending(gb);
     }
   } else {
     for (int l = 0; l < g.L; ++l) mcheck(fm_batch_prepare(g.ranks[l].m, gb.parts[l].b), "fm_batch_prepare");
@@ -1487,7 +1501,6 @@ int group_init_from_batch(fm_ctx* ctx, fm_batch* b, int64_t* n_present) {
         launch_init_entries(r.m->view(), ids.as<uint32_t>(), n_in, r.m->cfg.seed, r.m->cfg.init_sd, r.m->epoch,
                             r.m->cum_host.back(), r.m->stream);
         FM_HIP_CHECK(hipStreamSynchronize(r.m->stream));
-        ids.release();
       });
     }
   } else {
@@ -1503,7 +1516,6 @@ int group_init_from_batch(fm_ctx* ctx, fm_batch* b, int64_t* n_present) {
           launch_init_entries(r.m->view(), col.as<uint32_t>(), p.nnz, r.m->cfg.seed, r.m->cfg.init_sd, r.m->epoch,
                               r.m->cum_host.back(), r.m->stream);
           FM_HIP_CHECK(hipStreamSynchronize(r.m->stream));
-          col.release();
         });
       }
   }

@@ -71,10 +71,41 @@ inline int32_t record_stride(int32_t kp) {
   return (need + 31) / 32 * 32;
 }
 
-// device buffer helper
+// device buffer: owns its allocation (freed by the destructor; move-only), or borrows a range of
+// another buffer (a view: never freed here).  Every device allocation of the library is one of
+// these, counted in fm_device_bytes_live / fm_device_allocs_live.
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  bool borrowed = false;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes), borrowed(o.borrowed) {
+    o.p = nullptr;
+    o.bytes = 0;
+    o.borrowed = false;
+  }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      bytes = o.bytes;
+      borrowed = o.borrowed;
+      o.p = nullptr;
+      o.bytes = 0;
+      o.borrowed = false;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  // n bytes at q inside a buffer someone else owns (what this one owned is freed)
+  void borrow(const void* q, size_t n) {
+    release();
+    p = const_cast<void*>(q);
+    bytes = n;
+    borrowed = true;
+  }
   void ensure(size_t n);
   // at least n bytes; a growth takes an eighth more (batches refilled with slightly different
   // sizes, e.g. randomSplit splits, then stop growing: a growth drains the device)

@@ -798,9 +798,9 @@ void shard_owner_partials(fm_ctx* ctx, fm_batch* b, void* partials_out, uint32_t
     BatchDev view;
     view.n_rows = S.P;
     view.nnz = S.n;
-    view.row_ptr.p = S.pair_ptr.p;
-    view.col.p = const_cast<uint32_t*>(S.recv_slot);
-    view.ent.p = const_cast<uint2*>(S.recv_ent);
+    view.row_ptr.borrow(S.pair_ptr.p, S.pair_ptr.bytes);
+    view.col.borrow(S.recv_slot, sizeof(uint32_t) * S.n);
+    view.ent.borrow(S.recv_ent, sizeof(uint2) * S.n);
     StepParams p{};
     p.cumE = ctx->cum_host.back();
     int64_t nblk = 0;
@@ -814,7 +814,6 @@ void shard_owner_partials(fm_ctx* ctx, fm_batch* b, void* partials_out, uint32_t
     }
     launch_forward(ctx->view(), view, ctx->work, p, st, &nblk, reinterpret_cast<float*>(partials_out), &xo,
                    ctx->cfg.wire == FM_WIRE_FP64);
-    view.row_ptr.p = view.col.p = view.ent.p = nullptr;  // borrowed
     FM_HIP_CHECK(hipGetLastError());
   }
   if (chunk + 1 == chunks) {

@@ -166,7 +166,11 @@ int fm_set_side_stream(fm_ctx* ctx, void* hip_stream);
 /* Wait for everything the context has enqueued: its step stream, its side stream (preparations) and
  * its copy stream (fm_step uploads, fm_batch_from_rows gathers); a multi-GPU context, every rank's. */
 int fm_sync(fm_ctx* ctx);
-/* Pre-size the per-step workspace so no step allocates. */
+/* Pre-size the per-step workspace (the forward's, sort's and update's scratch) so that no step on a
+ * device-resident batch of at most max_rows x max_nnz allocates.  What belongs to a batch is sized
+ * when the batch is first seen, not here: a batch's own prepared view, a multi-GPU context's
+ * per-batch routing state and wire buffers, and fm_step's two upload slots, each of which grows to
+ * the largest host batch it has held (steady after every batch size has passed through both). */
 int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz);
 
 /* ---- tables (C9: Strength / FactorizedInteraction, Model.scala:275-289) ------------ */
@@ -199,6 +203,12 @@ int64_t fm_epoch(fm_ctx* ctx);
 /* ---- mini-batches --------------------------------------------------------------------- */
 /* Copy a CSR batch into device memory once (validated: ids in range, row_ptr monotone). */
 int fm_batch_create(fm_ctx* ctx, const fm_csr* csr, fm_batch** out);
+/* Frees the batch's device memory once the work queued on it has run.  A batch may outlive its
+ * context, also a multi-GPU context's (fm_destroy drains the context's streams; the batch's
+ * destructor touches only its own events and buffers, and a multi-GPU batch points at its context
+ * only while it is that context's pending prepare, which fm_destroy clears), but no call takes it
+ * after that except this one; a view made by
+ * fm_batch_split_view is destroyed before the dataset it borrows from is. */
 void fm_batch_destroy(fm_batch* b);
 /* Sort the batch's entries by feature (the grouping the gradient reduction consumes) ahead
  * of its step, on the context's side stream, so the sort overlaps whatever the previous step
@@ -324,6 +334,12 @@ int fm_profile_enable(fm_ctx* ctx, int32_t on);
 int fm_profile_read(fm_ctx* ctx, char* names, int64_t names_cap, double* total_ms,
                     int64_t* launches, int64_t cap, int64_t* n);
 int fm_profile_reset(fm_ctx* ctx);
+/* Device memory the library holds right now, over every context, batch and device of the process:
+ * bytes and number of live allocations (every device allocation of the library is counted; exact,
+ * no context, no host synchronisation).  A steady-state call leaves both unchanged; destroying every
+ * context and batch returns both to 0. */
+int64_t fm_device_bytes_live(void);
+int64_t fm_device_allocs_live(void);
 
 /* ---- input format: Spark 2.1 `libsvm` data source (data/sample.txt, config c1) ------------ */
 /* MLUtils.parseLibSVMFile semantics: trimmed lines, '#'-lines and empty lines skipped, one-based

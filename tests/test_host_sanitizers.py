@@ -59,3 +59,27 @@ def test_host_pool_jobs_and_exceptions(tmp_path, san):
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "0 failure(s)" in r.stdout and "Sanitizer" not in r.stderr
+
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+LIB_DIR = os.path.join(ROOT, "fm_spark_amd", "lib")
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_group_batch_may_outlive_its_group_under_asan(tmp_path):
+    """fm_destroy before fm_batch_destroy on a multi-GPU context: the batch's back pointer to its
+    group (set while it is the group's pending prepare) is cleared whenever the pending batch changes
+    and when the group goes, so ~GroupBatch never reads a freed group.  tests/native/group_lifetime.cpp
+    includes fm_group.hip itself (host code under ASan, the rest from the built library) and makes no
+    device call."""
+    assert os.path.exists(os.path.join(LIB_DIR, "libfm_hip.so")), "run __graft_entry__.build() first"
+    exe = tmp_path / "group_lifetime"
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Xarch_host",
+                    "-fsanitize=address", os.path.join(HERE, "native", "group_lifetime.cpp"), "-o", str(exe),
+                    f"-L{LIB_DIR}", "-lfm_hip", "-L/opt/rocm/lib", "-lrccl", f"-Wl,-rpath,{LIB_DIR}",
+                    "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    # (the HIP runtime's own start-up allocations are not this test's business)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:verify_asan_link_order=0")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "0 failure(s)" in r.stdout and "AddressSanitizer" not in r.stderr
