@@ -137,7 +137,9 @@ void radix_sort_pairs64(SortWork& w, const uint32_t* keys_in, const uint2* vals_
                         const uint2** vals_out, uint32_t* final_keys = nullptr,
                         uint2* final_vals = nullptr);
 // Stable sort by key bits [lo_bit, hi_bit) only (the bits below ride along), output written to
-// final_keys / final_vals.
+// final_keys / final_vals.  The keys must hold nothing at hi_bit and above (fm_shard_route's end at
+// sb + ob): the last pass takes a whole digit, so such bits would be sorted on as well
+// (tests/test_gpu_sort.py test_sort_by_a_bit_range).
 void radix_sort_pairs64_bits(SortWork& w, const uint32_t* keys_in, const uint2* vals_in, int64_t n, int lo_bit,
                              int hi_bit, hipStream_t st, uint32_t* final_keys, uint2* final_vals);
 

@@ -19,6 +19,15 @@
 // between the count and the scatter, a third of a c3 pass's L2 requests; the step is bound by the
 // L2 request rate).
 // HBM traffic per pass: 4 B (count) + (4 + P) B read + (4 + P) B write per pair.
+//
+// tests/test_gpu_sort.py calls the three entry points directly (tests/native/sort_probe.hip) and
+// compares keys and payloads, element for element, with a stable host sort at every tile, chunk,
+// digit-plan and alignment edge of this file, and at fm_shard_route's bit ranges: run it after any
+// change here.
+// Every pass takes a whole RB-bit digit, the last one too.  The keys must therefore hold nothing
+// above the sorted field: below 2^key_bits, and for radix_sort_pairs64_bits below 2^hi_bit
+// (fm_internal.h).  With bits above it, a field whose width is no multiple of RB is sorted by them
+// as well ([10, 11) by [10, 19)); the test's bit ranges that end below bit 32 keep to the contract.
 #include <type_traits>
 
 #include "fm_device.h"
@@ -474,6 +483,9 @@ static void radix_sort_impl(SortWork& w, const uint32_t* keys_in, const P* vals_
     const bool last = p == passes - 1 && final_keys != nullptr;
     uint32_t* ko = last ? final_keys : kbuf[which];
     P* vo = last ? final_vals : vbuf[which];
+    // (cases 6-8: digit_bits never returns less than kMinRB = 9, so they are not reached; they are the
+    // digit widths of DESIGN.md §5's 7- and 8-bit measurements, kept so that kMinRB can be lowered
+    // for such a measurement again without touching the kernels' instantiations)
     switch (rb) {
       case 6: radix_pass<P, 6>(kin, vin, ko, vo, n, shift, w, ntiles, st); break;
       case 7: radix_pass<P, 7>(kin, vin, ko, vo, n, shift, w, ntiles, st); break;
