@@ -19,6 +19,8 @@
 // singleton: 92 % of a c3 batch's distinct rows) is updated here, by the sample that holds that
 // entry, instead of by the segmented update (see "Singleton rows" in fm_device.h).
 // (the modes are FwdMode, fm_internal.h; FwdOut::mode names the one a launch runs)
+#include <atomic>
+
 #include "fm_device.h"
 
 namespace fmhip {
@@ -448,6 +450,19 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
   if constexpr (MODE == kTrain || MODE == kTrainFused) block_loss_partial(loss_acc, nloss, loss_part);
 }
 
+// The suite's seam (fm_internal.h, set_forward_grid_cap): the block cap in force, 0 = kFwdGrid, and
+// the launches made under a cap.
+std::atomic<int64_t> g_grid_cap{0};
+std::mutex g_log_mu;  // a group's ranks launch from their own threads
+std::vector<FwdLaunchRec> g_log;
+int64_t g_logged = 0;
+
+void log_launch(const FwdLaunchRec& r) {
+  std::lock_guard<std::mutex> lk(g_log_mu);
+  if ((int)g_log.size() < kFwdLogCap) g_log.push_back(r);
+  ++g_logged;
+}
+
 // The one launch of k_forward: the arguments each mode takes.
 template <int GS, int TEAM, int MODE, int U>
 void launch_fwd_m(const TableView& T, const BatchDev& b, StepWork& w, const StepParams& p, hipStream_t st,
@@ -455,9 +470,12 @@ void launch_fwd_m(const TableView& T, const BatchDev& b, StepWork& w, const Step
   constexpr bool PARTIAL = MODE == kPartial || MODE == kPartial64, TRAIN = MODE == kTrain || MODE == kTrainFused;
   constexpr int TPB = kBlock / TEAM;
   int64_t blocks = (b.n_rows + TPB - 1) / TPB;
-  if (blocks > kFwdGrid) blocks = kFwdGrid;
+  const int64_t cap = g_grid_cap.load(std::memory_order_relaxed);  // the suite's seam; 0 = the tuned grid
+  const int64_t grid = cap > 0 ? cap : kFwdGrid;
+  if (blocks > grid) blocks = grid;
   if (blocks < 1) blocks = 1;
   *nblk = blocks;
+  if (cap > 0) log_launch(FwdLaunchRec{MODE, GS, TEAM, U, PARTIAL ? xo.ch_c : 0, PARTIAL ? xo.ch_C : 1, blocks, b.n_rows});
   float* S_out = nullptr;
   float2* yl_out = nullptr;
   int64_t sstr = T.kp, ystr = 1;
@@ -518,6 +536,22 @@ void launch_partial_t(const TableView& T, const BatchDev& b, StepWork& w, const 
 }
 
 }  // namespace
+
+void set_forward_grid_cap(int64_t blocks) { g_grid_cap.store(blocks > 0 ? blocks : 0, std::memory_order_relaxed); }
+
+void clear_forward_log() {
+  std::lock_guard<std::mutex> lk(g_log_mu);
+  g_log.clear();
+  g_logged = 0;
+}
+
+int read_forward_log(FwdLaunchRec* out, int cap) {
+  std::lock_guard<std::mutex> lk(g_log_mu);
+  for (int i = 0; out && i < cap && i < (int)g_log.size(); ++i) out[i] = g_log[i];
+  return (int)g_logged;
+}
+
+FwdConsts forward_consts() { return FwdConsts{kFwdGrid, kBlock, kFuseNS, kFuseU}; }
 
 void launch_forward(const TableView& T, const BatchDev& b, StepWork& w, const StepParams& p, hipStream_t st,
                     int64_t* nblk, float* partial_out, const FwdOut* pred, bool partial_wide) {

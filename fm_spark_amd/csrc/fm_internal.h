@@ -215,6 +215,27 @@ constexpr int kMaxChunkSources = 64;  // sources a chunked partial pass can spli
 void launch_forward(const TableView& T, const BatchDev& b, StepWork& w, const StepParams& p,
                     hipStream_t st, int64_t* n_fwd_blocks, float* partial_out = nullptr,
                     const FwdOut* pred = nullptr, bool partial_wide = false);
+// A seam for the suite (tests/native/forward_probe.hip), not configuration: a process-wide cap on the
+// forward's blocks in place of the tuned constant, so a test can make every team walk several
+// samples at a batch of a few hundred rows.  0 (the default) = the tuned grid.  It is not in
+// include/fm_hip.h and is not read from the environment.  While a cap is set, every forward launch
+// of the process (the step, the fused step, predict, loss-grad, each rank's partial passes) is
+// appended to a bounded log (the first kFwdLogCap launches since the last clear); with no cap set
+// nothing is logged and a launch costs one relaxed load.
+struct FwdLaunchRec {
+  int32_t mode, gs, team, u;  // the k_forward instantiation: FwdMode, lanes per row, lanes per sample, passes in flight
+  int32_t chunk, chunks;      // the partial pass's chunk (0 of 1 elsewhere): the launch walks that chunk's pairs only
+  int64_t blocks, rows;       // the grid launched, and the batch's rows (all the owner's pairs, for a partial pass)
+};
+constexpr int kFwdLogCap = 256;
+struct FwdConsts {
+  int32_t grid, block, fuse_ns, fuse_u;  // the tuned block cap, threads per block, kFuseNS, kFuseU
+};
+void set_forward_grid_cap(int64_t blocks);
+void clear_forward_log();
+int read_forward_log(FwdLaunchRec* out, int cap);  // copies at most cap records; returns the launches under a cap since the last clear
+FwdConsts forward_consts();
+
 // per-sample inputs of the segmented update: S rows of s_stride floats, {yhat, y} at yl[s * yl_stride]
 struct SegSource {
   const float* S;

@@ -3,7 +3,9 @@
 Test infrastructure, not C-ABI: a small shared library beside libfm_hip.so, linked against it, that
 lets tests/test_gpu_sort.py call fmhip::radix_sort_pairs / radix_sort_pairs64 /
 radix_sort_pairs64_bits of the built library directly.  __graft_entry__.build() calls
-build_probe() after the library; the tests only load what was built.
+build_probe() after the library; the tests only load what was built.  The same library carries a
+second source, tests/native/forward_probe.hip: the door to the forward's launch-size seam
+(tests/forward_probe.py wraps it).
 """
 
 from __future__ import annotations
@@ -19,6 +21,8 @@ import numpy as np
 HERE = Path(__file__).resolve().parent
 ROOT = HERE.parent
 SRC = HERE / "native" / "sort_probe.hip"
+# the same library carries the forward's launch-size door (tests/forward_probe.py)
+SRCS = [SRC, HERE / "native" / "forward_probe.hip"]
 LIB_DIR = ROOT / "fm_spark_amd" / "lib"
 PROBE = LIB_DIR / "libfm_sort_probe.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -41,10 +45,11 @@ def build_probe(verbose: bool = False, force: bool = False, lib: Path | None = N
     out = Path(out) if out else lib.parent / PROBE.name
     if not lib.exists():
         raise RuntimeError(f"{lib} is missing: build the library first")
-    deps = [SRC, ROOT / "fm_spark_amd" / "csrc" / "fm_internal.h", ROOT / "include" / "fm_hip.h", lib]
+    deps = [*SRCS, ROOT / "fm_spark_amd" / "csrc" / "fm_internal.h", ROOT / "include" / "fm_hip.h", lib]
     if not force and out.exists() and all(d.stat().st_mtime <= out.stat().st_mtime for d in deps):
         return out
-    cmd = [HIPCC, f"--offload-arch={ARCH}", "-O2", "-std=c++17", "-fPIC", "-Wall", "-shared", str(SRC), "-o", str(out),
+    cmd = [HIPCC, f"--offload-arch={ARCH}", "-O2", "-std=c++17", "-fPIC", "-Wall", "-shared", *map(str, SRCS), "-o",
+           str(out),
            f"-L{lib.parent}", f"-l:{lib.name}", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)

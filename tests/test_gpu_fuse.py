@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 from oracle import fm_ref as R
-from problems import make_problem
+from problems import make_problem, make_rows
 from test_gpu_parity import assert_tables, to_host
 
 pytestmark = pytest.mark.gpu
@@ -149,16 +149,34 @@ def test_fused_all_singletons_and_all_multi(gpu):
 
 @pytest.mark.parametrize("k", [8, 16])
 def test_fused_teams_take_many_samples_of_mixed_lengths(gpu, k):
-    """40,000 rows, more than the forward's 2048 blocks x 8 teams, so every team walks several
-    samples, of 1..19 entries (odd lengths below the 8 / 16 entry slots of a pass included).  A lane
-    group with no entry in a sample flushes the previous sample's singleton rows before the entry
-    loop while its neighbour flushes inside it; each must still write the other's row headers (the
-    paired stores), or w misses its update and V is shrunk twice.  Three steps, the fused table
+    """At the production grid: twice the forward's block cap x 8 teams, and 37 rows more, so every team
+    walks at least two samples, of 0..19 entries (odd lengths below the 8 / 16 entry slots of a pass
+    included).  The row count is taken from the forward probe (tests/forward_probe.py), not written
+    here, and the launch log -- kept by running under a cap equal to the tuned grid, which launches what
+    the default does -- shows that every team took two samples: a retuned grid moves this test with it
+    (tests/test_gpu_forward_teams.py walks the hand-over at every edge under a cap of 1 and 3 blocks).
+    A lane group with no entry in a sample flushes the previous sample's singleton rows before the
+    entry loop while its neighbour flushes inside it; each must still write the other's row headers
+    (the paired stores), or w misses its update and V is shrunk twice.  Three steps, the fused table
     against the unfused one and the fp64 oracle, with an L1 strong enough to show a double shrink."""
-    F = 400_000
-    csrs = [make_problem(900 + i + k, 40_000, F, k, 10, empty_frac=0.05)[0] for i in range(2)]
+    import forward_probe as fp
+
+    c = fp.consts()
+    F, rows = 400_000, 2 * c.grid * (c.block // 32) + 37
+    csrs = []
+    for i in range(2):
+        rng = np.random.default_rng(900 + i + k)
+        lengths = np.where(rng.random(rows) < 0.05, 0, rng.integers(1, 20, rows))
+        kinds = (rng.random(int(lengths.sum())) < 0.15).astype(np.int64)  # ids no other entry has, among repeated ones
+        csrs.append(make_rows(900 + i + k, lengths, F, k, kinds=kinds, pool=F // 2, x_scale=False)[0])
     _, ids, w, V = make_problem(76, 1, F, k, 1)
-    fused = _steps(True, csrs, F, k, ids, w, V, 3, reg=1e-2)
+    with fp.grid_cap(c.grid):  # (the tuned grid again on the way out, whatever happens)
+        fused = _steps(True, csrs, F, k, ids, w, V, 3, reg=1e-2)
+        log = fp.read_log()
+    assert len(log) == 3
+    for r in log:
+        assert (r.mode, r.u, r.blocks, r.rows) == (fp.TRAIN_FUSED, c.fuse_u, c.grid, rows), r
+        assert r.rows >= 2 * r.blocks * (c.block // r.team), r  # every team took at least two samples
     unfused = _steps(False, csrs, F, k, ids, w, V, 3, reg=1e-2)
     _assert_same(fused, unfused)
     model = R.Model.empty(F, k)
