@@ -21,6 +21,7 @@ FM_TRANSPORT_AUTO, FM_TRANSPORT_RCCL, FM_TRANSPORT_COPY = 0, 1, 2
 FM_MAX_LOCAL = 16
 FM_FUSE_DEFAULT, FM_FUSE_ON, FM_FUSE_OFF = 0, 1, -1
 FM_WIRE_FP32, FM_WIRE_FP64 = 0, 1
+FM_RANK_MAX_TOP = 1024
 
 
 class FMError(RuntimeError):
@@ -106,6 +107,9 @@ SIGNATURES = {
     "fm_loss_history": (C.c_int, [_P, _DP, C.c_int64, _I64P]),
     "fm_predict": (C.c_int, [_P, C.POINTER(fm_csr), C.c_double, C.c_double, _DP]),
     "fm_predict_batch": (C.c_int, [_P, _P, C.c_double, C.c_double, _DP]),
+    "fm_rank_candidates": (C.c_int, [_P, C.POINTER(fm_csr), C.POINTER(fm_csr), C.c_int32, C.c_double, C.c_double,
+                                     _I32P, _DP]),
+    "fm_rank_batch": (C.c_int, [_P, _P, _P, C.c_int32, C.c_double, C.c_double, _I32P, _DP]),
     "fm_init_from_batch": (C.c_int, [_P, _P, _I64P]),
     "fm_loss_grad": (C.c_int, [_P, C.POINTER(fm_csr), _DP, _DP, _DP, _DP]),
     "fm_calc_loss_grad": (C.c_int, [_P, C.POINTER(fm_csr), C.c_double, C.c_uint64, _DP, _DP, _DP, _DP]),

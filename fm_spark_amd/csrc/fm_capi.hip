@@ -1035,6 +1035,107 @@ int fm_predict_batch(fm_ctx* ctx, fm_batch* b, double lo, double hi, double* pre
   });
 }
 
+// fm_rank_candidates / fm_rank_batch on one whole table: the two row sets' summaries, then the score
+// and merge passes over the contexts in tiles whose split lists fit the budget (fm_rank.hip).
+static int rank_impl(fm_ctx* ctx, const BatchDev& bu, const BatchDev& bc, int32_t n_top, double lo, double hi,
+                     int32_t* top_index, double* top_score) {
+  const int64_t U = bu.n_rows, Cn = bc.n_rows;
+  const int kp = ctx->kp;
+  RankWork& w = ctx->rank;
+  const size_t srow = sizeof(double) * (size_t)(kp + 2);
+  w.sum_u.ensure_slack(srow * U);
+  w.sum_c.ensure_slack(srow * Cn);
+  w.cnt_u.ensure_slack(sizeof(uint32_t) * U);
+  w.cnt_c.ensure_slack(sizeof(uint32_t) * Cn);
+  w.bias_u.ensure_slack(sizeof(double) * U);
+  w.bias_c.ensure_slack(sizeof(double) * Cn);
+  const int splits = rank_splits(Cn, U);
+  const int64_t tile = std::min<int64_t>(U, rank_ctx_tile(splits, n_top));
+  w.lkey.ensure_slack(sizeof(uint64_t) * (size_t)(tile * splits * n_top));
+  w.lidx.ensure_slack(sizeof(uint32_t) * (size_t)(tile * splits * n_top));
+  w.out_idx.ensure_slack(sizeof(int32_t) * (size_t)(U * n_top));
+  w.out_score.ensure_slack(sizeof(double) * (size_t)(U * n_top));
+  hipStream_t st = ctx->stream;
+  const TableView T = ctx->view();
+  const double cumE = ctx->cum_host.back(), w0 = ctx->cfg.w0;
+  hipEvent_t e0 = ctx->prof_begin(st);
+  launch_summary(T, bu, cumE, w.sum_u.as<double>(), w.cnt_u.as<uint32_t>(), st);
+  launch_summary(T, bc, cumE, w.sum_c.as<double>(), w.cnt_c.as<uint32_t>(), st);
+  launch_rank_bias(w.sum_u.as<double>(), U, kp, w.bias_u.as<double>(), st);
+  launch_rank_bias(w.sum_c.as<double>(), Cn, kp, w.bias_c.as<double>(), st);
+  ctx->prof_end("rank_summary", e0, st);
+  for (int64_t u0 = 0; u0 < U; u0 += tile) {
+    const int64_t Ut = std::min<int64_t>(tile, U - u0);
+    e0 = ctx->prof_begin(st);
+    launch_rank_score(w.sum_u.as<double>() + u0 * kp, w.bias_u.as<double>() + u0, w.cnt_u.as<uint32_t>() + u0, Ut,
+                      w.sum_c.as<double>(), w.bias_c.as<double>(), w.cnt_c.as<uint32_t>(), Cn, kp, splits, n_top, w0,
+                      w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), st);
+    ctx->prof_end("rank_score", e0, st);
+    e0 = ctx->prof_begin(st);
+    launch_rank_merge(w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), Ut, splits, n_top, w.cnt_u.as<uint32_t>() + u0,
+                      w.cnt_c.as<uint32_t>(), w0, lo, hi, w.out_idx.as<int32_t>() + u0 * n_top,
+                      w.out_score.as<double>() + u0 * n_top, st);
+    ctx->prof_end("rank_merge", e0, st);
+  }
+  FM_HIP_CHECK(hipMemcpyAsync(top_index, w.out_idx.p, sizeof(int32_t) * (size_t)(U * n_top), hipMemcpyDeviceToHost, st));
+  FM_HIP_CHECK(hipMemcpyAsync(top_score, w.out_score.p, sizeof(double) * (size_t)(U * n_top), hipMemcpyDeviceToHost, st));
+  FM_HIP_CHECK(hipStreamSynchronize(st));
+  return FM_OK;
+}
+
+// the argument rules both entry points share, for U contexts and Cn candidates; false: nothing to do
+static bool rank_check(const fm_ctx* ctx, int64_t U, int64_t Cn, int32_t n_top, const int32_t* top_index,
+                       const double* top_score) {
+  FM_REQUIRE(ctx->cfg.shard_count == 1,
+             "fm_rank needs the whole table on one device (shard_count == 1): a row-sharded table is not ranked yet");
+  if (U == 0) return false;
+  FM_REQUIRE(Cn >= 1, "fm_rank needs at least one candidate row");
+  FM_REQUIRE(Cn < (int64_t(1) << 31), "fm_rank takes fewer than 2^31 candidate rows");
+  FM_REQUIRE(n_top >= 1 && n_top <= FM_RANK_MAX_TOP && n_top <= Cn, "n_top must be in [1, min(candidate rows, FM_RANK_MAX_TOP)]");
+  FM_REQUIRE(top_index != nullptr && top_score != nullptr, "null argument");
+  return true;
+}
+
+int fm_rank_candidates(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, int32_t n_top, double lo, double hi,
+                       int32_t* top_index, double* top_score) {
+  if (ctx && ctx->group) {
+    // a replicated group's replicas are identical: member 0 answers, with the group locked (as fm_loss_grad)
+    return guarded(ctx, [&]() -> int {
+      FM_REQUIRE(ctx->cfg.parallel == FM_PARALLEL_REPLICATED,
+                 "fm_rank needs the whole table on one device (a replicated or single-table context): a row-sharded "
+                 "table is not ranked yet");
+      return fm_rank_candidates(group_member0(ctx), contexts, candidates, n_top, lo, hi, top_index, top_score);
+    });
+  }
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
+    if (!rank_check(ctx, contexts->n_rows, candidates->n_rows, n_top, top_index, top_score)) return FM_OK;
+    fm_batch* bu = host_batch(ctx);
+    if (!ctx->host_batch2) ctx->host_batch2.reset(new fm_batch());
+    fm_batch* bc = ctx->host_batch2.get();
+    upload_batch(ctx, contexts, bu, false);
+    upload_batch(ctx, candidates, bc, false);
+    return rank_impl(ctx, bu->dev, bc->dev, n_top, lo, hi, top_index, top_score);
+  });
+}
+
+int fm_rank_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t n_top, double lo, double hi,
+                  int32_t* top_index, double* top_score) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
+    FM_REQUIRE(contexts->owner == ctx && candidates->owner == ctx, "batch belongs to another context");
+    FM_REQUIRE(!ctx->group && !contexts->grp && !candidates->grp,
+               "fm_rank_batch needs both row sets whole on one device: a multi-GPU context's batches are cut over its "
+               "ranks (fm_rank_candidates takes host rows)");
+    FM_REQUIRE(contexts->split_rows.empty() && candidates->split_rows.empty(),
+               "a dataset made by fm_batch_create_splits is ranked through its split views");
+    if (!rank_check(ctx, contexts->dev.n_rows, candidates->dev.n_rows, n_top, top_index, top_score)) return FM_OK;
+    wait_built(contexts, ctx->stream);
+    wait_built(candidates, ctx->stream);
+    return rank_impl(ctx, contexts->dev, candidates->dev, n_top, lo, hi, top_index, top_score);
+  });
+}
+
 int fm_init_from_batch(fm_ctx* ctx, fm_batch* b, int64_t* n_present) {
   return guarded(ctx, [&]() -> int {
     FM_REQUIRE(b != nullptr && b->owner == ctx, "batch belongs to another context");

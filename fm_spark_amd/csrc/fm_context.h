@@ -184,6 +184,8 @@ struct fm_ctx {
   Pinned pinned;
   Pinned up_pin;                         // host CSR upload staging (upload_batch)
   std::unique_ptr<fm_batch> host_batch;  // reused by fm_predict / fm_loss_grad
+  std::unique_ptr<fm_batch> host_batch2;  // fm_rank_candidates' second row set (the candidates)
+  RankWork rank;                         // fm_rank_* scratch (fm_rank.hip)
   HostSlot hslot[2];                     // fm_step's double-buffered uploads
   int hnext = 0;
   hipStream_t copy_stream = nullptr;     // their host -> device copies
@@ -326,7 +328,8 @@ struct fm_ctx {
                       &route_sort.keys_a, &route_sort.keys_b, &route_sort.vals_a, &route_sort.vals_b,
                       &route_sort.counts, &route_sort.digit_tot,
                       &sh_okey, &sh_mask, &sh_tcnt, &sh_tot, &sh_pay, &sh_skey, &sh_ent2, &repl_cnt,
-                      &split_work.cnt, &split_work.off};
+                      &split_work.cnt, &split_work.off, &rank.sum_u, &rank.sum_c, &rank.cnt_u, &rank.cnt_c,
+                      &rank.bias_u, &rank.bias_c, &rank.lkey, &rank.lidx, &rank.out_idx, &rank.out_score};
     for (auto* b : bufs) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }

@@ -18,6 +18,9 @@
 // MODE kTrainFused: kTrain, and every row whose feature has exactly one entry in the batch (a
 // singleton: 92 % of a c3 batch's distinct rows) is updated here, by the sample that holds that
 // entry, instead of by the segmented update (see "Singleton rows" in fm_device.h).
+// MODE kSummary: a row's fp64 summary for fm_rank_* (fm_rank.hip): kPredict's entry handling (ids
+// outside the table dropped, x from the batch's stream, the learned entries counted) with kPartial64's
+// stores: S as [row][kp] doubles, {sum v^2 x^2, sum w*x} as a double2 and the count per row.
 // (the modes are FwdMode, fm_internal.h; FwdOut::mode names the one a launch runs)
 #include <atomic>
 
@@ -269,6 +272,7 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
                double2* __restrict__ loss_part, FwdOut xo) {
   constexpr bool PARTIAL = MODE == kPartial || MODE == kPartial64;
   constexpr bool STASH = MODE == kTrainFused;
+  constexpr bool SUMMARY = MODE == kSummary;  // predict's entries, the fp64 partial pass's stores
   using Stash = SingletonStash<GS, TEAM, STASH>;
   constexpr int RPP = TEAM / GS;  // entries per pass
   constexpr int TPB = kBlock / TEAM;
@@ -344,7 +348,7 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
           // the batch's x stream (4 B per entry); the partial pass's entries carry x themselves
           const float xl = PARTIAL ? __uint_as_float(ent[ec].y) : xs[ec];
           id[j] = ok[j] ? idl : 0u;
-          if (MODE == kPredict) ok[j] = ok[j] && id[j] < (uint64_t)T.rows;
+          if (MODE == kPredict || SUMMARY) ok[j] = ok[j] && id[j] < (uint64_t)T.rows;
           x[j] = ok[j] ? xl : 0.f;
         }
       }
@@ -370,7 +374,7 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         float w;
-        if ((MODE == kPredict || PARTIAL) && g == 0 && h[j].t >= 0) ++npres;
+        if ((MODE == kPredict || PARTIAL || SUMMARY) && g == 0 && h[j].t >= 0) ++npres;
         current_row(h[j], v[j], w, cumE);
         if (MODE == kLossGrad && xo.fill_sd > 0.0 && ok[j] && h[j].t < 0) fill_row(xo, T.k, g, eb + j * RPP, v[j], w);
         const double xd = x[j];
@@ -394,11 +398,11 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
     for (int o = 1; o < TEAM; o <<= 1) {
       vv += __shfl_xor(vv, o);
       wx += __shfl_xor(wx, o);
-      if (MODE == kPredict || PARTIAL) npres += __shfl_xor(npres, o);
+      if (MODE == kPredict || PARTIAL || SUMMARY) npres += __shfl_xor(npres, o);
     }
     // ---- the mode's epilogue
-    if (PARTIAL) {  // vectors [pair][kp] in S_out, scalars {sum v^2 x^2, sum w x} in yl_out
-      if constexpr (MODE == kPartial64) {  // the fp64 wire: two 16-B stores per lane, one for the scalars
+    if (PARTIAL || SUMMARY) {  // vectors [pair][kp] in S_out, scalars {sum v^2 x^2, sum w x} in yl_out
+      if constexpr (MODE == kPartial64 || SUMMARY) {  // the fp64 wire: two 16-B stores per lane, one for the scalars
         if (rs == 0 && qok) {
           double2* so = reinterpret_cast<double2*>(reinterpret_cast<double*>(S_out) + s * sstr + g * 4);
           so[0] = make_double2(a0, a1);
@@ -487,6 +491,10 @@ void launch_fwd_m(const TableView& T, const BatchDev& b, StepWork& w, const Step
     yl_out = MODE == kPartial64 ? reinterpret_cast<float2*>(reinterpret_cast<double*>(partial_out) + b.n_rows * T.kp)
                                 : reinterpret_cast<float2*>(partial_out + b.n_rows * T.kp);
   }
+  if (MODE == kSummary) {  // the fp64 wire's layout in xo.summary
+    S_out = reinterpret_cast<float*>(xo.summary);
+    yl_out = reinterpret_cast<float2*>(xo.summary + b.n_rows * T.kp);
+  }
   if (TRAIN) {
     w.loss_part.ensure(sizeof(double2) * blocks);
     S_out = w.S.as<float>();
@@ -515,6 +523,11 @@ void launch_fwd_t(const TableView& T, const BatchDev& b, StepWork& w, const Step
       break;
     case kPartial: return launch_fwd_m<GS, TEAM, kPartial, U>(T, b, w, p, st, nblk, partial_out, xo);
     case kPredict: return launch_fwd_m<GS, TEAM, kPredict, U>(T, b, w, p, st, nblk, partial_out, xo);
+    case kSummary:
+      // (predict's team shapes only: the partial pass's narrow teams never summarise)
+      if constexpr (TEAM >= kFwdTeam) return launch_fwd_m<GS, TEAM, kSummary, U>(T, b, w, p, st, nblk, partial_out, xo);
+      else FM_REQUIRE(false, "the row summary takes predict's team shapes");
+      break;
     case kLossGrad: return launch_fwd_m<GS, TEAM, kLossGrad, U>(T, b, w, p, st, nblk, partial_out, xo);
     case kTrainFused:
       if constexpr (GS <= 4 && TEAM >= 16) return launch_fwd_m<GS, TEAM, kTrainFused, kFuseU>(T, b, w, p, st, nblk, partial_out, xo);
@@ -590,6 +603,21 @@ void launch_predict(const TableView& T, const BatchDev& b, double cumE, double w
   xo.lo = lo;
   xo.hi = hi;
   xo.pred = pred;
+  StepWork unused;
+  int64_t nblk = 0;
+  launch_forward(T, b, unused, p, st, &nblk, nullptr, &xo);
+}
+
+void launch_summary(const TableView& T, const BatchDev& b, double cumE, double* summary, uint32_t* present,
+                    hipStream_t st) {
+  FM_REQUIRE(T.shard_count == 1, "fm_rank needs the whole table (shard_count == 1)");
+  if (b.n_rows <= 0) return;
+  StepParams p{};
+  p.cumE = cumE;
+  FwdOut xo{};
+  xo.mode = kSummary;
+  xo.summary = summary;
+  xo.pcount = present;
   StepWork unused;
   int64_t nblk = 0;
   launch_forward(T, b, unused, p, st, &nblk, nullptr, &xo);

@@ -183,8 +183,9 @@ struct StepParams {
 // k_forward's modes (fm_forward.hip): the step's forward, plain or with the singleton rows' updates
 // fused in; the sharded owner's partial pass with the fp32 or the fp64 wire; predict (clamp bounds,
 // fp64 score per sample into pred); calcLossGrad (fp64 pred / loss / dw per entry, dv [entries][k],
-// the absent-id flag)
-enum FwdMode : int { kTrain = 0, kPartial = 1, kPredict = 2, kLossGrad = 3, kTrainFused = 4, kPartial64 = 5 };
+// the absent-id flag); a row's fp64 summary for ranking (predict's entry handling, the fp64 partial
+// pass's stores: S, {sum v^2 x^2, sum w x} and the learned-entry count per row)
+enum FwdMode : int { kTrain = 0, kPartial = 1, kPredict = 2, kLossGrad = 3, kTrainFused = 4, kPartial64 = 5, kSummary = 6 };
 struct FwdOut {
   int mode = kTrain;  // a FwdMode; launch_forward sets the partial modes itself (partial_out / partial_wide)
   double lo = 0.0, hi = 0.0;
@@ -193,7 +194,8 @@ struct FwdOut {
   double* dw = nullptr;
   double* dv = nullptr;
   int32_t* absent = nullptr;
-  uint32_t* pcount = nullptr;  // partial pass (sharded predict): present rows per pair
+  uint32_t* pcount = nullptr;  // partial pass (sharded predict): present rows per pair; kSummary: learned entries per row
+  double* summary = nullptr;   // kSummary: [rows][kp] doubles sum v*x, then [rows] double2 {sum v^2 x^2, sum w*x}
   // partial pass over chunk ch_c of ch_C (ch_C > 1): of every source r < ch_R, the pairs
   // [off[r] + P_r ch_c / ch_C, off[r] + P_r (ch_c + 1) / ch_C), P_r = off[r + 1] - off[r] (device off)
   const int64_t* ch_off = nullptr;
@@ -280,6 +282,10 @@ void launch_gather_rows(const TableView& T, const int32_t* ids, int64_t n, doubl
 void launch_table_reset(const TableView& T, hipStream_t st);
 void launch_predict(const TableView& T, const BatchDev& b, double cumE, double w0, double lo, double hi,
                     double* pred, hipStream_t st);
+// fm_rank_*: every row's summary (FwdOut::summary's layout) and its count of learned entries, with
+// predict's team shapes; ids outside the table or absent from the model contribute nothing
+void launch_summary(const TableView& T, const BatchDev& b, double cumE, double* summary, uint32_t* present,
+                    hipStream_t st);
 void launch_init_entries(const TableView& T, const uint32_t* col, int64_t n, uint64_t seed, double sd,
                          int32_t epoch, double cumE, hipStream_t st);
 void launch_loss_grad(const TableView& T, const BatchDev& b, double cumE, double w0, double* pred,
@@ -302,6 +308,32 @@ void launch_explode(const int64_t* row_ptr_in, const double* label_in, const int
 void launch_layout_splits(const int64_t* src_row_ptr, const double* src_label, const int32_t* xoff, const uint32_t* col_in,
                           const float* x_in, const int64_t* order, const int64_t* row_ptr_in, const int64_t* split_rows,
                           int32_t n_splits, int64_t B, BatchDev& dst, int64_t* split_rp, hipStream_t st);
+
+// ---------------------------------------------------------------- ranking (fm_rank.hip)
+// Scratch of fm_rank_candidates / fm_rank_batch, kept with the context (grown, never shrunk).
+struct RankWork {
+  DevBuf sum_u, sum_c;    // the two row sets' summaries (FwdOut::summary's layout)
+  DevBuf cnt_u, cnt_c;    // uint32 learned entries per row
+  DevBuf bias_u, bias_c;  // double a_r = L + (|S|^2 - Q) / 2 per row
+  DevBuf lkey, lidx;      // the context tile's split lists: uint64 keys, uint32 candidate rows
+  DevBuf out_idx, out_score;  // int32 / double [U][n_top]
+};
+// candidate splits of a call of U contexts (whole chunks each; fewer as the contexts alone fill the
+// chip) and the contexts one pass of the score kernel takes (the list budget)
+int rank_splits(int64_t C, int64_t U);
+int64_t rank_ctx_tile(int splits, int n_top);
+// a_r for n rows of a summary buffer
+void launch_rank_bias(const double* summary, int64_t n, int kp, double* bias, hipStream_t st);
+// contexts [0, Ut) of the given arrays against all C candidates: per (context, split) the split's
+// best n_top in order into lkey / lidx [Ut][splits][n_top]
+void launch_rank_score(const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut,
+                       const double* sum_c, const double* bias_c, const uint32_t* cnt_c, int64_t C, int kp, int splits,
+                       int n_top, double w0, uint64_t* lkey, uint32_t* lidx, hipStream_t st);
+// the splits' lists merged in split order; the first n_top per context into out_idx / out_score
+// (w0 for a pair without a learned entry, else the key's value clamped to [lo, hi])
+void launch_rank_merge(const uint64_t* lkey, const uint32_t* lidx, int64_t Ut, int splits, int n_top,
+                       const uint32_t* cnt_u, const uint32_t* cnt_c, double w0, double lo, double hi, int32_t* out_idx,
+                       double* out_score, hipStream_t st);
 
 // fm_batch_from_rows: dst row s = src row rows[s] (device rows[B]); row_ptr_in[B + 1] (device) is the
 // result's row_ptr, computed by the host from the source's

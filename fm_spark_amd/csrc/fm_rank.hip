@@ -1,0 +1,250 @@
+// Top-N candidate ranking for gfx950 (MI355X): fm_rank_candidates / fm_rank_batch (include/fm_hip.h).
+//
+// The FM score of a context row u and a candidate row c, their entries taken together, separates:
+//   yhat(u, c) = w0 + a_u + b_c + <S_u, S_c>,   a_r = b_r = L_r + (|S_r|^2 - Q_r) / 2
+// with the row summaries S_r = sum v x, Q_r = sum |v|^2 x^2, L_r = sum w x that k_forward's kSummary
+// mode writes in fp64 (fm_forward.hip).  Ranking is then three passes, none of which reads the table
+// after the summaries:
+//   k_rank_bias   a_r of every row, one fixed-order sum over f = 0 .. kp - 1;
+//   k_rank_score  a block owns one context and one split of the candidates (a run of whole chunks of
+//                 kRankChunk rows).  Per chunk it forms the keys -- yhat as an order-preserving 64-bit
+//                 integer, the candidate row as the tie-break -- sorts the chunk in LDS (bitonic,
+//                 descending) and folds its first W into the split's running best W, W the power of
+//                 two that holds n_top: with A and B sorted descending, max(A[i], B[W - 1 - i]) holds
+//                 the best W of both as a bitonic sequence, which one bitonic merge sorts.  The
+//                 split's first n_top leave as its list;
+//   k_rank_merge  a block per context folds the splits' lists in split order the same way and writes
+//                 the first n_top: the candidate row, and the key's value clamped (w0 unclamped for a
+//                 pair without a learned entry).
+// (key, row) is a total order over a context's candidates (rows are distinct), so the best n_top and
+// their order do not depend on the chunking, the splits, the context tile or the other contexts of
+// the call; a score is ((w0 + a_u) + b_c) + dot with the dot product summed by one thread in the
+// order f = 0 .. kp - 1, so equal rows score bit for bit alike wherever they sit.  Nothing on the
+// path is rounded to fp32.
+//
+// Scratch: the summaries and biases, (U + C) (kp + 3) doubles and a count per row, and the split
+// lists [contexts of a pass][splits][n_top] of 12 bytes, held under kRankListBudget by passing over
+// the contexts in tiles (rank_ctx_tile); at most kRankMaxSplits splits, so a context's lists never
+// exceed kRankMaxSplits * kRankChunk * 12 B = 768 KiB.  Nothing grows with U * C.  A call of many
+// contexts takes fewer splits (rank_splits: about kRankTargetBlocks blocks in all), so its blocks
+// stream several chunks each and the merge folds fewer lists.
+#include <algorithm>
+
+#include "fm_device.h"
+
+namespace fmhip {
+
+namespace {
+
+constexpr int kRankChunk = 1024;      // candidates a block scores and sorts at a time (= FM_RANK_MAX_TOP)
+constexpr int kRankMaxSplits = 64;    // blocks that share one context's candidates, at most
+constexpr int kRankTargetBlocks = 512;  // ... and no more than fill the chip: two blocks per CU over all contexts
+constexpr int64_t kRankListBudget = 4 << 20;  // bytes of split lists in flight (one pass over a context tile)
+constexpr int kRankPer = kRankChunk / kBlock;  // chunk elements per thread
+static_assert(kRankChunk == FM_RANK_MAX_TOP, "a split's running list holds the largest n_top");
+static_assert(kRankChunk % (2 * kBlock) == 0, "the compare-exchange loop takes whole rounds");
+
+constexpr uint64_t kWorstKey = 0;           // below every finite score's key
+constexpr uint32_t kNoRow = 0xFFFFFFFFu;    // the padding's row: after every candidate row (C < 2^31)
+
+// yhat -> an integer whose unsigned order is yhat's (both signs; -0 was folded into +0 before)
+__device__ __forceinline__ uint64_t key_of(double y) {
+  const uint64_t b = (uint64_t)__double_as_longlong(y);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double value_of(uint64_t k) {
+  const uint64_t b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+  return __longlong_as_double((long long)b);
+}
+// (ka, ia) ranks before (kb, ib): the larger key, then the smaller row
+__device__ __forceinline__ bool before(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
+  return ka > kb || (ka == kb && ia < ib);
+}
+
+// One compare-exchange stage over n elements in LDS (n a power of two <= kRankChunk): partner
+// distance j, blocks of kk sorted descending where (i & kk) == 0, ascending elsewhere (kk = n: all
+// descending).
+__device__ __forceinline__ void bitonic_stage(uint64_t* key, uint32_t* row, int j, int kk, int n) {
+  for (int t = threadIdx.x; t < n / 2; t += kBlock) {
+    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+    const int l = i | j;
+    const uint64_t ki = key[i], kl = key[l];
+    const uint32_t ri = row[i], rl = row[l];
+    const bool desc = (i & kk) == 0;
+    if (before(kl, rl, ki, ri) == desc) {
+      key[i] = kl; row[i] = rl;
+      key[l] = ki; row[l] = ri;
+    }
+  }
+  __syncthreads();
+}
+// a chunk in any order -> descending (the caller has synchronised after writing key / row)
+__device__ __forceinline__ void bitonic_sort(uint64_t* key, uint32_t* row) {
+  for (int kk = 2; kk <= kRankChunk; kk <<= 1)
+    for (int j = kk >> 1; j > 0; j >>= 1) bitonic_stage(key, row, j, kk, kRankChunk);
+}
+// the first W of best[] and of add[], both descending (W a power of two >= n_top) -> the first W of
+// best[] = the best W of the two, descending
+__device__ __forceinline__ void fold_sorted(uint64_t* bkey, uint32_t* brow, const uint64_t* akey, const uint32_t* arow,
+                                            int W) {
+  for (int i = threadIdx.x; i < W; i += kBlock) {
+    const uint64_t ka = akey[W - 1 - i];
+    const uint32_t ra = arow[W - 1 - i];
+    if (before(ka, ra, bkey[i], brow[i])) {
+      bkey[i] = ka;
+      brow[i] = ra;
+    }
+  }
+  __syncthreads();
+  for (int j = W >> 1; j > 0; j >>= 1) bitonic_stage(bkey, brow, j, W, W);
+}
+// the list width of a call: the power of two that holds n_top
+__device__ __forceinline__ int list_width(int n_top) {
+  int W = 1;
+  while (W < n_top) W <<= 1;
+  return W;
+}
+
+__global__ __launch_bounds__(kBlock) void k_rank_bias(const double* __restrict__ summary, int64_t n, int kp,
+                                                      double* __restrict__ bias) {
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r >= n) return;
+  const double2* S = reinterpret_cast<const double2*>(summary + r * kp);
+  double ss = 0.0;
+  for (int f = 0; f < kp / 2; ++f) {
+    const double2 s = S[f];
+    ss = fma(s.x, s.x, ss);
+    ss = fma(s.y, s.y, ss);
+  }
+  const double2 ql = reinterpret_cast<const double2*>(summary + n * kp)[r];  // {Q, L}
+  bias[r] = ql.y + 0.5 * (ss - ql.x);
+}
+
+// block b: context b / splits, split b % splits = the chunks [nch s / splits, nch (s + 1) / splits)
+__global__ __launch_bounds__(kBlock) void k_rank_score(const double* __restrict__ sum_u, const double* __restrict__ bias_u,
+                                                       const uint32_t* __restrict__ cnt_u, const double* __restrict__ sum_c,
+                                                       const double* __restrict__ bias_c, const uint32_t* __restrict__ cnt_c,
+                                                       int64_t C, int kp, int splits, int n_top, double w0,
+                                                       uint64_t* __restrict__ lkey, uint32_t* __restrict__ lidx) {
+  __shared__ double su[256];  // the context's S (kp <= 256)
+  __shared__ uint64_t bkey[kRankChunk], ckey[kRankChunk];
+  __shared__ uint32_t brow[kRankChunk], crow[kRankChunk];
+  const int tid = threadIdx.x;
+  const int64_t u = blockIdx.x / splits;
+  const int s = blockIdx.x % splits;
+  const int64_t nch = (C + kRankChunk - 1) / kRankChunk;
+  const int64_t ch0 = nch * s / splits, ch1 = nch * (s + 1) / splits;
+  for (int f = tid; f < kp; f += kBlock) su[f] = sum_u[u * kp + f];
+  const int W = list_width(n_top);
+  const double base = w0 + bias_u[u];
+  const bool learned_u = cnt_u[u] != 0;
+  __syncthreads();
+  for (int64_t ch = ch0; ch < ch1; ++ch) {
+    uint64_t* key = ch == ch0 ? bkey : ckey;  // the split's first chunk is its running list
+    uint32_t* row = ch == ch0 ? brow : crow;
+#pragma unroll
+    for (int j = 0; j < kRankPer; ++j) {
+      const int i = tid + j * kBlock;
+      const int64_t c = ch * kRankChunk + i;
+      uint64_t k = kWorstKey;
+      uint32_t r = kNoRow;
+      if (c < C) {
+        const double2* Sc = reinterpret_cast<const double2*>(sum_c + c * kp);
+        double dot = 0.0;
+        for (int f = 0; f < kp / 2; ++f) {
+          const double2 v = Sc[f];
+          dot = fma(su[2 * f], v.x, dot);
+          dot = fma(su[2 * f + 1], v.y, dot);
+        }
+        double y = (base + bias_c[c]) + dot;
+        if (!learned_u && cnt_c[c] == 0) y = w0;  // no learned entry on either side ranks at w0
+        k = key_of(y + 0.0);
+        r = (uint32_t)c;
+      }
+      key[i] = k;
+      row[i] = r;
+    }
+    __syncthreads();
+    bitonic_sort(key, row);
+    if (ch != ch0) fold_sorted(bkey, brow, ckey, crow, W);
+  }
+  const int64_t o = ((int64_t)u * splits + s) * n_top;
+  for (int i = tid; i < n_top; i += kBlock) {
+    lkey[o + i] = bkey[i];
+    lidx[o + i] = brow[i];
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_rank_merge(const uint64_t* __restrict__ lkey, const uint32_t* __restrict__ lidx,
+                                                       int splits, int n_top, const uint32_t* __restrict__ cnt_u,
+                                                       const uint32_t* __restrict__ cnt_c, double w0, double lo, double hi,
+                                                       int32_t* __restrict__ out_idx, double* __restrict__ out_score) {
+  __shared__ uint64_t bkey[kRankChunk], ckey[kRankChunk];
+  __shared__ uint32_t brow[kRankChunk], crow[kRankChunk];
+  const int tid = threadIdx.x;
+  const int64_t u = blockIdx.x;
+  const int W = list_width(n_top);
+  for (int s = 0; s < splits; ++s) {
+    uint64_t* key = s == 0 ? bkey : ckey;
+    uint32_t* row = s == 0 ? brow : crow;
+    const int64_t o = (u * splits + s) * n_top;
+    for (int i = tid; i < W; i += kBlock) {  // a list is descending; the padding follows it
+      key[i] = i < n_top ? lkey[o + i] : kWorstKey;
+      row[i] = i < n_top ? lidx[o + i] : kNoRow;
+    }
+    __syncthreads();
+    if (s != 0) fold_sorted(bkey, brow, ckey, crow, W);
+  }
+  const bool learned_u = cnt_u[u] != 0;
+  for (int i = tid; i < n_top; i += kBlock) {
+    const uint32_t c = brow[i];
+    double y = w0;  // a pair without a learned entry: globalBias, unclamped (Model.scala:86)
+    if (c != kNoRow && (learned_u || cnt_c[c] != 0)) y = fmin(fmax(value_of(bkey[i]), lo), hi);
+    out_idx[u * n_top + i] = (int32_t)c;
+    out_score[u * n_top + i] = y;
+  }
+}
+
+}  // namespace
+
+int rank_splits(int64_t C, int64_t U) {
+  const int64_t nch = (C + kRankChunk - 1) / kRankChunk;
+  const int64_t want = (kRankTargetBlocks + (U < 1 ? 1 : U) - 1) / (U < 1 ? 1 : U);
+  const int64_t s = std::min<int64_t>(std::min<int64_t>(nch, kRankMaxSplits), want);
+  return (int)(s < 1 ? 1 : s);
+}
+
+int64_t rank_ctx_tile(int splits, int n_top) {
+  const int64_t per_ctx = (int64_t)splits * n_top * (int64_t)(sizeof(uint64_t) + sizeof(uint32_t));
+  const int64_t t = kRankListBudget / per_ctx;
+  return t < 1 ? 1 : t;
+}
+
+void launch_rank_bias(const double* summary, int64_t n, int kp, double* bias, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_rank_bias, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, summary, n, kp, bias);
+  FM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_rank_score(const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut, const double* sum_c,
+                       const double* bias_c, const uint32_t* cnt_c, int64_t C, int kp, int splits, int n_top, double w0,
+                       uint64_t* lkey, uint32_t* lidx, hipStream_t st) {
+  FM_REQUIRE(kp <= 256, "dimFactorization > 256 is not supported");
+  FM_REQUIRE(Ut >= 1 && C >= 1 && n_top >= 1 && n_top <= kRankChunk && n_top <= C, "rank: bad shape");
+  FM_REQUIRE(splits >= 1 && splits <= (C + kRankChunk - 1) / kRankChunk, "rank: every split needs a chunk");
+  FM_REQUIRE(Ut * splits < (int64_t(1) << 31), "rank: context tile too large");
+  hipLaunchKernelGGL(k_rank_score, dim3((unsigned)(Ut * splits)), dim3(kBlock), 0, st, sum_u, bias_u, cnt_u, sum_c, bias_c,
+                     cnt_c, C, kp, splits, n_top, w0, lkey, lidx);
+  FM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_rank_merge(const uint64_t* lkey, const uint32_t* lidx, int64_t Ut, int splits, int n_top, const uint32_t* cnt_u,
+                       const uint32_t* cnt_c, double w0, double lo, double hi, int32_t* out_idx, double* out_score,
+                       hipStream_t st) {
+  FM_REQUIRE(Ut >= 1 && Ut < (int64_t(1) << 31) && splits >= 1 && n_top >= 1 && n_top <= kRankChunk, "rank: bad shape");
+  hipLaunchKernelGGL(k_rank_merge, dim3((unsigned)Ut), dim3(kBlock), 0, st, lkey, lidx, splits, n_top, cnt_u, cnt_c, w0, lo,
+                     hi, out_idx, out_score);
+  FM_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace fmhip

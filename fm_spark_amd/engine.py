@@ -319,6 +319,29 @@ class FMContext:
                                            N.ptr(out, C.c_double)), "fm_predict_batch")
         return out[: b.n_rows]
 
+    def rank(self, contexts: N.CSRHost, candidates: N.CSRHost, n_top: int, min_label: float, max_label: float):
+        """For every context row the n_top candidate rows with the largest FM score of the two rows'
+        entries together (fm_rank_candidates): (index [U, n_top] int32, score [U, n_top] float64), by
+        the unclamped score descending, ties by ascending candidate row."""
+        return self._rank(self._lib.fm_rank_candidates, "fm_rank_candidates", C.byref(contexts.c),
+                          C.byref(candidates.c), contexts.n_rows, n_top, min_label, max_label)
+
+    def rank_batch(self, contexts: DeviceBatch, candidates: DeviceBatch, n_top: int, min_label: float,
+                   max_label: float):
+        """rank over device-resident batches of this context (fm_rank_batch)."""
+        return self._rank(self._lib.fm_rank_batch, "fm_rank_batch", contexts.handle, candidates.handle,
+                          contexts.n_rows, n_top, min_label, max_label)
+
+    def _rank(self, fn, what, contexts, candidates, n_ctx, n_top, min_label, max_label):
+        n_top = int(n_top)
+        n = max(n_ctx * max(n_top, 0), 1)
+        idx = np.zeros(n, dtype=np.int32)
+        score = np.zeros(n)
+        N.check(fn(self.handle, contexts, candidates, n_top, float(min_label), float(max_label),
+                   N.ptr(idx, C.c_int32), N.ptr(score, C.c_double)), what)
+        m = n_ctx * n_top
+        return idx[:m].reshape(n_ctx, n_top), score[:m].reshape(n_ctx, n_top)
+
     def loss_grad(self, csr: N.CSRHost, initial_sd: float | None = None, seed: int = 0):
         """calcLossGrad per entry (pred, loss, deltaWi, deltaVi).  initial_sd: ids the model lacks
         get their own N(0, initial_sd^2) draws per entry (fm_calc_loss_grad, keyed by seed); None:

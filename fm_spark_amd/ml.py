@@ -231,6 +231,30 @@ class FactorizationMachinesModel:
         pred = self._ctx.predict(csr, self.getMinLabel(), self.getMaxLabel())
         return dataset.with_column(self._params["predictionCol"], [float(p) for p in pred])
 
+    def recommend(self, contexts: DataFrame, candidates: DataFrame, numItems: int) -> DataFrame:
+        """The numItems best rows of `candidates` for every row of `contexts` (the shape of
+        ALSModel.recommendForUserSubset): both frames carry featuresCol; the result is `contexts` plus
+        a ``recommendations`` column, per row a list of (candidate_row, prediction) in rank order.  A
+        pair's prediction is transform's for the row made of the two rows' entries, clamped to
+        [minLabel, maxLabel]; the order is that of the unclamped score, ties by candidate row
+        (fm_rank_candidates, include/fm_hip.h).  numItems outside [1, min(len(candidates), 1024)]
+        raises ValueError; a model whose table is row-sharded refuses with FMError, as calcLossGrad."""
+        fcol = self._params["featuresCol"]
+        n_cand = candidates.count()
+        if isinstance(numItems, bool) or not isinstance(numItems, (int, np.integer)):
+            raise ValueError("numItems must be an integer")
+        if not 1 <= int(numItems) <= min(n_cand, N.FM_RANK_MAX_TOP):
+            raise ValueError(f"numItems must be in [1, min(len(candidates), {N.FM_RANK_MAX_TOP})], got {numItems}")
+        _check_schema(contexts, fcol, None)
+        _check_schema(candidates, fcol, None)
+        rows = []
+        for df in (contexts, candidates):
+            rp, col, val = _explode(df[fcol])
+            rows.append(N.CSRHost(rp, col, val, np.zeros(df.count())))
+        idx, score = self._ctx.rank(rows[0], rows[1], int(numItems), self.getMinLabel(), self.getMaxLabel())
+        recs = [[(int(i), float(s)) for i, s in zip(ri, rs)] for ri, rs in zip(idx, score)]
+        return contexts.with_column("recommendations", recs)
+
     def calcLossGrad(self, dfSampleIndexed: DataFrame, initialSd: float, seed: int = 0) -> DataFrame:
         """Model.scala:135-234: one row per active entry with columns label, sampleId,
         featureId, prediction, loss, deltaWi, deltaVi (deltaVi before the (pred - label) factor).

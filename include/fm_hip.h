@@ -170,7 +170,9 @@ int fm_sync(fm_ctx* ctx);
  * device-resident batch of at most max_rows x max_nnz allocates.  What belongs to a batch is sized
  * when the batch is first seen, not here: a batch's own prepared view, a multi-GPU context's
  * per-batch routing state and wire buffers, and fm_step's two upload slots, each of which grows to
- * the largest host batch it has held (steady after every batch size has passed through both). */
+ * the largest host batch it has held (steady after every batch size has passed through both).  The
+ * scratch of fm_rank_candidates / fm_rank_batch is not covered either: it is sized by the two row
+ * sets and n_top at the call, and kept. */
 int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz);
 
 /* ---- tables (C9: Strength / FactorizedInteraction, Model.scala:275-289) ------------ */
@@ -305,6 +307,45 @@ int fm_predict(fm_ctx* ctx, const fm_csr* csr, double min_label, double max_labe
 /* The same on a device-resident batch (fm_batch_create): transform over a cached DataFrame
  * without re-uploading it.  pred is a host buffer of fm_batch_rows(batch) doubles. */
 int fm_predict_batch(fm_ctx* ctx, fm_batch* batch, double min_label, double max_label, double* pred);
+/* Top-N ranking, the serving side of transform (the shape of ALSModel.recommendForUserSubset): for
+ * every row of `contexts` (a user and their history, a page view) the n_top rows of `candidates`
+ * (movies, ads) with the largest FM score of the two rows' entries taken together, without
+ * materialising the U x C concatenated rows.  top_index[u * n_top + j] = the candidate row ranked
+ * j-th for context u, top_score[u * n_top + j] = its score (host buffers of U * n_top).
+ *   score : fm_predict's for the row made of the two entry lists, one after the other: ids >=
+ *           num_features or absent from the model are dropped (Model.scala:103-112), the lazy L1
+ *           shrink is caught up on read, a pair with no learned entry on either side scores w0
+ *           unclamped (Model.scala:86), every other pair clamp(yhat, min_label, max_label)
+ *           (:129-132).  An id that occurs in both rows counts as two entries (the library does not
+ *           check that the two rows are disjoint).  Labels are not read.
+ *   order : by the unclamped yhat, descending (a pair with no learned entry ranks at w0); equal keys
+ *           by ascending candidate row.  So the result is a function of the two row sets and the
+ *           table alone: not of the library's tiling, of U, or of the other contexts in the call.
+ *           top_score holds the clamped value, which may tie where the order does not.  The order
+ *           of NaN keys is unspecified.
+ *   arithmetic : yhat(u, c) = w0 + a_u + b_c + <S_u, S_c> with S_r = sum v x, a_r = b_r = sum w x +
+ *           (|S_r|^2 - sum |v|^2 x^2) / 2 per row: fp64 sums of the fp32 table values, the pair term
+ *           an fp64 dot product in a fixed factor order; nothing on the path is rounded to fp32.
+ *   arguments : 1 <= n_top <= min(C, FM_RANK_MAX_TOP), else FM_ERR_ARG; C = 0 with U >= 1 is
+ *           FM_ERR_ARG; U = 0 is FM_OK with nothing written; C < 2^31; null pointers are FM_ERR_ARG;
+ *           the CSRs are validated as fm_predict validates its own.
+ *   contexts : a single table with shard_count == 1; a replicated multi-GPU context is answered by
+ *           its first rank (fm_rank_candidates only: its batches are cut over the ranks, so
+ *           fm_rank_batch is FM_ERR_ARG there).  A row-sharded table (FM_PARALLEL_SHARDED, or
+ *           shard_count > 1) is FM_ERR_ARG: left for later, and natural there -- the per-owner row
+ *           summaries are additive, and the fp64 wire of the sharded step (FM_WIRE_FP64) already
+ *           carries exactly these words.
+ * Synchronous, on the context's main stream behind every queued step; the table, the epoch and the
+ * loss history are unchanged.  The scratch is kept with the context and grows to the largest call
+ * (two equal calls leave fm_device_bytes_live / fm_device_allocs_live equal). */
+#define FM_RANK_MAX_TOP 1024
+int fm_rank_candidates(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, int32_t n_top,
+                       double min_label, double max_label, int32_t* top_index, double* top_score);
+/* The same on device-resident batches of this context (fm_batch_create / fm_batch_from_rows /
+ * fm_batch_split_view results; a split dataset itself is FM_ERR_ARG, as for fm_step_batch); waits
+ * for a refilled batch's gather. */
+int fm_rank_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t n_top,
+                  double min_label, double max_label, int32_t* top_index, double* top_score);
 /* calcLossGrad (Model.scala:135-234), per active entry e in CSR order:
  * pred[e] = yhat of its row (unclamped), loss[e] = (yhat - y)^2, delta_w[e] = x,
  * delta_v[e*k + f] = vfxiSum_f * x - (v_f * x) * x.  Any output may be NULL.
