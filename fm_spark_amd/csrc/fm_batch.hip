@@ -206,21 +206,19 @@ __global__ __launch_bounds__(kBlock) void k_split_rebase(const int64_t* __restri
     for (int64_t e = e0 + tl; e < e1; e += T) ent[e].x = (uint32_t)(s - r0);
   }
 }
-void launch_explode(const int64_t* row_ptr_in, const double* label_in, const int32_t* xoff, const uint32_t* col_in,
-                    const float* x_in, int64_t B, int64_t N, int64_t* row_ptr, double* label, uint32_t* col, uint2* ent,
-                    float* xs, hipStream_t st) {
+void launch_explode(const CsrImage& in, int64_t B, int64_t N, BatchDev& dst, hipStream_t st) {
   (void)N;
   hipLaunchKernelGGL(k_explode, dim3(grid_for(std::max<int64_t>(B, 1) * 16, kBlock, 256 * 8)), dim3(kBlock), 0, st,
-                     row_ptr_in, label_in, xoff, col_in, x_in, B, row_ptr, label, col, ent, xs);
+                     in.row_ptr, in.label, in.xoff, in.col, in.x, B, dst.row_ptr.as<int64_t>(), dst.label.as<double>(),
+                     dst.col.as<uint32_t>(), dst.ent.as<uint2>(), dst.xs.as<float>());
   FM_HIP_CHECK(hipGetLastError());
 }
 
-void launch_layout_splits(const int64_t* src_row_ptr, const double* src_label, const int32_t* xoff, const uint32_t* col_in,
-                          const float* x_in, const int64_t* order, const int64_t* row_ptr_in, const int64_t* split_rows,
+void launch_layout_splits(const CsrImage& src, const int64_t* order, const int64_t* row_ptr_in, const int64_t* split_rows,
                           int32_t n_splits, int64_t B, BatchDev& dst, int64_t* split_rp, hipStream_t st) {
   FM_HIP_CHECK(hipMemsetAsync(split_rp, 0, sizeof(int64_t) * (B + n_splits), st));
   hipLaunchKernelGGL(k_layout_splits, dim3(grid_for(std::max<int64_t>(B, 1) * 16, kBlock, 256 * 8)), dim3(kBlock), 0, st,
-                     src_row_ptr, src_label, xoff, col_in, x_in, order, row_ptr_in, split_rows, n_splits, B,
+                     src.row_ptr, src.label, src.xoff, src.col, src.x, order, row_ptr_in, split_rows, n_splits, B,
                      dst.row_ptr.as<int64_t>(), dst.label.as<double>(), dst.col.as<uint32_t>(), dst.ent.as<uint2>(),
                      dst.xs.as<float>(), split_rp);
   FM_HIP_CHECK(hipGetLastError());

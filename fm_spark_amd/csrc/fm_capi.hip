@@ -133,40 +133,56 @@ struct Staged {
   size_t o_extra = 0;  // the caller's `extra` bytes of staging, behind the x area
   int nruns = 0;
   int64_t run_at[16] = {0}, run_n[16] = {0};  // packed value runs in the x area (floats)
+  // the image's five arrays at base: the pinned staging, or its device copy
+  CsrImage view(void* base) const {
+    char* p = reinterpret_cast<char*>(base);
+    return {reinterpret_cast<int64_t*>(p), reinterpret_cast<double*>(p + o_lab), reinterpret_cast<int32_t*>(p + o_xoff),
+            reinterpret_cast<uint32_t*>(p + o_col), reinterpret_cast<float*>(p + o_x)};
+  }
+  // the image's copies from the staging to its device copy, on st: one through col, then the packed
+  // value runs, each where its rows' xoff point
+  void enqueue_copies(void* dev, const void* pin, hipStream_t st) const {
+    FM_HIP_CHECK(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st));
+    for (int r = 0; r < nruns; ++r)
+      if (run_n[r] > 0)
+        FM_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(dev) + o_x + sizeof(float) * run_at[r],
+                                    reinterpret_cast<const char*>(pin) + o_x + sizeof(float) * run_at[r],
+                                    sizeof(float) * run_n[r], hipMemcpyHostToDevice, st));
+  }
 };
 
-static Staged stage_csr(fm_ctx* ctx, const fm_csr* c, bool check_range, Pinned& pin, size_t extra = 0) {
+void check_csr(const fm_csr* c) {
   FM_REQUIRE(c != nullptr, "null fm_csr");
   FM_REQUIRE(c->n_rows >= 0 && c->nnz >= 0, "negative n_rows / nnz");
   FM_REQUIRE(c->n_rows < (int64_t(1) << 31), "n_rows must be < 2^31");
   FM_REQUIRE(c->nnz < (int64_t(1) << 31), "nnz must be < 2^31 per batch");
   FM_REQUIRE(c->n_rows == 0 || (c->row_ptr && c->label), "null row_ptr / label");
   FM_REQUIRE(c->nnz == 0 || (c->col && c->val), "null col / val");
+  const int64_t B = c->n_rows;
+  if (B > 0) {
+    FM_REQUIRE(c->row_ptr[0] == 0, "row_ptr[0] must be 0");
+    FM_REQUIRE(c->row_ptr[B] == c->nnz, "row_ptr[n_rows] must equal nnz");
+    for (int64_t i = 0; i < B; ++i) FM_REQUIRE(c->row_ptr[i] <= c->row_ptr[i + 1], "row_ptr must be non-decreasing");
+  } else {
+    FM_REQUIRE(c->nnz == 0, "nnz > 0 with n_rows == 0");
+  }
+}
+
+static Staged stage_csr(fm_ctx* ctx, const fm_csr* c, bool check_range, Pinned& pin, size_t extra = 0) {
+  check_csr(c);
   Staged g;
   const int64_t B = c->n_rows, N = c->nnz;
   g.B = B;
   g.N = N;
-  if (B > 0) {
-    FM_REQUIRE(c->row_ptr[0] == 0, "row_ptr[0] must be 0");
-    FM_REQUIRE(c->row_ptr[B] == N, "row_ptr[n_rows] must equal nnz");
-    for (int64_t i = 0; i < B; ++i) FM_REQUIRE(c->row_ptr[i] <= c->row_ptr[i + 1], "row_ptr must be non-decreasing");
-  } else {
-    FM_REQUIRE(N == 0, "nnz > 0 with n_rows == 0");
-  }
   g.o_lab = sizeof(int64_t) * (B + 1);
   g.o_xoff = g.o_lab + sizeof(double) * B;
   g.o_col = (g.o_xoff + sizeof(int32_t) * B + 15) / 16 * 16;
   g.o_x = (g.o_col + sizeof(uint32_t) * N + 15) / 16 * 16;
   g.o_extra = (g.o_x + sizeof(float) * N + 16 + 15) / 16 * 16;  // M <= N
   pin.ensure_slack(g.o_extra + extra);
-  char* base = reinterpret_cast<char*>(pin.p);
-  int64_t* rp = reinterpret_cast<int64_t*>(base);
-  double* lab = reinterpret_cast<double*>(base + g.o_lab);
-  int32_t* xoff = reinterpret_cast<int32_t*>(base + g.o_xoff);
-  uint32_t* col = reinterpret_cast<uint32_t*>(base + g.o_col);
-  float* xs = reinterpret_cast<float*>(base + g.o_x);
-  if (B > 0) std::memcpy(rp, c->row_ptr, sizeof(int64_t) * (B + 1));
-  else rp[0] = 0;
+  const CsrImage im = g.view(pin.p);
+  if (B > 0) std::memcpy(im.row_ptr, c->row_ptr, sizeof(int64_t) * (B + 1));
+  else im.row_ptr[0] = 0;
   const int64_t F = ctx->cfg.num_features;
   std::atomic<int> bad{0};  // 1 negative id, 2 id >= num_features
   std::atomic<int64_t> mx{-1}, mlen{0};
@@ -178,17 +194,17 @@ static Staged stage_csr(fm_ctx* ctx, const fm_csr* c, bool check_range, Pinned& 
     int64_t lmx = -1, m = x0, llen = 0;
     int lbad = 0;
     for (int64_t i = r0; i < r1; ++i) {
-      lab[i] = c->label[i];  // Double, as the reference's label column (SGD.scala:145-146)
+      im.label[i] = c->label[i];  // Double, as the reference's label column (SGD.scala:145-146)
       llen = std::max<int64_t>(llen, c->row_ptr[i + 1] - c->row_ptr[i]);
-      xoff[i] = (int32_t)m;
+      im.xoff[i] = (int32_t)m;
       for (int64_t e = c->row_ptr[i]; e < c->row_ptr[i + 1]; ++e) {
         const int32_t id = c->col[e];
         if (id < 0) lbad |= 1;
         else if (check_range && id >= F) lbad |= 2;
         const float x = (float)c->val[e];
         const uint32_t valued = x != 1.0f;
-        col[e] = (uint32_t)id | (valued << 31);
-        xs[m] = x;  // branch-free: the slot is taken only by a value that is not 1
+        im.col[e] = (uint32_t)id | (valued << 31);
+        im.x[m] = x;  // branch-free: the slot is taken only by a value that is not 1
         m += valued;
         lmx = std::max<int64_t>(lmx, id);
       }
@@ -228,41 +244,22 @@ bool fuse_rule(const fm_ctx* ctx) {
 static bool fuse_on(const fm_ctx* ctx) { return ctx->cfg.shard_count == 1 && fuse_rule(ctx); }
 
 static bool batch_fits(const fm_batch* b, const Staged& g) {
-  return b->dev.row_ptr.bytes >= sizeof(int64_t) * (g.B + 1) &&
-         b->dev.col.bytes >= sizeof(uint32_t) * std::max<int64_t>(g.N, 4) + 16 &&
-         b->dev.ent.bytes >= sizeof(uint32_t) * 2 * std::max<int64_t>(g.N, 4) + 16 &&
-         b->dev.xs.bytes >= sizeof(float) * std::max<int64_t>(g.N, 4) + 16 &&
-         b->dev.label.bytes >= sizeof(double) * std::max<int64_t>(g.B, 4) + 16 &&
-         b->up.bytes >= g.o_x + sizeof(float) * g.N + 16;
+  const BatchBytes z = batch_bytes(g.B, g.N);
+  return b->dev.row_ptr.bytes >= z.row_ptr && b->dev.col.bytes >= z.col && b->dev.ent.bytes >= z.ent &&
+         b->dev.xs.bytes >= z.xs && b->dev.label.bytes >= z.label && b->up.bytes >= g.o_x + sizeof(float) * g.N + 16;
 }
 
-// b's device buffers (grown, never shrunk) filled from the staging by one async copy on st (into
-// b->up, the staging's device image), then col / label / row_ptr and the exploded entries are
+// b's device buffers (grown, never shrunk) filled from the staging by the image's async copies on st
+// (into b->up, the staging's device image), then col / label / row_ptr and the exploded entries are
 // laid out from it by one kernel pass on st.
 static void copy_staged(fm_ctx* ctx, const Staged& g, const Pinned& pin, fm_batch* b, hipStream_t st) {
-  const int64_t B = g.B, N = g.N;
   b->owner = ctx;
   b->device = ctx->cfg.device;
   b->max_id = g.max_id;
-  b->dev.n_rows = B;
-  b->dev.nnz = N;
-  b->dev.row_ptr.ensure_slack(sizeof(int64_t) * (B + 1));
-  b->dev.col.ensure_slack(sizeof(uint32_t) * std::max<int64_t>(N, 4) + 16);
-  b->dev.ent.ensure_slack(sizeof(uint32_t) * 2 * std::max<int64_t>(N, 4) + 16);
-  b->dev.xs.ensure_slack(sizeof(float) * std::max<int64_t>(N, 4) + 16);
-  b->dev.label.ensure_slack(sizeof(double) * std::max<int64_t>(B, 4) + 16);
-  b->up.ensure_slack(g.o_x + sizeof(float) * N + 16);
-  FM_HIP_CHECK(hipMemcpyAsync(b->up.p, pin.p, g.bytes, hipMemcpyHostToDevice, st));
-  for (int r = 0; r < g.nruns; ++r)  // the packed value runs, each where its rows' xoff point
-    if (g.run_n[r] > 0)
-      FM_HIP_CHECK(hipMemcpyAsync(b->up.as<char>() + g.o_x + sizeof(float) * g.run_at[r],
-                                  reinterpret_cast<const char*>(pin.p) + g.o_x + sizeof(float) * g.run_at[r],
-                                  sizeof(float) * g.run_n[r], hipMemcpyHostToDevice, st));
-  const char* up = b->up.as<char>();
-  launch_explode(reinterpret_cast<const int64_t*>(up), reinterpret_cast<const double*>(up + g.o_lab),
-                 reinterpret_cast<const int32_t*>(up + g.o_xoff), reinterpret_cast<const uint32_t*>(up + g.o_col),
-                 reinterpret_cast<const float*>(up + g.o_x), B, N, b->dev.row_ptr.as<int64_t>(),
-                 b->dev.label.as<double>(), b->dev.col.as<uint32_t>(), b->dev.ent.as<uint2>(), b->dev.xs.as<float>(), st);
+  size_batch(b->dev, g.B, g.N);
+  b->up.ensure_slack(g.o_x + sizeof(float) * g.N + 16);
+  g.enqueue_copies(b->up.p, pin.p, st);
+  launch_explode(g.view(b->up.p), g.B, g.N, b->dev, st);
 }
 
 // Synchronous upload (fm_batch_create, fm_predict, fm_loss_grad): staged in the context's
@@ -279,6 +276,22 @@ void upload_batch(fm_ctx* ctx, const fm_csr* c, fm_batch* b, bool check_range) {
 fm_batch* host_batch(fm_ctx* ctx) {
   if (!ctx->host_batch) ctx->host_batch.reset(new fm_batch());
   return ctx->host_batch.get();
+}
+
+OutBatch out_batch(fm_ctx* ctx, const fm_batch* data, fm_batch** out, bool group) {
+  OutBatch o;
+  o.out = out;
+  o.b = *out;
+  if (o.b == nullptr) {
+    o.fresh.reset(group ? new_group_batch(ctx) : new fm_batch());
+    o.b = o.fresh.get();
+    o.b->owner = ctx;
+    o.b->device = ctx->cfg.device;
+  } else {
+    FM_REQUIRE(o.b->owner == ctx && o.b != data && !o.b->grp == !group && o.b->split_rows.empty(),
+               "out must be a batch of this context other than data");
+  }
+  return o;
 }
 
 // A batch refilled by fm_batch_from_rows is written on the side stream: a reader on stream st waits
@@ -674,11 +687,7 @@ int fm_batch_prepare(fm_ctx* ctx, fm_batch* b) {
     FM_REQUIRE(b->split_rows.empty(), "a dataset made by fm_batch_create_splits is prepared through its split views");
     const int64_t N = b->dev.nnz;
     if (N == 0) return FM_OK;
-    if (!b->ready) {
-      FM_HIP_CHECK(hipEventCreateWithFlags(&b->ready, hipEventDisableTiming));
-      FM_HIP_CHECK(hipEventCreateWithFlags(&b->last_use, hipEventDisableTiming));
-      FM_HIP_CHECK(hipEventRecord(b->last_use, ctx->stream));
-    }
+    b->ensure_events(ctx->stream);
     b->skeys.ensure_slack(sizeof(uint32_t) * N);
     b->sents.ensure_slack(sizeof(uint2) * N);
     // the shared sort workspace and this batch's view may still be read by an enqueued step; a batch
@@ -722,24 +731,11 @@ int fm_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows, i
     const int64_t Bd = data->dev.n_rows;
     FM_REQUIRE((int64_t)data->host_rp.size() == Bd + 1,
                "data must be a batch made by fm_batch_create");
-    fm_batch* b = *out;
-    std::unique_ptr<fm_batch> fresh;
-    if (b == nullptr) {
-      fresh.reset(new fm_batch());
-      b = fresh.get();
-      b->owner = ctx;
-      b->device = ctx->cfg.device;
-    } else {
-      FM_REQUIRE(b->owner == ctx && b != data && !b->grp && b->split_rows.empty(),
-                 "out must be a batch of this context other than data");
-    }
+    OutBatch res = out_batch(ctx, data, out, false);
+    fm_batch* b = res.b;
     // a split view refilled as a selection: its borrowed pointers are dropped, its own buffers grown below
     b->detach_view();
-    if (!b->ready) {
-      FM_HIP_CHECK(hipEventCreateWithFlags(&b->ready, hipEventDisableTiming));
-      FM_HIP_CHECK(hipEventCreateWithFlags(&b->last_use, hipEventDisableTiming));
-      FM_HIP_CHECK(hipEventRecord(b->last_use, ctx->stream));
-    }
+    b->ensure_events(ctx->stream);
     if (!b->built) {
       FM_HIP_CHECK(hipEventCreateWithFlags(&b->built, hipEventDisableTiming));
       FM_HIP_CHECK(hipEventCreateWithFlags(&b->sel_copied, hipEventDisableTiming));
@@ -768,14 +764,8 @@ int fm_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows, i
     FM_HIP_CHECK(hipStreamWaitEvent(gs, b->last_use, 0));
     if (b->sh && b->sh->last_use) FM_HIP_CHECK(hipStreamWaitEvent(gs, b->sh->last_use, 0));
     if (b->prepared && b->ready) FM_HIP_CHECK(hipStreamWaitEvent(gs, b->ready, 0));
-    b->dev.n_rows = n;
-    b->dev.nnz = N;
     b->max_id = data->max_id;
-    b->dev.row_ptr.ensure_slack(sizeof(int64_t) * (n + 1));
-    b->dev.col.ensure_slack(sizeof(uint32_t) * std::max<int64_t>(N, 4) + 16);
-    b->dev.ent.ensure_slack(sizeof(uint32_t) * 2 * std::max<int64_t>(N, 4) + 16);
-    b->dev.xs.ensure_slack(sizeof(float) * std::max<int64_t>(N, 4) + 16);
-    b->dev.label.ensure_slack(sizeof(double) * std::max<int64_t>(n, 4) + 16);
+    size_batch(b->dev, n, N);
     b->up.ensure_slack(img + 16);
     FM_HIP_CHECK(hipMemcpyAsync(b->up.p, b->sel_pin.p, img, hipMemcpyHostToDevice, gs));
     FM_HIP_CHECK(hipEventRecord(b->sel_copied, gs));
@@ -788,7 +778,7 @@ int fm_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows, i
     FM_HIP_CHECK(hipEventRecord(b->built, gs));
     b->prepared = false;  // a refilled batch is sorted again by its own fm_batch_prepare
     b->host_rp.clear();   // a selection is not itself a dataset (fm_batch_create's batches are)
-    if (fresh) *out = fresh.release();
+    res.commit();
     return FM_OK;
   });
 }
@@ -845,29 +835,15 @@ int fm_batch_layout_splits(fm_ctx* ctx, const fm_csr* csr, int32_t n_splits, con
     b->owner = ctx;
     b->device = ctx->cfg.device;
     b->max_id = g.max_id;
-    b->dev.n_rows = n;
-    b->dev.nnz = N;
-    b->dev.row_ptr.ensure_slack(sizeof(int64_t) * (n + 1));
-    b->dev.col.ensure_slack(sizeof(uint32_t) * std::max<int64_t>(N, 4) + 16);
-    b->dev.ent.ensure_slack(sizeof(uint32_t) * 2 * std::max<int64_t>(N, 4) + 16);
-    b->dev.xs.ensure_slack(sizeof(float) * std::max<int64_t>(N, 4) + 16);
-    b->dev.label.ensure_slack(sizeof(double) * std::max<int64_t>(n, 4) + 16);
+    size_batch(b->dev, n, N);
     b->split_rp.ensure(sizeof(int64_t) * (n + n_splits));
-    // the image's copies as copy_staged makes them: through col, then the packed value runs
+    // the source's image and, behind it, the extra tail
     b->up.ensure(g.o_extra + extra);
-    char* up = b->up.as<char>();
-    const char* pin = reinterpret_cast<const char*>(ctx->up_pin.p);
-    FM_HIP_CHECK(hipMemcpyAsync(up, pin, g.bytes, hipMemcpyHostToDevice, st));
-    for (int r = 0; r < g.nruns; ++r)
-      if (g.run_n[r] > 0)
-        FM_HIP_CHECK(hipMemcpyAsync(up + g.o_x + sizeof(float) * g.run_at[r], pin + g.o_x + sizeof(float) * g.run_at[r],
-                                    sizeof(float) * g.run_n[r], hipMemcpyHostToDevice, st));
-    FM_HIP_CHECK(hipMemcpyAsync(up + g.o_extra, pin + g.o_extra, extra, hipMemcpyHostToDevice, st));
-    const int64_t* dord = reinterpret_cast<const int64_t*>(up + g.o_extra);
-    launch_layout_splits(reinterpret_cast<const int64_t*>(up), reinterpret_cast<const double*>(up + g.o_lab),
-                         reinterpret_cast<const int32_t*>(up + g.o_xoff), reinterpret_cast<const uint32_t*>(up + g.o_col),
-                         reinterpret_cast<const float*>(up + g.o_x), dord, dord + n, dord + 2 * n + 1, n_splits, n, b->dev,
-                         b->split_rp.as<int64_t>(), st);
+    g.enqueue_copies(b->up.p, ctx->up_pin.p, st);
+    int64_t* dord = reinterpret_cast<int64_t*>(b->up.as<char>() + g.o_extra);
+    FM_HIP_CHECK(hipMemcpyAsync(dord, hord, extra, hipMemcpyHostToDevice, st));
+    launch_layout_splits(g.view(b->up.p), dord, dord + n, dord + 2 * n + 1, n_splits, n, b->dev, b->split_rp.as<int64_t>(),
+                         st);
     b->host_rp.assign(rp, rp + n + 1);
     b->split_rows.assign(split_rows, split_rows + n_splits + 1);
     FM_HIP_CHECK(hipStreamSynchronize(st));
@@ -885,28 +861,15 @@ int fm_batch_split_view(fm_ctx* ctx, const fm_batch* data, int32_t split, fm_bat
     const int64_t ns = (int64_t)data->split_rows.size() - 1;
     FM_REQUIRE(ns >= 1, "data must be a dataset made by fm_batch_create_splits");
     FM_REQUIRE(split >= 0 && split < ns, "split index out of range");
-    fm_batch* b = *out;
-    std::unique_ptr<fm_batch> fresh;
-    if (b == nullptr) {
-      fresh.reset(new fm_batch());
-      b = fresh.get();
-      b->owner = ctx;
-      b->device = ctx->cfg.device;
-    } else {
-      FM_REQUIRE(b->owner == ctx && b != data && !b->grp && b->split_rows.empty(),
-                 "out must be a batch of this context other than data");
-    }
+    OutBatch res = out_batch(ctx, data, out, false);
+    fm_batch* b = res.b;
     if (!b->view_of) {
       // an owning batch becomes a view: its own buffers are freed once no queued work reads them
       for (hipEvent_t e : {b->last_use, b->ready, b->built, b->sel_copied})
         if (e) FM_HIP_CHECK(hipEventSynchronize(e));
       for (DevBuf* d : {&b->dev.row_ptr, &b->dev.col, &b->dev.ent, &b->dev.xs, &b->dev.label, &b->up}) d->release();
     }
-    if (!b->ready) {
-      FM_HIP_CHECK(hipEventCreateWithFlags(&b->ready, hipEventDisableTiming));
-      FM_HIP_CHECK(hipEventCreateWithFlags(&b->last_use, hipEventDisableTiming));
-      FM_HIP_CHECK(hipEventRecord(b->last_use, ctx->stream));
-    }
+    b->ensure_events(ctx->stream);
     // the split's rows, entries and labels in place: pointers into data (no copy, no gather); the
     // step's reads of a view are ordered like any batch's (data was complete when it was created)
     const int64_t r0 = data->split_rows[split], r1 = data->split_rows[split + 1];
@@ -922,7 +885,7 @@ int fm_batch_split_view(fm_ctx* ctx, const fm_batch* data, int32_t split, fm_bat
     b->max_id = data->max_id;
     b->prepared = false;
     b->host_rp.clear();
-    if (fresh) *out = fresh.release();
+    res.commit();
     return FM_OK;
   });
 }

@@ -100,7 +100,7 @@ struct fm_batch {
   int device = 0;
   BatchDev dev;
   int64_t max_id = -1;
-  DevBuf up;  // device image of the host staging (fm_capi.hip copy_staged)
+  DevBuf up;  // device image of the host staging (fm_capi.hip Staged::enqueue_copies)
   // feature-major view produced by fm_batch_prepare (consumed once by the next step): the whole
   // sorted view in skeys / sents, or -- split = true, the fused step -- the whole sorted view in
   // fkeys / fents, which the step splits into the runs of two or more entries (skeys / sents) with
@@ -111,6 +111,14 @@ struct fm_batch {
   bool split = false;
   hipEvent_t ready = nullptr;     // recorded on the side stream after the prepared sort
   hipEvent_t last_use = nullptr;  // recorded on the main stream after a step read the batch
+  // the pair made on first use (fm_batch_prepare, fm_batch_from_rows, fm_batch_split_view); last_use
+  // starts recorded on the context's main stream, so the first wait for it does not block
+  void ensure_events(hipStream_t main) {
+    if (ready) return;
+    FM_HIP_CHECK(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+    FM_HIP_CHECK(hipEventCreateWithFlags(&last_use, hipEventDisableTiming));
+    FM_HIP_CHECK(hipEventRecord(last_use, main));
+  }
   bool prepared = false;
   // fm_batch_from_rows: the host copy of row_ptr that sizes a selection of this batch's rows without
   // a device read (kept by fm_batch_create and fm_batch_from_rows), the selection's pinned staging
@@ -409,6 +417,21 @@ bool fuse_rule(const fm_ctx* ctx);
 // stream st waits until a batch refilled by fm_batch_from_rows has been gathered (copy stream)
 void wait_built(const fm_batch* b, hipStream_t st);
 void upload_batch(fm_ctx* ctx, const fm_csr* c, fm_batch* b, bool check_range);
+// what a well-formed fm_csr is (every upload checks it in stage_csr; fm_group.hip before it slices
+// the CSR by rows)
+void check_csr(const fm_csr* c);
+// The result handle of fm_batch_from_rows / fm_batch_split_view: *out when the caller passes a batch
+// to refill (validated: of this context, not data, not a split dataset, a group batch exactly when
+// `group`), else a fresh one, owned here until the call has succeeded (commit).
+struct OutBatch {
+  fm_batch* b = nullptr;
+  std::unique_ptr<fm_batch> fresh;
+  fm_batch** out = nullptr;
+  void commit() {
+    if (fresh) *out = fresh.release();
+  }
+};
+OutBatch out_batch(fm_ctx* ctx, const fm_batch* data, fm_batch** out, bool group);
 void reserve_work(fm_ctx* ctx, int64_t B, int64_t N);
 
 // the sharded route (fm_shard_route) in two halves, for fm_group.hip: enqueue (counts stay in
@@ -430,6 +453,7 @@ void shard_combine_predict(fm_ctx* ctx, fm_batch* b, const void* partials_in, co
 
 // multi-GPU contexts (fm_group.hip); each runs inside the group context's guarded()
 int group_create(const fm_config* cfg, fm_ctx** out);
+fm_batch* new_group_batch(fm_ctx* ctx);  // an fm_batch whose parts are member batches
 int group_batch_create(fm_ctx* ctx, const fm_csr* csr, fm_batch** out);
 int group_batch_prepare(fm_ctx* ctx, fm_batch* b);
 int group_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows, int64_t n, fm_batch** out);

@@ -312,6 +312,15 @@ GroupBatch::~GroupBatch() {
 void GroupDeleter::operator()(Group* g) const { delete g; }
 void GroupBatchDeleter::operator()(GroupBatch* g) const { delete g; }
 
+// A new group batch (an fm_batch whose parts are member batches).
+fm_batch* new_group_batch(fm_ctx* ctx) {
+  std::unique_ptr<fm_batch> b(new fm_batch());
+  b->owner = ctx;
+  b->device = ctx->cfg.device;
+  b->grp.reset(new GroupBatch());
+  return b.release();
+}
+
 namespace {
 
 // run f with the member locked and its device current (internal, non-ABI member calls)
@@ -524,29 +533,59 @@ struct HostClock {
 
 void drop_route(Group& g, GroupBatch& gb);
 
-// Split a host CSR by rows over the local ranks and upload each part into its member batch.
-void upload_parts(Group& g, const fm_csr* c, GroupBatch& gb, bool check_range) {
-  FM_REQUIRE(c != nullptr, "null fm_csr");
-  FM_REQUIRE(c->n_rows >= 0 && c->nnz >= 0, "negative n_rows / nnz");
-  FM_REQUIRE(c->n_rows == 0 || (c->row_ptr && c->label), "null row_ptr / label");
-  const int64_t B = c->n_rows;
-  if (B > 0) {
-    FM_REQUIRE(c->row_ptr[0] == 0 && c->row_ptr[B] == c->nnz, "row_ptr must run from 0 to nnz");
-    for (int64_t i = 0; i < B; ++i) FM_REQUIRE(c->row_ptr[i] <= c->row_ptr[i + 1], "row_ptr must be non-decreasing");
-  } else {
-    FM_REQUIRE(c->nnz == 0, "nnz > 0 with n_rows == 0");
-  }
-  drop_route(g, gb);  // a routed plan of the old contents is dropped before its buffers are reused
+// Local rank l's share [lo, hi) of a range of n rows cut over the L local ranks.  Every cut is this
+// one: a host batch's and a selection's rows (upload_parts, group_batch_from_rows), each split of a
+// dataset (group_batch_create_splits, group_batch_layout_splits), and the row0 of a split view's
+// part (group_batch_split_view) -- where group_predict_* places the rank's predictions, so it must be
+// the start of the share the builders cut.
+struct Share {
+  int64_t lo, hi;
+};
+Share rank_share(int64_t n, int l, int L) { return {n * l / L, n * (l + 1) / L}; }
+
+// A group batch about to be refilled: the routed plan of its old contents is dropped before its
+// buffers are reused, and so are the per-rank full copies a former dataset holds of them (none on a
+// batch that was only ever uploaded to: dataset_replica alone makes them).
+void reset_group_batch(Group& g, GroupBatch& gb) {
+  drop_route(g, gb);
+  for (fm_batch* f : gb.full)
+    if (f) fm_batch_destroy(f);
+  gb.full.clear();
   gb.parts.resize(g.L);
+  gb.prefetched = false;
+}
+
+// A group batch whose parts are set: the job's miniBatchSize, and fm_batch_rows / fm_batch_nnz of
+// the handle.  gather: the ranks' row counts all-gathered over every process (one host wait, which
+// also synchronises every rank's side stream); otherwise this process holds the whole job and its
+// own rows are the count -- which of the two a constructor takes is its caller's decision.
+void close_group_batch(Group& g, fm_batch* b, bool gather) {
+  GroupBatch& gb = *b->grp;
+  if (gather) {
+    std::vector<std::vector<int64_t>> cnt(g.L, std::vector<int64_t>(1));
+    for (int l = 0; l < g.L; ++l) cnt[l][0] = gb.parts[l].rows;
+    const std::vector<int64_t> all = allgather(g, cnt, 1);
+    gb.global_rows = std::accumulate(all.begin(), all.end(), int64_t(0));
+  } else {
+    gb.global_rows = gb.rows;
+  }
+  b->dev.n_rows = gb.rows;
+  b->dev.nnz = gb.nnz;
+}
+
+// Split a host CSR by rows over the local ranks and upload each part into its member batch.
+void upload_parts(Group& g, const fm_csr* c, fm_batch* b, bool check_range) {
+  check_csr(c);
+  GroupBatch& gb = *b->grp;
+  reset_group_batch(g, gb);
+  const int64_t B = c->n_rows;
   gb.rows = B;
   gb.nnz = c->nnz;
-  gb.prefetched = false;
   std::vector<int64_t> rp;
-  std::vector<std::vector<int64_t>> rows(g.L, std::vector<int64_t>(1));
   for (int l = 0; l < g.L; ++l) {
     Rank& r = g.ranks[l];
     GPart& p = gb.parts[l];
-    const int64_t r0 = B * l / g.L, r1 = B * (l + 1) / g.L;
+    const auto [r0, r1] = rank_share(B, l, g.L);
     const int64_t e0 = B > 0 ? c->row_ptr[r0] : 0, e1 = B > 0 ? c->row_ptr[r1] : 0;
     rp.resize(r1 - r0 + 1);
     for (int64_t i = r0; i <= r1; ++i) rp[i - r0] = B > 0 ? c->row_ptr[i] - e0 : 0;
@@ -564,24 +603,8 @@ void upload_parts(Group& g, const fm_csr* c, GroupBatch& gb, bool check_range) {
     p.rows = sub.n_rows;
     p.row0 = r0;
     p.nnz = sub.nnz;
-    rows[l][0] = p.rows;
   }
-  const std::vector<int64_t> all = allgather(g, rows, 1);
-  gb.global_rows = std::accumulate(all.begin(), all.end(), int64_t(0));
-}
-
-// A new group batch (an fm_batch whose parts are member batches).
-fm_batch* new_group_batch(fm_ctx* ctx) {
-  std::unique_ptr<fm_batch> b(new fm_batch());
-  b->owner = ctx;
-  b->device = ctx->cfg.device;
-  b->grp.reset(new GroupBatch());
-  return b.release();
-}
-
-void sync_group_batch_view(fm_batch* b) {  // fm_batch_rows / fm_batch_nnz of the group batch
-  b->dev.n_rows = b->grp->rows;
-  b->dev.nnz = b->grp->nnz;
+  close_group_batch(g, b, true);
 }
 
 // Sharded prepare, phase 1: every local rank's route (fm_shard.hip phase 1) on its side stream,
@@ -1109,8 +1132,7 @@ fm_ctx* group_member0(fm_ctx* ctx) { return grp(ctx).ranks[0].m; }
 int group_batch_create(fm_ctx* ctx, const fm_csr* csr, fm_batch** out) {
   FM_REQUIRE(out != nullptr, "null out");
   std::unique_ptr<fm_batch> b(new_group_batch(ctx));
-  upload_parts(grp(ctx), csr, *b->grp, true);
-  sync_group_batch_view(b.get());
+  upload_parts(grp(ctx), csr, b.get(), true);
   *out = b.release();
   return FM_OK;
 }
@@ -1165,10 +1187,12 @@ fm_batch* dataset_replica(Group& g, GroupBatch& dg, int l, const std::vector<int
     f->dev.n_rows = B;
     f->dev.nnz = N;
     f->max_id = mx;
-    f->dev.row_ptr.ensure(sizeof(int64_t) * (B + 1));
-    f->dev.col.ensure(sizeof(uint32_t) * std::max<int64_t>(N, 4) + 16);
-    f->dev.xs.ensure(sizeof(float) * std::max<int64_t>(N, 4) + 16);
-    f->dev.label.ensure(sizeof(double) * std::max<int64_t>(B, 4) + 16);
+    // exact sizes (made once per dataset), and no ent: a gather's source needs none
+    const BatchBytes z = batch_bytes(B, N);
+    f->dev.row_ptr.ensure(z.row_ptr);
+    f->dev.col.ensure(z.col);
+    f->dev.xs.ensure(z.xs);
+    f->dev.label.ensure(z.label);
     FM_HIP_CHECK(hipMemcpy(f->dev.row_ptr.p, rp.data(), sizeof(int64_t) * (B + 1), hipMemcpyHostToDevice));
     int64_t e = 0, row = 0;
     for (const Seg& sg : segs) {
@@ -1203,29 +1227,16 @@ int group_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows
   FM_REQUIRE(data != nullptr && data->owner == ctx && data->grp, "data belongs to another context");
   GroupBatch& dg = *const_cast<fm_batch*>(data)->grp;
   for (int64_t i = 0; i < n; ++i) FM_REQUIRE(rows[i] >= 0 && rows[i] < dg.rows, "row index out of [0, rows of data)");
-  std::unique_ptr<fm_batch> fresh;
-  fm_batch* b = *out;
-  if (!b) {
-    fresh.reset(new_group_batch(ctx));
-    b = fresh.get();
-  }
-  FM_REQUIRE(b->owner == ctx && b->grp && b != data && b->split_rows.empty(),
-             "out must be a batch of this context other than data");
+  OutBatch res = out_batch(ctx, data, out, true);
+  fm_batch* b = res.b;
   GroupBatch& gb = *b->grp;
-  drop_route(g, gb);  // a routed plan of the old contents is dropped before its buffers are reused
-  // a former dataset refilled as a selection: its per-rank full copies describe the old contents
-  for (fm_batch* f : gb.full)
-    if (f) fm_batch_destroy(f);
-  gb.full.clear();
-  gb.parts.resize(g.L);
-  gb.prefetched = false;
+  reset_group_batch(g, gb);
   gb.rows = n;
   gb.nnz = 0;
-  std::vector<std::vector<int64_t>> cnt(g.L, std::vector<int64_t>(1));
   for (int l = 0; l < g.L; ++l) {
     Rank& r = g.ranks[l];
     GPart& p = gb.parts[l];
-    const int64_t r0 = n * l / g.L, r1 = n * (l + 1) / g.L;  // the split's rows by rows, as upload_parts
+    const auto [r0, r1] = rank_share(n, l, g.L);
     fm_batch* src = dataset_replica(g, dg, l, data->split_rows);
     mcheck(fm_batch_from_rows(r.m, src, rows + r0, r1 - r0, &p.b), "fm_batch_from_rows");
     p.device = r.device;
@@ -1233,43 +1244,26 @@ int group_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows
     p.row0 = r0;
     p.nnz = fm_batch_nnz(p.b);
     gb.nnz += p.nnz;
-    cnt[l][0] = p.rows;
   }
-  // the global miniBatchSize: this process's rows, or every process's (one host wait for the counts)
-  if (g.nprocs == 1) {
-    gb.global_rows = n;
-  } else {
-    const std::vector<int64_t> all = allgather(g, cnt, 1);
-    gb.global_rows = std::accumulate(all.begin(), all.end(), int64_t(0));
-  }
-  sync_group_batch_view(b);
-  if (fresh) *out = fresh.release();
+  // fit calls this every iteration: a one-process job takes its own rows, with no host wait
+  close_group_batch(g, b, g.nprocs > 1);
+  res.commit();
   return FM_OK;
 }
 
 // A dataset laid out split by split (fm_batch_create_splits): local rank l holds its share of every
-// split -- the split's rows by rows over the local ranks, as a host CSR's are (upload_parts) -- as a
+// split -- the split's rows by rows over the local ranks (rank_share), as a host CSR's are -- as a
 // member dataset with the same number of splits, so split s of the group dataset is every rank's
 // split s (group_batch_split_view).
 int group_batch_create_splits(fm_ctx* ctx, const fm_csr* c, int32_t n_splits, const int64_t* split_rows,
                               fm_batch** out) {
   Group& g = grp(ctx);
-  FM_REQUIRE(c->n_rows >= 0 && c->nnz >= 0, "negative n_rows / nnz");
-  FM_REQUIRE(c->n_rows == 0 || (c->row_ptr && c->label), "null row_ptr / label");
-  FM_REQUIRE(c->nnz == 0 || (c->col && c->val), "null col / val");
-  const int64_t B = c->n_rows;
-  if (B > 0) {
-    FM_REQUIRE(c->row_ptr[0] == 0 && c->row_ptr[B] == c->nnz, "row_ptr must run from 0 to nnz");
-    for (int64_t i = 0; i < B; ++i) FM_REQUIRE(c->row_ptr[i] <= c->row_ptr[i + 1], "row_ptr must be non-decreasing");
-  } else {
-    FM_REQUIRE(c->nnz == 0, "nnz > 0 with n_rows == 0");
-  }
+  check_csr(c);
   std::unique_ptr<fm_batch> b(new_group_batch(ctx));
   GroupBatch& gb = *b->grp;
   gb.parts.resize(g.L);
-  gb.rows = B;
+  gb.rows = c->n_rows;
   gb.nnz = c->nnz;
-  std::vector<std::vector<int64_t>> rows(g.L, std::vector<int64_t>(1));
   std::vector<int64_t> rp, msr;
   std::vector<int32_t> col;
   std::vector<double> val, lab;
@@ -1280,8 +1274,8 @@ int group_batch_create_splits(fm_ctx* ctx, const fm_csr* c, int32_t n_splits, co
     val.clear();
     lab.clear();
     for (int32_t s = 0; s < n_splits; ++s) {
-      const int64_t ns = split_rows[s + 1] - split_rows[s];
-      const int64_t a = split_rows[s] + ns * l / g.L, z = split_rows[s] + ns * (l + 1) / g.L;
+      const Share sh = rank_share(split_rows[s + 1] - split_rows[s], l, g.L);
+      const int64_t a = split_rows[s] + sh.lo, z = split_rows[s] + sh.hi;
       for (int64_t i = a; i < z; ++i) {
         lab.push_back(c->label[i]);
         col.insert(col.end(), c->col + c->row_ptr[i], c->col + c->row_ptr[i + 1]);
@@ -1303,21 +1297,18 @@ int group_batch_create_splits(fm_ctx* ctx, const fm_csr* c, int32_t n_splits, co
     p.rows = sub.n_rows;
     p.row0 = 0;  // its rows are not one range of the dataset (the dataset is not predicted as a whole)
     p.nnz = sub.nnz;
-    rows[l][0] = p.rows;
   }
-  const std::vector<int64_t> all = allgather(g, rows, 1);
-  gb.global_rows = std::accumulate(all.begin(), all.end(), int64_t(0));
   b->split_rows.assign(split_rows, split_rows + n_splits + 1);
-  sync_group_batch_view(b.get());
+  close_group_batch(g, b.get(), true);
   *out = b.release();
   return FM_OK;
 }
 
 // fm_batch_layout_splits: the same dataset from the source in its own row order.  Local rank l's share
-// of every split, cut as group_batch_create_splits cuts it, is a row list of its own (the shares of
-// `order`) with its own split offsets: the member lays it out on its device from the whole source,
-// so no per-rank sub-CSR is assembled on the host.  Every member stages the source itself (DESIGN.md
-// section 6).
+// of every split (rank_share, as group_batch_create_splits cuts it) is a row list of its own (the
+// shares of `order`) with its own split offsets: the member lays it out on its device from the whole
+// source, so no per-rank sub-CSR is assembled on the host.  Every member stages the source itself
+// (DESIGN.md section 6).
 int group_batch_layout_splits(fm_ctx* ctx, const fm_csr* c, int32_t n_splits, const int64_t* split_rows,
                               const int64_t* order, fm_batch** out) {
   Group& g = grp(ctx);
@@ -1326,14 +1317,13 @@ int group_batch_layout_splits(fm_ctx* ctx, const fm_csr* c, int32_t n_splits, co
   gb.parts.resize(g.L);
   gb.rows = split_rows[n_splits];
   gb.nnz = 0;
-  std::vector<std::vector<int64_t>> rows(g.L, std::vector<int64_t>(1));
   std::vector<int64_t> ord, msr;
   for (int l = 0; l < g.L; ++l) {
     ord.clear();
     msr.assign(1, 0);
     for (int32_t s = 0; s < n_splits; ++s) {
-      const int64_t ns = split_rows[s + 1] - split_rows[s];
-      const int64_t a = split_rows[s] + ns * l / g.L, z = split_rows[s] + ns * (l + 1) / g.L;
+      const Share sh = rank_share(split_rows[s + 1] - split_rows[s], l, g.L);
+      const int64_t a = split_rows[s] + sh.lo, z = split_rows[s] + sh.hi;
       ord.insert(ord.end(), order + a, order + z);
       msr.push_back((int64_t)ord.size());
     }
@@ -1344,12 +1334,9 @@ int group_batch_layout_splits(fm_ctx* ctx, const fm_csr* c, int32_t n_splits, co
     p.row0 = 0;  // its rows are not one range of the dataset (the dataset is not predicted as a whole)
     p.nnz = fm_batch_nnz(p.b);
     gb.nnz += p.nnz;
-    rows[l][0] = p.rows;
   }
-  const std::vector<int64_t> all = allgather(g, rows, 1);
-  gb.global_rows = std::accumulate(all.begin(), all.end(), int64_t(0));
   b->split_rows.assign(split_rows, split_rows + n_splits + 1);
-  sync_group_batch_view(b.get());
+  close_group_batch(g, b.get(), true);
   *out = b.release();
   return FM_OK;
 }
@@ -1360,43 +1347,24 @@ int group_batch_split_view(fm_ctx* ctx, const fm_batch* data, int32_t split, fm_
   FM_REQUIRE(data->grp && !data->split_rows.empty(), "data must be a dataset made by fm_batch_create_splits");
   FM_REQUIRE(split >= 0 && split + 1 < (int32_t)data->split_rows.size(), "split index out of range");
   const GroupBatch& dg = *data->grp;
-  std::unique_ptr<fm_batch> fresh;
-  fm_batch* b = *out;
-  if (!b) {
-    fresh.reset(new_group_batch(ctx));
-    b = fresh.get();
-  }
-  FM_REQUIRE(b->owner == ctx && b->grp && b != data && b->split_rows.empty(),
-             "out must be a batch of this context other than data");
+  OutBatch res = out_batch(ctx, data, out, true);
+  fm_batch* b = res.b;
   GroupBatch& gb = *b->grp;
-  drop_route(g, gb);  // a routed plan of the old contents is dropped before the parts change
-  for (fm_batch* f : gb.full)
-    if (f) fm_batch_destroy(f);
-  gb.full.clear();
-  gb.parts.resize(g.L);
-  gb.prefetched = false;
+  reset_group_batch(g, gb);
   const int64_t n = data->split_rows[split + 1] - data->split_rows[split];
   gb.rows = n;
   gb.nnz = 0;
-  std::vector<std::vector<int64_t>> cnt(g.L, std::vector<int64_t>(1));
   for (int l = 0; l < g.L; ++l) {
     GPart& p = gb.parts[l];
     mcheck(fm_batch_split_view(g.ranks[l].m, dg.parts[l].b, split, &p.b), "fm_batch_split_view");
     p.device = g.ranks[l].device;
     p.rows = fm_batch_rows(p.b);
-    p.row0 = n * l / g.L;  // as group_batch_create_splits cut the split
+    p.row0 = rank_share(n, l, g.L).lo;
     p.nnz = fm_batch_nnz(p.b);
     gb.nnz += p.nnz;
-    cnt[l][0] = p.rows;
   }
-  if (g.nprocs == 1) {
-    gb.global_rows = n;
-  } else {
-    const std::vector<int64_t> all = allgather(g, cnt, 1);
-    gb.global_rows = std::accumulate(all.begin(), all.end(), int64_t(0));
-  }
-  sync_group_batch_view(b);
-  if (fresh) *out = fresh.release();
+  close_group_batch(g, b, g.nprocs > 1);  // every iteration of fit, as group_batch_from_rows
+  res.commit();
   return FM_OK;
 }
 
@@ -1430,16 +1398,14 @@ int group_step_batch(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, doub
 
 int group_step(fm_ctx* ctx, const fm_csr* csr, int32_t t, double step_size, double reg_param, fm_step_out* out) {
   fm_batch* b = host_slot(ctx);
-  upload_parts(grp(ctx), csr, *b->grp, true);
-  sync_group_batch_view(b);
+  upload_parts(grp(ctx), csr, b, true);
   return step_group_batch(ctx, *b->grp, t, step_size, reg_param, out);
 }
 
 int group_predict(fm_ctx* ctx, const fm_csr* csr, double lo, double hi, double* pred) {
   FM_REQUIRE(csr != nullptr && (csr->n_rows == 0 || pred), "null argument");
   fm_batch* b = host_slot(ctx);
-  upload_parts(grp(ctx), csr, *b->grp, false);
-  sync_group_batch_view(b);
+  upload_parts(grp(ctx), csr, b, false);
   predict_group_batch(ctx, *b->grp, lo, hi, pred);
   return FM_OK;
 }

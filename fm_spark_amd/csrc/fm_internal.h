@@ -152,6 +152,28 @@ struct BatchDev {
   DevBuf row_ptr, col, ent, label;  // int64 [B+1], uint32 [N] feature slot, uint2 [N], double [B]
   DevBuf xs;                         // fp32 [N]: x alone, the forward's stream (8 B per entry with col)
 };
+// The byte size of each BatchDev buffer for B rows and N entries.  The kernels read past the end on
+// purpose (k_forward's unguarded loads from clamped indices: at least 4 entries and 16 bytes beyond),
+// so this padding is a safety condition, and every constructor of a batch sizes its buffers here.
+struct BatchBytes {
+  size_t row_ptr, col, ent, xs, label;
+};
+inline BatchBytes batch_bytes(int64_t B, int64_t N) {
+  const size_t n = (size_t)(N > 4 ? N : 4), b = (size_t)(B > 4 ? B : 4);
+  return {sizeof(int64_t) * (size_t)(B + 1), sizeof(uint32_t) * n + 16, sizeof(uint2) * n + 16, sizeof(float) * n + 16,
+          sizeof(double) * b + 16};
+}
+// d holds B rows and N entries: its five buffers grown (never shrunk) to batch_bytes, with slack
+inline void size_batch(BatchDev& d, int64_t B, int64_t N) {
+  const BatchBytes z = batch_bytes(B, N);
+  d.n_rows = B;
+  d.nnz = N;
+  d.row_ptr.ensure_slack(z.row_ptr);
+  d.col.ensure_slack(z.col);
+  d.ent.ensure_slack(z.ent);
+  d.xs.ensure_slack(z.xs);
+  d.label.ensure_slack(z.label);
+}
 
 // The single-table step's per-sample record: S (kp floats) and, for kp <= 16, the sample's
 // {r, yhat} in the same 64-B (kp <= 12) or 128-B (kp = 16) record, so the update's S gather and
@@ -296,17 +318,22 @@ void launch_segment_sum(const uint32_t* skeys, const uint32_t* svals, int64_t n,
                         int64_t* n_out_dev, hipStream_t st);
 void launch_count_present(const TableView& T, int64_t* out, hipStream_t st);
 // the uploaded CSR image (row_ptr, label, xoff, col with bit 31 = a value follows, the compact
-// non-unit values) -> the device batch: row_ptr / label / col copied, ent[e] = {sample of e, x
+// non-unit values), on the host (the pinned staging) or on the device (its copy)
+struct CsrImage {
+  int64_t* row_ptr;
+  double* label;
+  int32_t* xoff;
+  uint32_t* col;
+  float* x;
+};
+// the device image -> the device batch: row_ptr / label / col copied, ent[e] = {sample of e, x
 // bits} rebuilt from row_ptr and the compact values (the explode of Model.scala:148-153)
-void launch_explode(const int64_t* row_ptr_in, const double* label_in, const int32_t* xoff, const uint32_t* col_in,
-                    const float* x_in, int64_t B, int64_t N, int64_t* row_ptr, double* label, uint32_t* col, uint2* ent,
-                    float* xs, hipStream_t st);
-// fm_batch_layout_splits: the uploaded CSR image of the source (as launch_explode takes it) -> dst
+void launch_explode(const CsrImage& in, int64_t B, int64_t N, BatchDev& dst, hipStream_t st);
+// fm_batch_layout_splits: the device image of the source (as launch_explode takes it) -> dst
 // row s = source row order[s] (device order[B]), laid out split after split: row_ptr_in[B + 1]
 // (device) is the result's row_ptr, computed by the host; split_rows [n_splits + 1] (device);
 // split_rp [B + n_splits] and the entries' sample indices as launch_split_rebase leaves them
-void launch_layout_splits(const int64_t* src_row_ptr, const double* src_label, const int32_t* xoff, const uint32_t* col_in,
-                          const float* x_in, const int64_t* order, const int64_t* row_ptr_in, const int64_t* split_rows,
+void launch_layout_splits(const CsrImage& src, const int64_t* order, const int64_t* row_ptr_in, const int64_t* split_rows,
                           int32_t n_splits, int64_t B, BatchDev& dst, int64_t* split_rp, hipStream_t st);
 
 // ---------------------------------------------------------------- ranking (fm_rank.hip)

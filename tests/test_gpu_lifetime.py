@@ -65,8 +65,14 @@ def owned(kind, ids):
     return ids[ids % 3 == 1] if kind == "shard1of3" else ids
 
 
+def cycle_split_rows(n):
+    return np.array([0, n // 3, n // 3, n - 7, n], dtype=np.int64)  # an empty split among them
+
+
 class Env:
-    """One context of a kind with the whole table loaded, a device batch, and the calls it answers."""
+    """One context of a kind with the whole table loaded, a device batch, a split dataset of the same
+    rows with two reusable handles (a selection and a view: what fit refills every iteration), and the
+    calls it answers."""
 
     def __init__(self, kind, k):
         self.kind, self.k = kind, k
@@ -76,6 +82,11 @@ class Env:
         ctx.load_tables(ids, w, V)
         self.hb = host(csr)
         self.db = ctx.batch(self.hb)
+        self.data = ctx.batch_splits(self.hb, cycle_split_rows(csr.n_rows))
+        self.rows = np.arange(0, csr.n_rows, 2, dtype=np.int64)  # a fixed 100-row list
+        self.sel = ctx.batch_from_rows(self.db, self.rows)
+        self.view = ctx.split_view(self.data, 0)
+        self.n_views = 0
         self.own = owned(kind, ids)
         self.t = 0
         rng = np.random.default_rng(5)
@@ -83,8 +94,18 @@ class Env:
         self.vecs = rng.normal(size=(1000, k))
 
     def close(self):
-        self.db.close()
+        for b in (self.sel, self.view, self.data, self.db):  # views before the dataset they borrow from
+            b.close()
         self.ctx.close()
+
+    def split_view_into(self):
+        self.n_views += 1
+        self.ctx.split_view(self.data, (0, 2)[self.n_views % 2], into=self.view)  # the two large splits in turn
+
+    def view_selection_cycle(self):
+        """A selection becomes a view and a selection again: the call ends in the state it started in."""
+        self.ctx.split_view(self.data, 2, into=self.sel)
+        self.ctx.batch_from_rows(self.db, self.rows, into=self.sel)
 
     def profiled_steps(self):
         self.ctx.profile_enable(True)
@@ -108,6 +129,9 @@ class Env:
             "init_from_batch": lambda: ctx.init_from_batch(self.db),
             "vector_sum_by_key": lambda: ctx.vector_sum_by_key(self.keys, self.vecs),
             "loss_history": lambda: ctx.loss_history(),
+            "from_rows_into": lambda: ctx.batch_from_rows(self.db, self.rows, into=self.sel),
+            "split_view_into": self.split_view_into,
+            "view_selection_cycle": self.view_selection_cycle,
         }
         if self.kind != "shard1of3":
             c["predict"] = lambda: ctx.predict(self.hb, -1.0, 2.0)
@@ -121,7 +145,7 @@ class Env:
 
 CALLS = ["export_rows", "export_tables", "num_present", "load_tables", "init_random", "init_random_range",
          "init_from_batch", "predict", "predict_batch", "loss_grad", "loss_grad_initial_sd", "vector_sum_by_key",
-         "loss_history", "profile_read"]
+         "loss_history", "profile_read", "from_rows_into", "split_view_into", "view_selection_cycle"]
 
 
 @pytest.fixture(scope="module")
@@ -275,7 +299,7 @@ def _cycle(kind, ctx_first):
     ctx = make_ctx(kind)
     ctx.load_tables(ids, w, V)
     n = csr.n_rows
-    split_rows = np.array([0, n // 3, n // 3, n - 7, n], dtype=np.int64)  # an empty split among them
+    split_rows = cycle_split_rows(n)
     order = np.random.default_rng(1).permutation(n)
     plain = ctx.batch(hb)
     data = ctx.batch_splits(hb, split_rows)
