@@ -308,7 +308,7 @@ void reserve_work(fm_ctx* ctx, int64_t B, int64_t N) {
   const int64_t nranges = (N + 255) / 256;  // update waves (fm_update.hip, kWaveEnt)
   w.part.ensure_slack(sizeof(double) * (size_t)std::max<int64_t>(nranges, 1) * 2 * (ctx->kp + 2));
   w.ucnt.ensure_slack(sizeof(uint32_t) * (size_t)std::max<int64_t>((N + 1023) / 1024, 1));
-  w.loss_part.ensure(sizeof(double) * 2 * 256 * 8);
+  w.loss_part.ensure(sizeof(double2) * kLossPartBlocks);
 }
 
 }  // namespace fmhip

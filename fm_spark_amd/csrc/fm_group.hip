@@ -95,11 +95,6 @@ __global__ void k_copy_list(CopyList cl) {
   }
 }
 
-inline unsigned grid_of(int64_t n) {
-  int64_t g = (n + kBlock - 1) / kBlock;
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(g, 256 * 16));
-}
-
 }  // namespace
 
 struct Rank {
@@ -945,7 +940,7 @@ int step_replicated(fm_ctx* ctx, Group& g, GroupBatch& gb, int32_t t, double ste
     for (int l = 1; l < L; ++l) {
       FM_HIP_CHECK(hipSetDevice(r0.device));
       FM_HIP_CHECK(hipMemcpyAsync(r0.gtmp.p, g.ranks[l].grad.p, sizeof(float) * n, hipMemcpyDefault, r0.m->stream));
-      hipLaunchKernelGGL(k_add_f32, dim3(grid_of(n)), dim3(kBlock), 0, r0.m->stream, r0.grad.as<float>(),
+      hipLaunchKernelGGL(k_add_f32, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, r0.m->stream, r0.grad.as<float>(),
                          r0.gtmp.as<float>(), n);
       FM_HIP_CHECK(hipGetLastError());
     }
@@ -1461,7 +1456,7 @@ int group_init_from_batch(fm_ctx* ctx, fm_batch* b, int64_t* n_present) {
         FM_HIP_CHECK(hipStreamSynchronize(r.m->side));
         DevBuf ids;
         ids.ensure(sizeof(uint32_t) * n_in);
-        hipLaunchKernelGGL(k_slots_to_ids, dim3(grid_of(n_in)), dim3(kBlock), 0, r.m->stream,
+        hipLaunchKernelGGL(k_slots_to_ids, dim3(grid_for(n_in, kBlock)), dim3(kBlock), 0, r.m->stream,
                            static_cast<const uint32_t*>(p.in_slot), n_in, (uint32_t)g.R, (uint32_t)r.global,
                            ids.as<uint32_t>());
         launch_init_entries(r.m->view(), ids.as<uint32_t>(), n_in, r.m->cfg.seed, r.m->cfg.init_sd, r.m->epoch,

@@ -291,6 +291,9 @@ void launch_segment_update(const TableView& T, int64_t N, const SegSource& src, 
 // the number of touched rows -> *n_touched (device, fp64 stats slot), through per-block counts in
 // blk_touched[kReplApplyBlocks]
 constexpr int kReplApplyBlocks = 256 * 16;
+// The most blocks that leave a loss partial (StepWork::loss_part is reserved for this many): the
+// grid cap of the sharded combine.  The single-table forward sizes loss_part by its own grid.
+constexpr int kLossPartBlocks = 256 * 8;
 void launch_repl_apply(const TableView& T, const float* grad, const StepParams& p, uint32_t* blk_touched,
                        double* n_touched, hipStream_t st);
 

@@ -282,164 +282,210 @@ __global__ __launch_bounds__(kBlock) void k_pair_table(const uint2* __restrict__
   }
 }
 
-// ------------------------------------------------------------------ requester: combine
+// ------------------------------------------------------------------ requester: combine, predict
 // The partial direction's element type W: float (FM_WIRE_FP32) or double (FM_WIRE_FP64).
 template <typename W>
 using wire2 = std::conditional_t<std::is_same<W, double>::value, double2, float2>;
-// quad q of a partial row added to the lane's four fp64 column sums (fp64 words: two 16-B halves)
-__device__ __forceinline__ void add_quad(const float* __restrict__ row, int q, double& a0, double& a1, double& a2,
-                                         double& a3) {
-  const float4 t = reinterpret_cast<const float4*>(row)[q];
-  a0 += (double)t.x; a1 += (double)t.y; a2 += (double)t.z; a3 += (double)t.w;
+
+// What a requester kernel reads of the partials.  Wire layout (structure of arrays): vec [pair][kp]
+// sum v*x, sc [pair] {sum v^2 x^2, sum w x}; the sample's pair at owner o is poff[o] + pairidx[s * R + o]
+// (-1: none).
+template <typename W>
+struct ReqIn {
+  const int64_t* poff;
+  const W* vec;
+  const wire2<W>* sc;
+  int kp;
+  double w0;
+};
+
+// The two ways of reaching a sample's rows in the owners' blocks.
+//
+// Owner by owner (OwnerWalk, any R up to kMaxR): guarded loads, one per owner, each waited out its
+// round trip before the next: 2R + R round trips per sample and quad.
+//
+// Slots in registers (int64_t pj[OW], R <= OW owners; -1: no pair): every owner's loads of a pass
+// are issued before any is used (clamped owner indices; a pair the sample lacks reads poff's first
+// bytes and is masked out; poff is allocated at least 32 B so every masked load, 16 B at the most,
+// stays inside it).  W = double: an owner's quad is loaded as two double2 halves, one half of every
+// owner at a time, so the loads in flight take the registers the fp32 quads take.  pj stays a local
+// array of the kernel and the helpers are free functions over a reference to it (as members of a
+// struct holding pj the same code took up to 26 VGPRs more and a wave per SIMD: DESIGN.md §5).
+struct OwnerWalk {
+  const int32_t* pi;  // the sample's row of pairidx
+  const int64_t* poff;
+  int R;
+};
+
+template <int OW>
+__device__ __forceinline__ void load_slots(int64_t (&pj)[OW], const int32_t* pi, const int64_t* poff, int R) {
+  int32_t ix[OW];
+#pragma unroll
+  for (int o = 0; o < OW; ++o) {
+    const int oc = o < R ? o : R - 1;
+    ix[o] = pi[oc];
+    pj[o] = poff[oc];
+  }
+#pragma unroll
+  for (int o = 0; o < OW; ++o) pj[o] = o < R && ix[o] >= 0 ? pj[o] + ix[o] : -1;
 }
-__device__ __forceinline__ void add_quad(const double* __restrict__ row, int q, double& a0, double& a1, double& a2,
-                                         double& a3) {
-  const double2 lo = reinterpret_cast<const double2*>(row)[2 * q], hi = reinterpret_cast<const double2*>(row)[2 * q + 1];
-  a0 += lo.x; a1 += lo.y; a2 += hi.x; a3 += hi.y;
+
+// f(pair) for every pair of the sample, in owner order
+template <typename F>
+__device__ __forceinline__ void for_each_pair(const OwnerWalk& s, F&& f) {
+  for (int o = 0; o < s.R; ++o) {
+    const int32_t ix = s.pi[o];
+    if (ix >= 0) f(s.poff[o] + ix);
+  }
 }
-// Team of GS lanes per sample (one quad each): the owners' partials summed in owner order
-// in fp64 -> S = vfxiSum, yhat = 0.5 (|S|^2 - sum v^2 x^2) + sum w x + w0
-// (FactorizationMachinesModel.scala:221, :260-262), the loss partial (:230), and the S rows
-// sent back to every owner holding entries of the sample.  Wire layout (structure of arrays):
-// part_vec / s_vec [pair][kp], part_sc / s_sc [pair] float2 ({sum v^2 x^2, sum w x} / {yhat, y}).
-// OW > 0 (R <= OW owners): the sample's pair slots live in registers and every owner's loads of a
-// pass are issued before any is used (clamped owner indices; a pair the sample lacks reads poff's
-// first bytes and is masked out; poff is allocated at least 32 B so every masked load, 16 B at the
-// most, stays inside it) -- as guarded loads, one per owner, each waited out its round trip
-// before the next: 2R + R round trips per sample.  OW = 0: any R up to kMaxR, owner by owner.
-// W = double: an owner's quad is loaded as two double2 halves, one half of every owner at a time, so
-// the loads in flight take the registers the fp32 quads take.
+template <int OW, typename F>
+__device__ __forceinline__ void for_each_pair(const int64_t (&pj)[OW], F&& f) {
+#pragma unroll
+  for (int o = 0; o < OW; ++o)
+    if (pj[o] >= 0) f(pj[o]);
+}
+
+// The sample's scalar sums over its owners in owner order, fp64, and n: its pairs (kCombine), or its
+// present entries (pcnt [pair]: the owner's present rows among the pair's entries).
+template <bool kCombine, typename W>
+__device__ __forceinline__ void sum_scalars(const OwnerWalk& s, const ReqIn<W>& in, const uint32_t* pcnt, double& vv,
+                                            double& wx, uint32_t& n) {
+  for_each_pair(s, [&](int64_t p) {
+    const wire2<W> t = in.sc[p];
+    vv += (double)t.x;
+    wx += (double)t.y;
+    n += kCombine ? 1u : pcnt[p];
+  });
+}
+template <bool kCombine, int OW, typename W>
+__device__ __forceinline__ void sum_scalars(const int64_t (&pj)[OW], const ReqIn<W>& in, const uint32_t*, double& vv,
+                                            double& wx, uint32_t& n) {
+  wire2<W> t[OW];
+#pragma unroll
+  for (int o = 0; o < OW; ++o) t[o] = *(pj[o] >= 0 ? in.sc + pj[o] : reinterpret_cast<const wire2<W>*>(in.poff));
+#pragma unroll
+  for (int o = 0; o < OW; ++o) {
+    vv += pj[o] >= 0 ? (double)t[o].x : 0.0;
+    wx += pj[o] >= 0 ? (double)t[o].y : 0.0;
+    n += pj[o] >= 0;
+  }
+}
+
+// Quad q of the sample's partial rows added to the lane's four fp64 column sums, owner order
+// (fp64 words: two 16-B halves).
+template <typename W>
+__device__ __forceinline__ void sum_quad(const OwnerWalk& s, const ReqIn<W>& in, int q, double& a0, double& a1,
+                                         double& a2, double& a3) {
+  for_each_pair(s, [&](int64_t p) {
+    const W* row = in.vec + p * in.kp;
+    if constexpr (std::is_same<W, double>::value) {
+      const double2 lo = reinterpret_cast<const double2*>(row)[2 * q], hi = reinterpret_cast<const double2*>(row)[2 * q + 1];
+      a0 += lo.x; a1 += lo.y; a2 += hi.x; a3 += hi.y;
+    } else {
+      const float4 t = reinterpret_cast<const float4*>(row)[q];
+      a0 += (double)t.x; a1 += (double)t.y; a2 += (double)t.z; a3 += (double)t.w;
+    }
+  });
+}
+template <int OW, typename W>
+__device__ __forceinline__ void sum_quad(const int64_t (&pj)[OW], const ReqIn<W>& in, int q, double& a0, double& a1,
+                                         double& a2, double& a3) {
+  if constexpr (std::is_same<W, double>::value) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {  // columns 4q + 2h, 4q + 2h + 1 of every owner, owner order
+      double2 tv[OW];
+#pragma unroll
+      for (int o = 0; o < OW; ++o)
+        tv[o] = pj[o] >= 0 ? reinterpret_cast<const double2*>(in.vec + pj[o] * in.kp)[2 * q + h]
+                           : *reinterpret_cast<const double2*>(in.poff);
+      double b0 = 0.0, b1 = 0.0;
+#pragma unroll
+      for (int o = 0; o < OW; ++o) {
+        const bool ok = pj[o] >= 0;
+        b0 += ok ? tv[o].x : 0.0; b1 += ok ? tv[o].y : 0.0;
+      }
+      if (h == 0) { a0 = b0; a1 = b1; } else { a2 = b0; a3 = b1; }
+    }
+  } else {
+    float4 tv[OW];
+#pragma unroll
+    for (int o = 0; o < OW; ++o)
+      tv[o] = pj[o] >= 0 ? reinterpret_cast<const float4*>(in.vec + pj[o] * in.kp)[q]
+                         : *reinterpret_cast<const float4*>(in.poff);
+#pragma unroll
+    for (int o = 0; o < OW; ++o) {
+      const bool ok = pj[o] >= 0;
+      a0 += ok ? (double)tv[o].x : 0.0; a1 += ok ? (double)tv[o].y : 0.0;
+      a2 += ok ? (double)tv[o].z : 0.0; a3 += ok ? (double)tv[o].w : 0.0;
+    }
+  }
+}
+
+// One sample of a team of GS lanes (lane g: quads g, g + GS, ...): the owners' partials summed in
+// owner order in fp64 -> S = vfxiSum, yhat = 0.5 (|S|^2 - sum v^2 x^2) + sum w x + w0
+// (FactorizationMachinesModel.scala:221, :260-262), returned to every lane of the team.
+// kCombine: S, rounded, goes to s_vec [pair][kp] for every pair of the sample.  n: see sum_scalars.
+template <int GS, bool kCombine, typename W, typename Slots>
+__device__ __forceinline__ double sample_yhat(const Slots& slots, const ReqIn<W>& in, int g, const uint32_t* pcnt,
+                                              float* s_vec, uint32_t& n) {
+  const int nq = in.kp >> 2;
+  const double w0 = in.w0;
+  double vv = 0.0, wx = 0.0, ss = 0.0;
+  sum_scalars<kCombine>(slots, in, pcnt, vv, wx, n);
+  for (int qc = 0; qc < nq; qc += GS) {
+    const int q = qc + g;
+    if (q >= nq) break;  // (q grows with qc)
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    sum_quad(slots, in, q, a0, a1, a2, a3);
+    ss += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
+    if constexpr (kCombine) {
+      const float4 sq = make_float4((float)a0, (float)a1, (float)a2, (float)a3);
+      for_each_pair(slots, [&](int64_t p) { reinterpret_cast<float4*>(s_vec + p * in.kp)[q] = sq; });
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < GS; o <<= 1) ss += __shfl_xor(ss, o);
+  return 0.5 * (ss - vv) + wx + w0;
+}
+
+// The combine's sample: S rows and {r, yhat} (r = yhat - y formed in fp64, then rounded) sent back to
+// every owner holding entries of the sample; s_sc [pair] float2.  A sample with no pair is not
+// counted in the loss (:230).
+template <int GS, typename W, typename Slots>
+__device__ __forceinline__ void combine_sample(const Slots& slots, const ReqIn<W>& in, int g, const double* y, float* s_vec,
+                                               float2* s_sc, double& loss_acc, double& nloss) {
+  uint32_t n = 0;
+  const double yhat = sample_yhat<GS, true>(slots, in, g, nullptr, s_vec, n);
+  if (g == 0) {
+    const double d = yhat - *y;
+    for_each_pair(slots, [&](int64_t p) { s_sc[p] = make_float2((float)d, (float)yhat); });  // {r, yhat}
+    if (n) {
+      loss_acc += d * d;
+      nloss += 1.0;
+    }
+  }
+}
+
+// OW > 0 (R <= OW owners): the sample's pair slots in registers; OW = 0: owner by owner.
 template <int GS, int OW, typename W>
 __global__ __launch_bounds__(kBlock) void k_shard_combine(const int32_t* __restrict__ pairidx,
                                                           const int64_t* __restrict__ poff, int R, int64_t B,
                                                           const W* __restrict__ part_vec,
-                                                          const wire2<W>* __restrict__ part_sc,
-                                                          const double* __restrict__ label, int kp, double w0,
-                                                          float* __restrict__ s_vec, float2* __restrict__ s_sc,
-                                                          double2* __restrict__ loss_part) {
+                                                          const wire2<W>* __restrict__ part_sc, int kp, double w0,
+                                                          const double* __restrict__ label, float* __restrict__ s_vec,
+                                                          float2* __restrict__ s_sc, double2* __restrict__ loss_part) {
   constexpr int TPB = kBlock / GS;
   const int tid = threadIdx.x, g = tid % GS;
-  const int nq = kp >> 2;
+  const ReqIn<W> in{poff, part_vec, part_sc, kp, w0};
   double loss_acc = 0.0, nloss = 0.0;
   for (int64_t s = (int64_t)blockIdx.x * TPB + tid / GS; s < B; s += (int64_t)gridDim.x * TPB) {
     const int32_t* pi = pairidx + s * R;
-    double vv = 0.0, wx = 0.0, ss = 0.0;
-    bool any = false;
     if constexpr (OW > 0) {
-      int32_t ix[OW];
-      int64_t pj[OW];  // the sample's pair slot in owner o's block, -1: none
-#pragma unroll
-      for (int o = 0; o < OW; ++o) {
-        const int oc = o < R ? o : R - 1;
-        ix[o] = pi[oc];
-        pj[o] = poff[oc];
-      }
-      wire2<W> t[OW];
-#pragma unroll
-      for (int o = 0; o < OW; ++o) {
-        pj[o] = o < R && ix[o] >= 0 ? pj[o] + ix[o] : -1;
-        t[o] = *(pj[o] >= 0 ? part_sc + pj[o] : reinterpret_cast<const wire2<W>*>(poff));
-      }
-#pragma unroll
-      for (int o = 0; o < OW; ++o) {  // owner order, as the loop below
-        vv += pj[o] >= 0 ? (double)t[o].x : 0.0;
-        wx += pj[o] >= 0 ? (double)t[o].y : 0.0;
-        any = any || pj[o] >= 0;
-      }
-      for (int qc = 0; qc < nq; qc += GS) {
-        const int q = qc + g;
-        if (q >= nq) break;  // (q grows with qc)
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        if constexpr (std::is_same<W, double>::value) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {  // columns 4q + 2h, 4q + 2h + 1 of every owner, owner order
-            double2 tv[OW];
-#pragma unroll
-            for (int o = 0; o < OW; ++o)
-              tv[o] = pj[o] >= 0 ? reinterpret_cast<const double2*>(part_vec + pj[o] * kp)[2 * q + h]
-                                 : *reinterpret_cast<const double2*>(poff);
-            double b0 = 0.0, b1 = 0.0;
-#pragma unroll
-            for (int o = 0; o < OW; ++o) {
-              const bool ok = pj[o] >= 0;
-              b0 += ok ? tv[o].x : 0.0; b1 += ok ? tv[o].y : 0.0;
-            }
-            if (h == 0) { a0 = b0; a1 = b1; } else { a2 = b0; a3 = b1; }
-          }
-        } else {
-          float4 tv[OW];
-#pragma unroll
-          for (int o = 0; o < OW; ++o)
-            tv[o] = pj[o] >= 0 ? reinterpret_cast<const float4*>(part_vec + pj[o] * kp)[q]
-                               : *reinterpret_cast<const float4*>(poff);
-#pragma unroll
-          for (int o = 0; o < OW; ++o) {
-            const bool ok = pj[o] >= 0;
-            a0 += ok ? (double)tv[o].x : 0.0; a1 += ok ? (double)tv[o].y : 0.0;
-            a2 += ok ? (double)tv[o].z : 0.0; a3 += ok ? (double)tv[o].w : 0.0;
-          }
-        }
-        ss += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-        const float4 sq = make_float4((float)a0, (float)a1, (float)a2, (float)a3);
-#pragma unroll
-        for (int o = 0; o < OW; ++o)
-          if (pj[o] >= 0) reinterpret_cast<float4*>(s_vec + pj[o] * kp)[q] = sq;
-      }
-#pragma unroll
-      for (int o = 1; o < GS; o <<= 1) ss += __shfl_xor(ss, o);
-      const double yhat = 0.5 * (ss - vv) + wx + w0;
-      if (g == 0) {
-        const double y = label[s];
-#pragma unroll
-        for (int o = 0; o < OW; ++o)
-          if (pj[o] >= 0) s_sc[pj[o]] = make_float2((float)(yhat - y), (float)yhat);  // {r, yhat}
-        if (any) {
-          const double d = yhat - y;
-          loss_acc += d * d;
-          nloss += 1.0;
-        }
-      }
-      continue;
-    }
-    for (int o = 0; o < R; ++o) {
-      const int32_t ix = pi[o];
-      if (ix >= 0) {
-        const wire2<W> t = part_sc[poff[o] + ix];
-        vv += (double)t.x;
-        wx += (double)t.y;
-        any = true;
-      }
-    }
-    for (int qc = 0; qc < nq; qc += GS) {
-      const int q = qc + g;
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-      if (q < nq) {
-        for (int o = 0; o < R; ++o) {
-          const int32_t ix = pi[o];
-          if (ix >= 0) add_quad(part_vec + (poff[o] + ix) * kp, q, a0, a1, a2, a3);
-        }
-        ss += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-        const float4 sq = make_float4((float)a0, (float)a1, (float)a2, (float)a3);
-        for (int o = 0; o < R; ++o) {
-          const int32_t ix = pi[o];
-          if (ix >= 0) reinterpret_cast<float4*>(s_vec + (poff[o] + ix) * kp)[q] = sq;
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < GS; o <<= 1) ss += __shfl_xor(ss, o);
-    const double yhat = 0.5 * (ss - vv) + wx + w0;
-    if (g == 0) {
-      const double y = label[s];
-      for (int o = 0; o < R; ++o) {
-        const int32_t ix = pi[o];
-        if (ix >= 0) s_sc[poff[o] + ix] = make_float2((float)(yhat - y), (float)yhat);  // {r, yhat}
-      }
-      if (any) {
-        const double d = yhat - y;
-        loss_acc += d * d;
-        nloss += 1.0;
-      }
+      int64_t pj[OW];
+      load_slots(pj, pi, poff, R);
+      combine_sample<GS>(pj, in, g, label + s, s_vec, s_sc, loss_acc, nloss);
+    } else {
+      combine_sample<GS>(OwnerWalk{pi, poff, R}, in, g, label + s, s_vec, s_sc, loss_acc, nloss);
     }
   }
   block_loss_partial(loss_acc, nloss, loss_part);
@@ -453,47 +499,17 @@ template <int GS, typename W>
 __global__ __launch_bounds__(kBlock) void k_shard_predict(const int32_t* __restrict__ pairidx,
                                                           const int64_t* __restrict__ poff, int R, int64_t B,
                                                           const W* __restrict__ part_vec,
-                                                          const wire2<W>* __restrict__ part_sc,
-                                                          const uint32_t* __restrict__ pcnt, int kp, double w0,
-                                                          double lo, double hi, double* __restrict__ pred) {
+                                                          const wire2<W>* __restrict__ part_sc, int kp, double w0,
+                                                          const uint32_t* __restrict__ pcnt, double lo, double hi,
+                                                          double* __restrict__ pred) {
   constexpr int TPB = kBlock / GS;
   const int tid = threadIdx.x, g = tid % GS;
-  const int nq = kp >> 2;
+  const ReqIn<W> in{poff, part_vec, part_sc, kp, w0};
   for (int64_t s = (int64_t)blockIdx.x * TPB + tid / GS; s < B; s += (int64_t)gridDim.x * TPB) {
-    const int32_t* pi = pairidx + s * R;
-    double vv = 0.0, wx = 0.0, ss = 0.0;
     uint32_t cnt = 0;
-    for (int o = 0; o < R; ++o) {
-      const int32_t ix = pi[o];
-      if (ix >= 0) {
-        const wire2<W> t = part_sc[poff[o] + ix];
-        vv += (double)t.x;
-        wx += (double)t.y;
-        cnt += pcnt[poff[o] + ix];
-      }
-    }
-    for (int qc = 0; qc < nq; qc += GS) {
-      const int q = qc + g;
-      if (q >= nq) continue;
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-      for (int o = 0; o < R; ++o) {
-        const int32_t ix = pi[o];
-        if (ix >= 0) add_quad(part_vec + (poff[o] + ix) * kp, q, a0, a1, a2, a3);
-      }
-      ss += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-    }
-#pragma unroll
-    for (int o = 1; o < GS; o <<= 1) ss += __shfl_xor(ss, o);
-    const double yhat = 0.5 * (ss - vv) + wx + w0;
+    const double yhat = sample_yhat<GS, false>(OwnerWalk{pairidx + s * R, poff, R}, in, g, pcnt, nullptr, cnt);
     if (g == 0) pred[s] = cnt == 0 ? w0 : fmin(fmax(yhat, lo), hi);
   }
-}
-
-inline unsigned blocks_for(int64_t threads, int64_t cap = 256 * 16) {
-  int64_t b = (threads + kBlock - 1) / kBlock;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (unsigned)b;
 }
 
 inline int team_for(int nq) {
@@ -526,33 +542,6 @@ void shard_owner_partials(fm_ctx* ctx, fm_batch* b, void* partials_out, uint32_t
 using namespace fmhip;
 
 namespace {
-
-// R <= 8: the owners' pair slots in registers (OW = 8), else owner by owner
-template <typename W>
-void launch_shard_combine(int GS, dim3 grid, hipStream_t st, const int32_t* pi, const int64_t* poff, int R, int64_t B,
-                          const void* partials_in, int64_t Ps, const double* lab, int kp, double w0, float* so,
-                          float2* ssc, double2* lp) {
-  const W* pin = reinterpret_cast<const W*>(partials_in);
-  const wire2<W>* psc = reinterpret_cast<const wire2<W>*>(pin ? pin + Ps * kp : nullptr);
-  const dim3 blk(kBlock);
-  if (R <= 8) {
-    switch (GS) {
-      case 1: hipLaunchKernelGGL((k_shard_combine<1, 8, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-      case 2: hipLaunchKernelGGL((k_shard_combine<2, 8, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-      case 4: hipLaunchKernelGGL((k_shard_combine<4, 8, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-      case 8: hipLaunchKernelGGL((k_shard_combine<8, 8, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-      default: hipLaunchKernelGGL((k_shard_combine<16, 8, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-    }
-  } else {
-    switch (GS) {
-      case 1: hipLaunchKernelGGL((k_shard_combine<1, 0, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-      case 2: hipLaunchKernelGGL((k_shard_combine<2, 0, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-      case 4: hipLaunchKernelGGL((k_shard_combine<4, 0, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-      case 8: hipLaunchKernelGGL((k_shard_combine<8, 0, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-      default: hipLaunchKernelGGL((k_shard_combine<16, 0, W>), grid, blk, 0, st, pi, poff, R, B, pin, psc, lab, kp, w0, so, ssc, lp); break;
-    }
-  }
-}
 
 // Owner-side step parameters (SGD.scala:121-124 with the global miniBatchSize).
 StepParams shard_params(fm_ctx* ctx, int32_t t, double step_size, double reg_param, int64_t global_rows) {
@@ -587,6 +576,74 @@ ShardBatchState& shard_state(fm_ctx* ctx, fm_batch* b) {
   return *b->sh;
 }
 
+// ------------------------------------------------------------------ requester: launch
+constexpr int kSlotRegs = 8;  // up to this many owners the combine keeps the sample's pair slots in registers
+
+// The requester kernel of a wire and team width: the combine (slots in registers or owner by
+// owner) or the predict (owner by owner).  For one W and kind every instantiation has one type.
+template <int GS, typename W, bool kPredict>
+auto requester_kernel_g(int R) {
+  if constexpr (kPredict) return &k_shard_predict<GS, W>;
+  else return R <= kSlotRegs ? &k_shard_combine<GS, kSlotRegs, W> : &k_shard_combine<GS, 0, W>;
+}
+template <typename W, bool kPredict>
+auto requester_kernel(int GS, int R) {
+  switch (GS) {
+    case 1: return requester_kernel_g<1, W, kPredict>(R);
+    case 2: return requester_kernel_g<2, W, kPredict>(R);
+    case 4: return requester_kernel_g<4, W, kPredict>(R);
+    case 8: return requester_kernel_g<8, W, kPredict>(R);
+    default: return requester_kernel_g<16, W, kPredict>(R);
+  }
+}
+
+// A wire buffer is [P][kp] vectors, then [P] scalar pairs.
+template <typename Sc, typename V>
+Sc* wire_scalars(V* vec, int64_t P, int kp) {
+  return reinterpret_cast<Sc*>(vec ? vec + P * kp : nullptr);
+}
+
+// What the combine and the predict take from a routed batch: its pairs over all owners, the team
+// width and the grid (one team per sample, at most kLossPartBlocks blocks).
+struct ReqPlan {
+  int R, kp, GS;
+  int64_t B, Ps;
+  unsigned blocks;
+  const int32_t* pi;
+  const int64_t* poff;
+};
+
+ReqPlan requester_plan(fm_ctx* ctx, fm_batch* b, const ShardBatchState& S) {
+  FM_REQUIRE(S.route_nnz == b->dev.nnz && (int)S.pairs_out.size() == ctx->cfg.shard_count,
+             "fm_shard_route must run on this batch first");
+  ReqPlan q{};
+  q.R = ctx->cfg.shard_count;
+  q.kp = ctx->kp;
+  q.GS = team_for(q.kp / 4);
+  q.B = b->dev.n_rows;
+  for (int o = 0; o < q.R; ++o) q.Ps += S.pairs_out[o];
+  q.blocks = grid_for(q.B, kBlock / q.GS, kLossPartBlocks);
+  q.pi = S.pairidx.as<int32_t>();
+  q.poff = S.poff.as<int64_t>();
+  return q;
+}
+
+// The combine or predict kernel of the context's wire on the main stream; tail: the kernel's own
+// arguments after the ones both take.
+template <bool kPredict, typename... Tail>
+void launch_requester(fm_ctx* ctx, const ReqPlan& q, const void* partials_in, Tail... tail) {
+  auto go = [&](auto word) {
+    using W = decltype(word);
+    const W* vec = reinterpret_cast<const W*>(partials_in);
+    auto kern = requester_kernel<W, kPredict>(q.GS, q.R);
+    hipLaunchKernelGGL(kern, dim3(q.blocks), dim3(kBlock), 0, ctx->stream, q.pi, q.poff, q.R, q.B, vec,
+                       wire_scalars<const wire2<W>>(vec, q.Ps, q.kp), q.kp, ctx->cfg.w0, tail...);
+  };
+  if (ctx->cfg.wire == FM_WIRE_FP64) go(double{});
+  else go(float{});
+  FM_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
@@ -613,92 +670,88 @@ namespace fmhip {
 // then [R] entries per owner, uint64): a multi-GPU context gathers every rank's counts on the
 // device and reads them back once for the whole job (fm_group.hip prefetch).
 void shard_route_launch(fm_ctx* ctx, fm_batch* b, void* send_slot, void* send_ent, hipStream_t st) {
-  {
-    ShardBatchState& S = shard_state(ctx, b);
-    const int R = ctx->cfg.shard_count;
-    FM_REQUIRE(R <= kMaxR, "the owner-computes sharded step supports at most 64 ranks");
-    const int64_t B = b->dev.n_rows, N = b->dev.nnz;
-    FM_REQUIRE(N == 0 || (send_slot && send_ent), "null send buffer");
-    if (!st) st = ctx->side;
-    // the batch's previous iteration may still read its requester state on the main stream; a batch
-    // refilled by fm_batch_from_rows is routed once its gather is done
-    FM_HIP_CHECK(hipStreamWaitEvent(st, S.last_use, 0));
-    wait_built(b, st);
-    hipEvent_t e0 = ctx->prof_begin(st);
-    const int64_t ntiles = std::max<int64_t>((B + kBlock - 1) / kBlock, 1);
-    ctx->sh_okey.ensure(sizeof(uint32_t) * std::max<int64_t>(N, 4) + 16);
-    ctx->sh_mask.ensure(sizeof(uint64_t) * std::max<int64_t>(B, 1));
-    ctx->sh_tcnt.ensure(sizeof(uint32_t) * R * ntiles);
-    ctx->sh_tot.ensure(sizeof(unsigned long long) * 2 * R);
-    S.pairidx.ensure(sizeof(int32_t) * std::max<int64_t>(B, 1) * R);
-    // at least 32 B: the combine's masked loads read poff's first bytes (k_shard_combine, OW > 0)
-    S.poff.ensure(sizeof(int64_t) * std::max(R + 1, 4));
-    unsigned long long* tot = ctx->sh_tot.as<unsigned long long>();  // [R] pairs, [R] entries
-    FM_HIP_CHECK(hipMemsetAsync(tot, 0, sizeof(unsigned long long) * 2 * R, st));
-    const uint64_t F = (uint64_t)ctx->cfg.num_features;
-    const bool drop = b->max_id >= (int64_t)F;  // a predict batch with ids outside the model
-    if (B > 0) {
-      hipLaunchKernelGGL(k_sample_mask, dim3(blocks_for(B * kTeamR)), dim3(kBlock), 0, st, b->dev.row_ptr.as<int64_t>(),
-                         b->dev.col.as<uint32_t>(), B, (uint32_t)R, F, ctx->sh_mask.as<uint64_t>(), tot + R);
-      hipLaunchKernelGGL(k_pair_count, dim3((unsigned)ntiles), dim3(kBlock), 0, st, ctx->sh_mask.as<uint64_t>(), B,
-                         R, ntiles, ctx->sh_tcnt.as<uint32_t>());
-      hipLaunchKernelGGL(k_rows_scan, dim3((unsigned)R), dim3(kBlock), 0, st, ctx->sh_tcnt.as<uint32_t>(), ntiles,
-                         tot);
-      hipLaunchKernelGGL(k_pair_index, dim3((unsigned)ntiles), dim3(kBlock), 0, st, ctx->sh_mask.as<uint64_t>(), B,
-                         R, ntiles, ctx->sh_tcnt.as<uint32_t>(), S.pairidx.as<int32_t>());
-    }
-    hipLaunchKernelGGL(k_owner_offsets, dim3(1), dim3(64), 0, st, tot, R, S.poff.as<int64_t>());
-    if (N > 0) {
-      // wire keys owner << sb | slot with payload {pair index within the owner's block, x}; one
-      // stable pass over the owner bits partitions them (CSR order kept inside each owner).  sb
-      // must hold the largest slot of ANY owner (owner 0 has the most rows), the same on every rank
-      const int sb = bits_for(std::max<int64_t>((ctx->cfg.num_features - 1) / R, 1));
-      const int ob = bits_for(drop ? R : R - 1);
-      FM_REQUIRE(sb + ob <= 32, "route key does not fit 32 bits");
-      if (R == 1 && !drop) {
-        // one owner: CSR order is already the owner order and the key is the slot -- the keys and
-        // payloads go straight to the send buffers, no partition pass
-        hipLaunchKernelGGL(k_route_keys, dim3(blocks_for(N)), dim3(kBlock), 0, st, b->dev.col.as<uint32_t>(),
-                           b->dev.ent.as<uint2>(), N, (uint32_t)R, sb, F, S.pairidx.as<int32_t>(),
-                           reinterpret_cast<uint32_t*>(send_slot), reinterpret_cast<uint2*>(send_ent));
-      } else {
-        ctx->sh_pay.ensure(sizeof(uint2) * std::max<int64_t>(N, 4) + 16);
-        ctx->sh_skey.ensure(sizeof(uint32_t) * std::max<int64_t>(N, 4) + 16);
-        hipLaunchKernelGGL(k_route_keys, dim3(blocks_for(N)), dim3(kBlock), 0, st, b->dev.col.as<uint32_t>(),
-                           b->dev.ent.as<uint2>(), N, (uint32_t)R, sb, F, S.pairidx.as<int32_t>(),
-                           ctx->sh_okey.as<uint32_t>(), ctx->sh_pay.as<uint2>());
-        radix_sort_pairs64_bits(ctx->route_sort, ctx->sh_okey.as<uint32_t>(), ctx->sh_pay.as<uint2>(), N, sb, sb + ob, st,
-                                ctx->sh_skey.as<uint32_t>(), reinterpret_cast<uint2*>(send_ent));
-        hipLaunchKernelGGL(k_key_slots, dim3(blocks_for(N)), dim3(kBlock), 0, st, ctx->sh_skey.as<uint32_t>(), N,
-                           (uint32_t)((sb >= 32) ? 0xFFFFFFFFu : ((1u << sb) - 1u)), reinterpret_cast<uint32_t*>(send_slot));
-      }
-    }
-    FM_HIP_CHECK(hipGetLastError());
-    ctx->prof_end("route", e0, st);
-    S.route_nnz = -1;  // until shard_route_finish has the counts
+  ShardBatchState& S = shard_state(ctx, b);
+  const int R = ctx->cfg.shard_count;
+  FM_REQUIRE(R <= kMaxR, "the owner-computes sharded step supports at most 64 ranks");
+  const int64_t B = b->dev.n_rows, N = b->dev.nnz;
+  FM_REQUIRE(N == 0 || (send_slot && send_ent), "null send buffer");
+  if (!st) st = ctx->side;
+  // the batch's previous iteration may still read its requester state on the main stream; a batch
+  // refilled by fm_batch_from_rows is routed once its gather is done
+  FM_HIP_CHECK(hipStreamWaitEvent(st, S.last_use, 0));
+  wait_built(b, st);
+  hipEvent_t e0 = ctx->prof_begin(st);
+  const int64_t ntiles = std::max<int64_t>((B + kBlock - 1) / kBlock, 1);
+  ctx->sh_okey.ensure(sizeof(uint32_t) * std::max<int64_t>(N, 4) + 16);
+  ctx->sh_mask.ensure(sizeof(uint64_t) * std::max<int64_t>(B, 1));
+  ctx->sh_tcnt.ensure(sizeof(uint32_t) * R * ntiles);
+  ctx->sh_tot.ensure(sizeof(unsigned long long) * 2 * R);
+  S.pairidx.ensure(sizeof(int32_t) * std::max<int64_t>(B, 1) * R);
+  // at least 32 B: the combine's masked loads read poff's first bytes (slots in registers)
+  S.poff.ensure(sizeof(int64_t) * std::max(R + 1, 4));
+  unsigned long long* tot = ctx->sh_tot.as<unsigned long long>();  // [R] pairs, [R] entries
+  FM_HIP_CHECK(hipMemsetAsync(tot, 0, sizeof(unsigned long long) * 2 * R, st));
+  const uint64_t F = (uint64_t)ctx->cfg.num_features;
+  const bool drop = b->max_id >= (int64_t)F;  // a predict batch with ids outside the model
+  if (B > 0) {
+    hipLaunchKernelGGL(k_sample_mask, dim3(grid_for(B * kTeamR, kBlock)), dim3(kBlock), 0, st, b->dev.row_ptr.as<int64_t>(),
+                       b->dev.col.as<uint32_t>(), B, (uint32_t)R, F, ctx->sh_mask.as<uint64_t>(), tot + R);
+    hipLaunchKernelGGL(k_pair_count, dim3((unsigned)ntiles), dim3(kBlock), 0, st, ctx->sh_mask.as<uint64_t>(), B,
+                       R, ntiles, ctx->sh_tcnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_rows_scan, dim3((unsigned)R), dim3(kBlock), 0, st, ctx->sh_tcnt.as<uint32_t>(), ntiles,
+                       tot);
+    hipLaunchKernelGGL(k_pair_index, dim3((unsigned)ntiles), dim3(kBlock), 0, st, ctx->sh_mask.as<uint64_t>(), B,
+                       R, ntiles, ctx->sh_tcnt.as<uint32_t>(), S.pairidx.as<int32_t>());
   }
+  hipLaunchKernelGGL(k_owner_offsets, dim3(1), dim3(64), 0, st, tot, R, S.poff.as<int64_t>());
+  if (N > 0) {
+    // wire keys owner << sb | slot with payload {pair index within the owner's block, x}; one
+    // stable pass over the owner bits partitions them (CSR order kept inside each owner).  sb
+    // must hold the largest slot of ANY owner (owner 0 has the most rows), the same on every rank
+    const int sb = bits_for(std::max<int64_t>((ctx->cfg.num_features - 1) / R, 1));
+    const int ob = bits_for(drop ? R : R - 1);
+    FM_REQUIRE(sb + ob <= 32, "route key does not fit 32 bits");
+    if (R == 1 && !drop) {
+      // one owner: CSR order is already the owner order and the key is the slot -- the keys and
+      // payloads go straight to the send buffers, no partition pass
+      hipLaunchKernelGGL(k_route_keys, dim3(grid_for(N, kBlock)), dim3(kBlock), 0, st, b->dev.col.as<uint32_t>(),
+                         b->dev.ent.as<uint2>(), N, (uint32_t)R, sb, F, S.pairidx.as<int32_t>(),
+                         reinterpret_cast<uint32_t*>(send_slot), reinterpret_cast<uint2*>(send_ent));
+    } else {
+      ctx->sh_pay.ensure(sizeof(uint2) * std::max<int64_t>(N, 4) + 16);
+      ctx->sh_skey.ensure(sizeof(uint32_t) * std::max<int64_t>(N, 4) + 16);
+      hipLaunchKernelGGL(k_route_keys, dim3(grid_for(N, kBlock)), dim3(kBlock), 0, st, b->dev.col.as<uint32_t>(),
+                         b->dev.ent.as<uint2>(), N, (uint32_t)R, sb, F, S.pairidx.as<int32_t>(),
+                         ctx->sh_okey.as<uint32_t>(), ctx->sh_pay.as<uint2>());
+      radix_sort_pairs64_bits(ctx->route_sort, ctx->sh_okey.as<uint32_t>(), ctx->sh_pay.as<uint2>(), N, sb, sb + ob, st,
+                              ctx->sh_skey.as<uint32_t>(), reinterpret_cast<uint2*>(send_ent));
+      hipLaunchKernelGGL(k_key_slots, dim3(grid_for(N, kBlock)), dim3(kBlock), 0, st, ctx->sh_skey.as<uint32_t>(), N,
+                         (uint32_t)((sb >= 32) ? 0xFFFFFFFFu : ((1u << sb) - 1u)), reinterpret_cast<uint32_t*>(send_slot));
+    }
+  }
+  FM_HIP_CHECK(hipGetLastError());
+  ctx->prof_end("route", e0, st);
+  S.route_nnz = -1;  // until shard_route_finish has the counts
 }
 
 // The host's copy of the route counts hc ([R] pairs, [R] entries) -> counts[0..R) entries and
 // counts[R..2R) pairs per owner, and the batch's requester state.
 void shard_route_finish(fm_ctx* ctx, fm_batch* b, const unsigned long long* hc, int64_t* counts) {
-  {
-    ShardBatchState& S = shard_state(ctx, b);
-    const int R = ctx->cfg.shard_count;
-    const int64_t N = b->dev.nnz;
-    const bool drop = b->max_id >= (int64_t)ctx->cfg.num_features;
-    S.pairs_out.assign(R, 0);
-    int64_t ne = 0;
-    for (int o = 0; o < R; ++o) {
-      counts[o] = (int64_t)hc[R + o];      // entries to owner o
-      counts[R + o] = (int64_t)hc[o];      // (sample, owner) pairs to owner o
-      S.pairs_out[o] = (int64_t)hc[o];
-      ne += (int64_t)hc[R + o];
-    }
-    FM_REQUIRE(drop ? ne <= N : ne == N, "route: inconsistent entry count");
-    S.route_nnz = N;
-    S.combined = false;
+  ShardBatchState& S = shard_state(ctx, b);
+  const int R = ctx->cfg.shard_count;
+  const int64_t N = b->dev.nnz;
+  const bool drop = b->max_id >= (int64_t)ctx->cfg.num_features;
+  S.pairs_out.assign(R, 0);
+  int64_t ne = 0;
+  for (int o = 0; o < R; ++o) {
+    counts[o] = (int64_t)hc[R + o];      // entries to owner o
+    counts[R + o] = (int64_t)hc[o];      // (sample, owner) pairs to owner o
+    S.pairs_out[o] = (int64_t)hc[o];
+    ne += (int64_t)hc[R + o];
   }
+  FM_REQUIRE(drop ? ne <= N : ne == N, "route: inconsistent entry count");
+  S.route_nnz = N;
+  S.combined = false;
 }
 
 }  // namespace fmhip
@@ -744,7 +797,7 @@ int fm_shard_owner_prepare(fm_ctx* ctx, fm_batch* b, const void* recv_slot, cons
         ctx->sh_ent2.ensure(sizeof(uint2) * n);
         ent2 = ctx->sh_ent2.as<uint2>();
       }
-      hipLaunchKernelGGL(k_pair_table, dim3(blocks_for(n)), dim3(kBlock), 0, st, reinterpret_cast<const uint2*>(recv_ent),
+      hipLaunchKernelGGL(k_pair_table, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, reinterpret_cast<const uint2*>(recv_ent),
                          n, S.src_off.as<int64_t>(), S.src_off.as<int64_t>() + (R + 1), R, pair_ptr,
                          R > 1 ? ctx->sh_ent2.as<uint2>() : nullptr);
       FM_HIP_CHECK(hipGetLastError());
@@ -822,48 +875,12 @@ void shard_owner_partials(fm_ctx* ctx, fm_batch* b, void* partials_out, uint32_t
   }
 }
 
-// the combine / predict kernels of the context's wire (GS = team_for(kp / 4))
-template <typename W>
-void launch_shard_predict(int GS, dim3 grid, hipStream_t st, const int32_t* pi, const int64_t* poff, int R, int64_t B,
-                          const void* partials_in, int64_t Ps, const uint32_t* present_in, int kp, double w0, double lo,
-                          double hi, double* pred_dev) {
-  const W* pv = reinterpret_cast<const W*>(partials_in);
-  const wire2<W>* ps = reinterpret_cast<const wire2<W>*>(pv ? pv + Ps * kp : nullptr);
-  const dim3 blk(kBlock);
-  switch (GS) {
-    case 1: hipLaunchKernelGGL((k_shard_predict<1, W>), grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
-    case 2: hipLaunchKernelGGL((k_shard_predict<2, W>), grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
-    case 4: hipLaunchKernelGGL((k_shard_predict<4, W>), grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
-    case 8: hipLaunchKernelGGL((k_shard_predict<8, W>), grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
-    default: hipLaunchKernelGGL((k_shard_predict<16, W>), grid, blk, 0, st, pi, poff, R, B, pv, ps, present_in, kp, w0, lo, hi, pred_dev); break;
-  }
-}
-
 void shard_combine_predict(fm_ctx* ctx, fm_batch* b, const void* partials_in, const uint32_t* present_in,
                            double lo, double hi, double* pred_dev) {
-  ShardBatchState& S = shard_state(ctx, b);
-  FM_REQUIRE(S.route_nnz == b->dev.nnz && (int)S.pairs_out.size() == ctx->cfg.shard_count,
-             "fm_shard_route must run on this batch first");
-  const int R = ctx->cfg.shard_count;
-  const int64_t B = b->dev.n_rows;
-  if (B == 0) return;
-  int64_t Ps = 0;
-  for (int o = 0; o < R; ++o) Ps += S.pairs_out[o];
-  FM_REQUIRE(Ps == 0 || (partials_in && present_in), "null buffer");
-  const int kp = ctx->kp;
-  const int GS = team_for(kp / 4);
-  int64_t blocks = std::max<int64_t>((B + kBlock / GS - 1) / (kBlock / GS), 1);
-  if (blocks > 256 * 8) blocks = 256 * 8;
-  const int32_t* pi = S.pairidx.as<int32_t>();
-  const int64_t* poff = S.poff.as<int64_t>();
-  const double w0 = ctx->cfg.w0;
-  hipStream_t st = ctx->stream;
-  const dim3 grid((unsigned)blocks);
-  if (ctx->cfg.wire == FM_WIRE_FP64)
-    launch_shard_predict<double>(GS, grid, st, pi, poff, R, B, partials_in, Ps, present_in, kp, w0, lo, hi, pred_dev);
-  else
-    launch_shard_predict<float>(GS, grid, st, pi, poff, R, B, partials_in, Ps, present_in, kp, w0, lo, hi, pred_dev);
-  FM_HIP_CHECK(hipGetLastError());
+  const ReqPlan q = requester_plan(ctx, b, shard_state(ctx, b));
+  if (q.B == 0) return;
+  FM_REQUIRE(q.Ps == 0 || (partials_in && present_in), "null buffer");
+  launch_requester<true>(ctx, q, partials_in, present_in, lo, hi, pred_dev);
 }
 
 }  // namespace fmhip
@@ -873,37 +890,16 @@ extern "C" {
 int fm_shard_combine(fm_ctx* ctx, fm_batch* b, const void* partials_in, void* s_send) {
   return guarded(ctx, [&]() -> int {
     ShardBatchState& S = shard_state(ctx, b);
-    FM_REQUIRE(S.route_nnz == b->dev.nnz && (int)S.pairs_out.size() == ctx->cfg.shard_count,
-               "fm_shard_route must run on this batch first");
-    const int R = ctx->cfg.shard_count;
-    const int64_t B = b->dev.n_rows;
-    int64_t Ps = 0;
-    for (int o = 0; o < R; ++o) Ps += S.pairs_out[o];
-    FM_REQUIRE(Ps == 0 || (partials_in && s_send), "null buffer");
+    const ReqPlan q = requester_plan(ctx, b, S);
+    FM_REQUIRE(q.Ps == 0 || (partials_in && s_send), "null buffer");
     hipStream_t st = ctx->stream;
     hipEvent_t e0 = ctx->prof_begin(st);
-    const int nq = ctx->kp / 4;
-    const int GS = team_for(nq);
-    const int64_t tpb = kBlock / GS;
-    int64_t blocks = std::max<int64_t>((B + tpb - 1) / tpb, 1);
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    ctx->work.loss_part.ensure(sizeof(double) * 2 * 256 * 8);  // reserve_work's size: no reallocation later
-    const int32_t* pi = S.pairidx.as<int32_t>();
-    const int64_t* poff = S.poff.as<int64_t>();
-    const int kp = ctx->kp;
-    float* so = reinterpret_cast<float*>(s_send);
-    float2* ssc = reinterpret_cast<float2*>(so ? so + Ps * kp : nullptr);
-    const double* lab = b->dev.label.as<double>();
-    double2* lp = ctx->work.loss_part.as<double2>();
-    const double w0 = ctx->cfg.w0;
-    const dim3 grid((unsigned)blocks);
-    if (ctx->cfg.wire == FM_WIRE_FP64)
-      launch_shard_combine<double>(GS, grid, st, pi, poff, R, B, partials_in, Ps, lab, kp, w0, so, ssc, lp);
-    else
-      launch_shard_combine<float>(GS, grid, st, pi, poff, R, B, partials_in, Ps, lab, kp, w0, so, ssc, lp);
-    FM_HIP_CHECK(hipGetLastError());
+    ctx->work.loss_part.ensure(sizeof(double2) * kLossPartBlocks);  // reserve_work's size: no reallocation later
+    float* s_vec = reinterpret_cast<float*>(s_send);
+    launch_requester<false>(ctx, q, partials_in, b->dev.label.as<double>(), s_vec,
+                            wire_scalars<float2>(s_vec, q.Ps, q.kp), ctx->work.loss_part.as<double2>());
     ctx->prof_end("combine", e0, st);
-    S.loss_blocks = blocks;
+    S.loss_blocks = q.blocks;
     S.combined = true;
     return FM_OK;
   });
@@ -928,13 +924,13 @@ int fm_shard_owner_update(fm_ctx* ctx, fm_batch* b, const void* s_recv, int32_t 
     hipEvent_t e0 = ctx->prof_begin(st);
     const float* Srow = reinterpret_cast<const float*>(s_recv);  // [P][kp] S, then [P] {r, yhat}
     const int kp = ctx->kp;
-    SegSource src{Srow, kp, reinterpret_cast<const float2*>(Srow ? Srow + S.P * kp : nullptr), 1};
+    SegSource src{Srow, kp, wire_scalars<const float2>(Srow, S.P, kp), 1};
     if (s_rec_yl(kp) && S.P > 0) {
       // one record per pair (S and {r, yhat} in one line), as the single-table step's
       const int rec = s_rec_floats(kp);
       ctx->work.S.ensure(sizeof(float) * (size_t)S.P * rec);
       const int64_t nq = S.P * (rec / 4);
-      hipLaunchKernelGGL(k_pack_srec, dim3(blocks_for(nq)), dim3(kBlock), 0, st, Srow, src.yl, S.P, kp, rec,
+      hipLaunchKernelGGL(k_pack_srec, dim3(grid_for(nq, kBlock)), dim3(kBlock), 0, st, Srow, src.yl, S.P, kp, rec,
                          ctx->work.S.as<float>());
       FM_HIP_CHECK(hipGetLastError());
       src = SegSource{ctx->work.S.as<float>(), rec, reinterpret_cast<const float2*>(ctx->work.S.as<float>() + kp), rec / 2};

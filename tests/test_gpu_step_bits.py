@@ -5,8 +5,12 @@ fm_repl_apply) and digests the loss history and the exported tables; the fixture
 known-good build gave.  Fused and unfused steps, prepared and unprepared batches, k = 3 .. 80,
 with absent rows, empty rows, a row long enough for the fused forward's overflow walk and runs of
 2, 300 and 768 entries (group-boundary pieces, the two-range and the long-run combine), three
-steps with regParam > 0.  Equality is exact: a change to the forward, the segmented update, its
-combine or the replicated apply that moves one bit of a table or a loss shows here.  The bits
+steps with regParam > 0.  The sharded cases run the same problems through a sharded context of
+R = 1 .. 12 ranks on one device, both wires, and add the digest of fm_predict on the trained tables:
+every team width and both owner-access variants of the requester's combine, and its predict with
+absent rows counted.  Equality is exact: a change to the forward, the segmented update, its
+combine, the replicated apply, or the sharded combine and predict that moves one bit of a table, a
+loss or a prediction shows here.  The bits
 depend on the compiler too; see the tool's docstring for regenerating the fixture.
 """
 
@@ -34,3 +38,4 @@ def test_step_bits(gpu, name):
     got = step_bits.run_case(name)
     assert got["loss"] == GOLDEN[name]["loss"]
     assert got["tables"] == GOLDEN[name]["tables"]
+    assert got.get("predict") == GOLDEN[name].get("predict")

@@ -1,8 +1,12 @@
 """Bit-level pin of the step's update paths (tests/golden/step_bits.json, tests/test_gpu_step_bits.py).
 
 A fixed set of small problems goes through fm_step_batch; per case the tool records the loss history
-as hex floats and a SHA-256 of the fm_export_tables bytes (ids, w, V).  A refactor of the forward,
-the segmented update, its combine or the replicated apply must reproduce every digest.
+as hex floats and a SHA-256 of the fm_export_tables bytes (ids, w, V).  A sharded case runs the same
+problem through a sharded context of R ranks on one device (the group path: route, owner forward,
+fm_shard_combine, owner update) and adds a SHA-256 of fm_predict over batch 0 on the trained tables
+(the sharded predict's combine, present counts included).  A refactor of the forward, the segmented
+update, its combine, the replicated apply, or the sharded requester's combine and predict must
+reproduce every digest.
 
     python tools/step_bits.py --out tests/golden/step_bits.json     # record (GPU)
     python tools/step_bits.py --check tests/golden/step_bits.json   # compare (GPU)
@@ -101,13 +105,25 @@ for _k in (32, 80):
 CASES["k16_mixed"] = (16, True, (1, 3))  # an unprepared step between fused ones
 CASES["k8_repl"] = (8, None, ())
 CASES["k16_repl"] = (16, None, ())
+# sharded: fuse = (R, wire); batch 1 is prepared (routed ahead) behind step 1, steps 1 and 3 route
+# inline.  The smallest shapes that reach every requester kernel family: teams of 1 .. 16 lanes
+# (k = 3, 8, 16, 32, 80; at k = 80 the 20 quads take two trips of the team, the second partly idle),
+# the pair slots in registers (R <= 8, all eight at R = 8) and owner by owner (R = 12), both wires,
+# and one owner alone.
+for _k, _r, _w in ((3, 3, "fp32"), (8, 3, "fp64"), (16, 3, "fp32"), (16, 3, "fp64"), (32, 8, "fp32"),
+                   (80, 2, "fp64"), (16, 12, "fp32"), (16, 12, "fp64"), (80, 12, "fp32"), (8, 1, "fp32")):
+    CASES[f"k{_k}_shard{_r}_{_w}"] = (_k, (_r, _w), (2,))
+
+
+def _sha(arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
 
 
 def _digest(loss, tables):
-    h = hashlib.sha256()
-    for a in tables:
-        h.update(np.ascontiguousarray(a).tobytes())
-    return {"loss": [float(x).hex() for x in loss], "tables": h.hexdigest()}
+    return {"loss": [float(x).hex() for x in loss], "tables": _sha(tables)}
 
 
 def run_case(name):
@@ -130,7 +146,12 @@ def run_case(name):
         out = _digest(loss, eng.export_tables())
         eng.ctx.close()
         return out
-    ctx = FMContext(F, k, fuse=fuse)
+    sharded = isinstance(fuse, tuple)
+    if sharded:
+        R, wire = fuse
+        ctx = FMContext(F, k, parallel="sharded", n_gpus=R, devices=[0] * R, transport="copy", wire=wire)
+    else:
+        ctx = FMContext(F, k, fuse=fuse)
     ctx.load_tables(ids, w, V)
     bs = [ctx.batch(h) for h in hosts]
     for t in range(1, STEPS + 1):
@@ -139,6 +160,8 @@ def run_case(name):
             b.prepare()
         ctx.step_batch(b, t, STEP_SIZE, REG)
     out = _digest(ctx.loss_history(), ctx.export_tables())
+    if sharded:
+        out["predict"] = _sha([ctx.predict(hosts[0], 0.0, 1.0)])
     ctx.close()
     return out
 
