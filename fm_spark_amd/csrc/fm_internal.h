@@ -287,6 +287,21 @@ void launch_split(const uint32_t* skeys, const uint2* sents, int64_t N, SplitWor
 void launch_segment_update(const TableView& T, int64_t N, const SegSource& src, StepWork& w, const StepParams& p,
                            const uint32_t* skeys, const uint2* sents, int64_t n_loss_blocks, double* stats_out,
                            hipStream_t st, float* emit = nullptr);
+// A seam for the suite (tests/native/update_probe.hip), not configuration: the update side's
+// geometry at padded width kp, read from the constants and the kp -> kernel choice that
+// launch_segment_update and launch_split use, so a test can place runs of equal keys against
+// the kernels' boundaries without keeping a copy of them.  No kernel reads it.
+struct UpdGeometry {
+  int32_t wave_entries;       // sorted entries per update wave (= per combine range)
+  int32_t group_entries;      // entries per lane group of k_segment_update at this kp
+  int32_t block_entries;      // entries per update block
+  int32_t paired;             // 1: a run closed in phase 2 leaves in a paired row store at this kp (table mode)
+  int32_t comb_lanes;         // k_segment_combine's lanes per range
+  int32_t comb_cols;          // long-run columns a combine lane sums at once
+  int32_t split_chunk;        // sorted entries per split wave
+  int32_t scan_round_chunks;  // split chunks k_split_scan takes per round
+};
+UpdGeometry update_geometry(int kp);
 // replicated mode: apply the all-reduced gradient sums grad[rows][kp + 4] to every touched row;
 // the number of touched rows -> *n_touched (device, fp64 stats slot), through per-block counts in
 // blk_touched[kReplApplyBlocks]

@@ -61,7 +61,27 @@ struct UpdGeom {
   // group) instead of living in registers until phase 3
   static constexpr int HEADS = NG * PIECE * 8;
   static constexpr int BYTES = IMG + HEADS;
+  // the configurations whose rows leave in paired stores at kp = 4Q (k_segment_update, "Paired row stores")
+  static constexpr bool PAIR = (Q == 2 || Q == 4) && NF == 1;
 };
+
+// The one choice of k_segment_update<Q, NF, D> by kp: f is called with the UpdCfg of the
+// instantiation that serves kp (the launch and update_geometry both go through here).
+template <int Q_, int NF_, int D_>
+struct UpdCfg {
+  static constexpr int Q = Q_, NF = NF_, D = D_;
+};
+template <class F>
+void with_update_cfg(int kp, F&& f) {
+  const int nq = kp / 4;  // column quads
+  if (nq <= 1) f(UpdCfg<1, 1, kUpdD>{});
+  else if (nq <= 2) f(UpdCfg<2, 1, kUpdD2>{});
+  else if (nq <= 4) f(UpdCfg<4, 1, kUpdD4>{});
+  else if (nq <= 8) f(UpdCfg<8, 1, kUpdD>{});
+  else if (nq <= 16) f(UpdCfg<16, 1, kUpdD>{});
+  else if (nq <= 32) f(UpdCfg<16, 2, 2>{});
+  else f(UpdCfg<16, 4, 1>{});
+}
 
 // The interaction gradient of one entry (Model.scala:201-204, SGD.scala:146) is
 //   g_V[f] = (S[s][f] * x - (v[f] * x) * x) * r,   r = yhat - y,
@@ -178,7 +198,7 @@ __global__ __launch_bounds__(kBlock, NF == 1 ? kUpdMinW : 1) void k_segment_upda
     // is kept in registers and written at the end of the entry step by 2Q lanes, the group's Q (V)
     // and its neighbour group's Q (header + zero pad), so every row leaves in ONE store
     // instruction covering its whole record instead of two half-record ones.
-    constexpr bool kPairCfg = (Q == 2 || Q == 4) && NF == 1;
+    constexpr bool kPairCfg = Geo::PAIR;
     const bool paired = kPairCfg && kp == 4 * Q && !a.emit;  // wave-uniform
     float4 pend_v = make_float4(0.f, 0.f, 0.f, 0.f);
     float pend_w = 0.f;             // the row's new w (its header is {w, epoch + 1, cum_next})
@@ -443,6 +463,7 @@ __device__ __forceinline__ void close_hdr(const SegArgs& a, uint32_t key, const 
 }
 
 constexpr int kStatLd = 8;     // block 0's stats loads in flight per thread
+constexpr int kCombLanes = 16;  // lanes per range (lane f: factor columns f, f + kCombLanes, ...)
 constexpr int kCombCols = 10;  // long-run columns a lane sums at once (even; W = kp + 2: k = 8 in one pass)
 __global__ __launch_bounds__(kBlock) void k_segment_combine(SegArgs a, const double2* __restrict__ loss_part,
                                                             int64_t n_loss_blocks, int64_t n_ucnt,
@@ -505,9 +526,9 @@ __global__ __launch_bounds__(kBlock) void k_segment_combine(SegArgs a, const dou
       stats_out[2] = ru[0];
     }
   }
-  // 16 lanes per range (lane f: factor columns f, f + 16, ...)
-  const int64_t chunk = ((int64_t)blockIdx.x * kBlock + tid) / 16;  // range index
-  const int f = tid & 15;
+  // kCombLanes lanes per range
+  const int64_t chunk = ((int64_t)blockIdx.x * kBlock + tid) / kCombLanes;  // range index
+  const int f = tid & (kCombLanes - 1);
   const int64_t L = a.L;
   bool owner = false, two = false;
   uint32_t key = 0;
@@ -538,7 +559,7 @@ __global__ __launch_bounds__(kBlock) void k_segment_combine(SegArgs a, const dou
     const RowCur rc = row_current(a, key);
     const double b = bt + bh;
     if (f < kp) close_col(a, key, rc, f, vf, b, st + sh);
-    for (int c = f + 16; c < kp; c += 16) {
+    for (int c = f + kCombLanes; c < kp; c += kCombLanes) {
       const double sm = pt[1 + c] + ph[1 + c];
       close_cols(a, key, rc, c, c + 1, 1, b, &sm);
     }
@@ -902,21 +923,33 @@ void launch_segment_update(const TableView& T, int64_t N, const SegSource& src, 
   a.n_dev = src.n_dev;
   if (ublocks > 0) {
     const dim3 grid((unsigned)ublocks), blk(kBlock);
-    const int nq = T.kp / 4;  // column quads
-    if (nq <= 1) hipLaunchKernelGGL((k_segment_update<1, 1, kUpdD>), grid, blk, 0, st, a);
-    else if (nq <= 2) hipLaunchKernelGGL((k_segment_update<2, 1, kUpdD2>), grid, blk, 0, st, a);
-    else if (nq <= 4) hipLaunchKernelGGL((k_segment_update<4, 1, kUpdD4>), grid, blk, 0, st, a);
-    else if (nq <= 8) hipLaunchKernelGGL((k_segment_update<8, 1, kUpdD>), grid, blk, 0, st, a);
-    else if (nq <= 16) hipLaunchKernelGGL((k_segment_update<16, 1, kUpdD>), grid, blk, 0, st, a);
-    else if (nq <= 32) hipLaunchKernelGGL((k_segment_update<16, 2, 2>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((k_segment_update<16, 4, 1>), grid, blk, 0, st, a);
+    with_update_cfg(T.kp, [&](auto cfg) {
+      using Cfg = decltype(cfg);
+      hipLaunchKernelGGL((k_segment_update<Cfg::Q, Cfg::NF, Cfg::D>), grid, blk, 0, st, a);
+    });
     FM_HIP_CHECK(hipGetLastError());
   }
-  int64_t cblocks = (nranges * 16 + kBlock - 1) / kBlock;
+  int64_t cblocks = (nranges * kCombLanes + kBlock - 1) / kBlock;
   if (cblocks < 1) cblocks = 1;
   hipLaunchKernelGGL(k_segment_combine, dim3((unsigned)cblocks), dim3(kBlock), 0, st, a,
                      w.loss_part.as<double2>(), n_fwd_blocks, ublocks, stats_out);
   FM_HIP_CHECK(hipGetLastError());
+}
+
+UpdGeometry update_geometry(int kp) {
+  UpdGeometry g{};
+  g.wave_entries = kWaveEnt;
+  g.block_entries = kWaveEnt * (kBlock / 64);
+  with_update_cfg(kp, [&](auto cfg) {
+    using Geo = UpdGeom<decltype(cfg)::Q, decltype(cfg)::NF>;
+    g.group_entries = Geo::RL;
+    g.paired = Geo::PAIR && kp == 4 * decltype(cfg)::Q;
+  });
+  g.comb_lanes = kCombLanes;
+  g.comb_cols = kCombCols;
+  g.split_chunk = kSplitChunk;
+  g.scan_round_chunks = kSplitScanNT * kSplitPer;
+  return g;
 }
 
 void launch_repl_apply(const TableView& T, const float* grad, const StepParams& p, uint32_t* blk_touched,

@@ -5,7 +5,8 @@ lets tests/test_gpu_sort.py call fmhip::radix_sort_pairs / radix_sort_pairs64 /
 radix_sort_pairs64_bits of the built library directly.  __graft_entry__.build() calls
 build_probe() after the library; the tests only load what was built.  The same library carries a
 second source, tests/native/forward_probe.hip: the door to the forward's launch-size seam
-(tests/forward_probe.py wraps it).
+(tests/forward_probe.py wraps it), and a third, tests/native/update_probe.hip: the door to the update
+side's geometry seam (tests/update_probe.py wraps it).
 """
 
 from __future__ import annotations
@@ -21,8 +22,9 @@ import numpy as np
 HERE = Path(__file__).resolve().parent
 ROOT = HERE.parent
 SRC = HERE / "native" / "sort_probe.hip"
-# the same library carries the forward's launch-size door (tests/forward_probe.py)
-SRCS = [SRC, HERE / "native" / "forward_probe.hip"]
+# the same library carries the forward's launch-size door (tests/forward_probe.py) and the update
+# side's geometry door (tests/update_probe.py)
+SRCS = [SRC, HERE / "native" / "forward_probe.hip", HERE / "native" / "update_probe.hip"]
 LIB_DIR = ROOT / "fm_spark_amd" / "lib"
 PROBE = LIB_DIR / "libfm_sort_probe.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

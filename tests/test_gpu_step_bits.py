@@ -4,8 +4,9 @@ tools/step_bits.py runs small fixed problems through fm_step_batch (and fm_repl_
 fm_repl_apply) and digests the loss history and the exported tables; the fixture holds what a
 known-good build gave.  Fused and unfused steps, prepared and unprepared batches, k = 3 .. 80,
 with absent rows, empty rows, a row long enough for the fused forward's overflow walk and runs of
-2, 300 and 768 entries (group-boundary pieces, the two-range and the long-run combine), three
-steps with regParam > 0.  The sharded cases run the same problems through a sharded context of
+2, 300 and 768 entries, three steps with regParam > 0.  (Whether the update's pieces and combines are
+right at their group, wave, block and range edges is tests/test_gpu_update_edges.py's question, against
+the oracle; this file only says when bits move.)  The sharded cases run the same problems through a sharded context of
 R = 1 .. 12 ranks on one device, both wires, and add the digest of fm_predict on the trained tables:
 every team width and both owner-access variants of the requester's combine, and its predict with
 absent rows counted.  Equality is exact: a change to the forward, the segmented update, its
