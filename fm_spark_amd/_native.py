@@ -71,6 +71,17 @@ class fm_step_out(C.Structure):
     ]
 
 
+class fm_eval_out(C.Structure):
+    _fields_ = [
+        ("n_rows", C.c_int64),
+        ("n_unlearned", C.c_int64),
+        ("epoch", C.c_int64),
+        ("sum_err", C.c_double),
+        ("sum_abs_err", C.c_double),
+        ("sum_sq_err", C.c_double),
+    ]
+
+
 _P = C.c_void_p
 _I64P = C.POINTER(C.c_int64)
 _I32P = C.POINTER(C.c_int32)
@@ -107,6 +118,9 @@ SIGNATURES = {
     "fm_loss_history": (C.c_int, [_P, _DP, C.c_int64, _I64P]),
     "fm_predict": (C.c_int, [_P, C.POINTER(fm_csr), C.c_double, C.c_double, _DP]),
     "fm_predict_batch": (C.c_int, [_P, _P, C.c_double, C.c_double, _DP]),
+    "fm_evaluate": (C.c_int, [_P, C.POINTER(fm_csr), C.c_double, C.c_double, _DP, C.POINTER(fm_eval_out)]),
+    "fm_evaluate_batch": (C.c_int, [_P, _P, C.c_double, C.c_double, _DP, C.POINTER(fm_eval_out)]),
+    "fm_eval_history": (C.c_int, [_P, C.POINTER(fm_eval_out), C.c_int64, _I64P]),
     "fm_rank_candidates": (C.c_int, [_P, C.POINTER(fm_csr), C.POINTER(fm_csr), C.c_int32, C.c_double, C.c_double,
                                      _I32P, _DP]),
     "fm_rank_batch": (C.c_int, [_P, _P, _P, C.c_int32, C.c_double, C.c_double, _I32P, _DP]),

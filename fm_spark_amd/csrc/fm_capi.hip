@@ -300,6 +300,31 @@ void wait_built(const fm_batch* b, hipStream_t st) {
   if (b->built) FM_HIP_CHECK(hipStreamWaitEvent(st, b->built, 0));
 }
 
+double* eval_next_slot(fm_ctx* ctx) {
+  ctx->ensure_eval_hist(ctx->eval_n + 1);
+  return ctx->eval_hist.as<double>() + kEvalRec * ctx->eval_n;
+}
+
+void eval_read(const double* rec, int64_t epoch, fm_eval_out* out) {
+  out->n_rows = (int64_t)rec[0];
+  out->n_unlearned = (int64_t)rec[1];
+  out->epoch = epoch;
+  out->sum_err = rec[2];
+  out->sum_abs_err = rec[3];
+  out->sum_sq_err = rec[4];
+}
+
+void eval_commit(fm_ctx* ctx, fm_eval_out* out) {
+  const double* slot = ctx->eval_hist.as<double>() + kEvalRec * ctx->eval_n;
+  ctx->eval_epoch.push_back(ctx->epoch);
+  ctx->eval_n += 1;
+  if (!out) return;
+  ctx->pinned.ensure(64);
+  FM_HIP_CHECK(hipMemcpyAsync(ctx->pinned.p, slot, sizeof(double) * kEvalRec, hipMemcpyDeviceToHost, ctx->stream));
+  FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  eval_read(reinterpret_cast<const double*>(ctx->pinned.p), ctx->epoch, out);
+}
+
 void reserve_work(fm_ctx* ctx, int64_t B, int64_t N) {
   StepWork& w = ctx->work;
   w.S.ensure_slack(sizeof(float) * (size_t)std::max<int64_t>(B, 1) * s_rec_floats(ctx->kp));
@@ -994,6 +1019,74 @@ int fm_predict_batch(fm_ctx* ctx, fm_batch* b, double lo, double hi, double* pre
     ctx->prof_end("predict", e0, ctx->stream);
     FM_HIP_CHECK(hipMemcpyAsync(pred, dp.p, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
     FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return FM_OK;
+  });
+}
+
+// One evaluation of a single-table context's batch on the main stream: the forward in kEvaluate mode,
+// the fold into the history's next slot, the record counted; pred / out as fm_evaluate_batch takes them.
+static int evaluate_impl(fm_ctx* ctx, fm_batch* b, double lo, double hi, double* pred, fm_eval_out* out) {
+  const int64_t B = b->dev.n_rows;
+  hipStream_t st = ctx->stream;
+  double* slot = eval_next_slot(ctx);
+  if (pred) ctx->eval_pred.ensure_slack(sizeof(double) * B);
+  wait_built(b, st);
+  hipEvent_t e0 = ctx->prof_begin(st);
+  const int64_t nblk = launch_evaluate(ctx->view(), b->dev, ctx->work, ctx->cum_host.back(), ctx->cfg.w0, lo, hi,
+                                       pred ? ctx->eval_pred.as<double>() : nullptr, st);
+  hipEvent_t ef = ctx->prof_begin(st);  // the fold alone, inside "evaluate"
+  launch_eval_fold(ctx->work.eval_part.as<double>(), nblk, slot, st);
+  ctx->prof_end("eval_fold", ef, st);
+  ctx->prof_end("evaluate", e0, st);
+  // a read of the batch: its next fm_batch_prepare or fm_batch_from_rows refill waits for it
+  if (b->last_use) FM_HIP_CHECK(hipEventRecord(b->last_use, st));
+  if (pred) FM_HIP_CHECK(hipMemcpyAsync(pred, ctx->eval_pred.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+  eval_commit(ctx, out);
+  return FM_OK;
+}
+
+int fm_evaluate(fm_ctx* ctx, const fm_csr* csr, double lo, double hi, double* pred, fm_eval_out* out) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(csr != nullptr && out != nullptr, "null argument");
+    *out = fm_eval_out{};
+    if (ctx->group) return group_evaluate(ctx, csr, lo, hi, pred, out);
+    if (csr->n_rows == 0) return FM_NOTHING_TO_DO;
+    fm_batch* b = host_batch(ctx);
+    upload_batch(ctx, csr, b, false);
+    return evaluate_impl(ctx, b, lo, hi, pred, out);
+  });
+}
+
+int fm_evaluate_batch(fm_ctx* ctx, fm_batch* b, double lo, double hi, double* pred, fm_eval_out* out) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(b != nullptr && b->owner == ctx, "batch belongs to another context");
+    FM_REQUIRE(out != nullptr || pred == nullptr, "pred needs out: an evaluation that only enqueues returns no predictions");
+    FM_REQUIRE(b->split_rows.empty(), "a dataset made by fm_batch_create_splits is evaluated by split");
+    if (out) *out = fm_eval_out{};
+    if (ctx->group) return group_evaluate_batch(ctx, b, lo, hi, pred, out);
+    if (b->dev.n_rows == 0) return FM_NOTHING_TO_DO;
+    return evaluate_impl(ctx, b, lo, hi, pred, out);
+  });
+}
+
+int fm_eval_history(fm_ctx* ctx, fm_eval_out* out, int64_t cap, int64_t* n) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(n != nullptr, "null n");
+    if (ctx->group) {  // the ranks' summed records, kept on the host
+      *n = (int64_t)ctx->eval_host.size();
+      if (cap == 0 || *n == 0) return FM_OK;
+      FM_REQUIRE(out != nullptr, "null history buffer");
+      std::copy_n(ctx->eval_host.begin(), std::min<int64_t>(cap, *n), out);
+      return FM_OK;
+    }
+    *n = ctx->eval_n;
+    if (cap == 0 || ctx->eval_n == 0) return FM_OK;
+    FM_REQUIRE(out != nullptr, "null history buffer");
+    const int64_t m = std::min<int64_t>(cap, ctx->eval_n);
+    std::vector<double> h(kEvalRec * m);
+    FM_HIP_CHECK(hipMemcpyAsync(h.data(), ctx->eval_hist.p, sizeof(double) * kEvalRec * m, hipMemcpyDeviceToHost, ctx->stream));
+    FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < m; ++i) eval_read(h.data() + kEvalRec * i, ctx->eval_epoch[i], out + i);
     return FM_OK;
   });
 }

@@ -188,6 +188,15 @@ struct fm_ctx {
   int32_t epoch = 0;
   DevBuf loss_hist;  // [hist_cap][3] double {loss, n_loss, n_unique}
   int64_t hist_cap = 0;
+  // fm_evaluate*: one record per evaluation of a non-empty batch, kept on the device until asked for
+  // (fm_eval_history), as the loss history; made at the first evaluation.  The epoch of each is known
+  // when it is enqueued and stays on the host.  A multi-GPU context keeps the ranks' summed records
+  // on the host instead (eval_host).
+  DevBuf eval_hist;  // [eval_cap][kEvalRec] double
+  int64_t eval_cap = 0, eval_n = 0;
+  std::vector<int64_t> eval_epoch;
+  std::vector<fm_eval_out> eval_host;
+  DevBuf eval_pred;  // the synchronous evaluation's predictions on their way to the host (grown to the largest call)
   StepWork work;
   Pinned pinned;
   Pinned up_pin;                         // host CSR upload staging (upload_batch)
@@ -304,6 +313,21 @@ struct fm_ctx {
     hist_cap = c;
   }
 
+  // the evaluation history holds `need` records: grown as ensure_hist grows the loss history
+  void ensure_eval_hist(int64_t need) {
+    if (need <= eval_cap) return;
+    int64_t c = std::max<int64_t>(4096, eval_cap);
+    while (c < need) c *= 2;
+    FM_HIP_CHECK(hipStreamSynchronize(stream));
+    DevBuf nb;
+    nb.ensure(sizeof(double) * kEvalRec * c);
+    FM_HIP_CHECK(hipMemset(nb.p, 0, sizeof(double) * kEvalRec * c));
+    if (eval_cap > 0)
+      FM_HIP_CHECK(hipMemcpy(nb.p, eval_hist.p, sizeof(double) * kEvalRec * eval_cap, hipMemcpyDeviceToDevice));
+    eval_hist = std::move(nb);  // the old history is freed (the stream was drained above)
+    eval_cap = c;
+  }
+
   ~fm_ctx() {
     group.reset();
     (void)hipSetDevice(cfg.device);
@@ -329,7 +353,8 @@ struct fm_ctx {
     // the context's device, after its streams drained and before the main stream is destroyed.
     rec.release();
     loss_hist.release();
-    DevBuf* bufs[] = {&work.S, &work.yl, &work.loss_part, &work.part, &work.ucnt,
+    eval_hist.release();
+    DevBuf* bufs[] = {&work.S, &work.yl, &work.loss_part, &work.part, &work.ucnt, &work.eval_part, &eval_pred,
                       &work.sort.keys_a, &work.sort.keys_b, &work.sort.vals_a, &work.sort.vals_b,
                       &work.sort.counts, &work.sort.digit_tot, &side_sort.keys_a, &side_sort.keys_b,
                       &side_sort.vals_a, &side_sort.vals_b, &side_sort.counts, &side_sort.digit_tot,
@@ -450,6 +475,18 @@ void shard_owner_partials(fm_ctx* ctx, fm_batch* b, void* partials_out, uint32_t
                           int chunks = 1);
 void shard_combine_predict(fm_ctx* ctx, fm_batch* b, const void* partials_in, const uint32_t* present_in,
                            double lo, double hi, double* pred_dev);
+// the requester's evaluation epilogue (k_shard_evaluate): the same scores against this rank's labels,
+// reduced into the record at rec_dev (device, kEvalRec doubles); pred_dev optional.  A rank without
+// rows launches nothing.
+void shard_combine_evaluate(fm_ctx* ctx, fm_batch* b, const void* partials_in, const uint32_t* present_in,
+                            double lo, double hi, double* pred_dev, double* rec_dev);
+// fm_evaluate*'s record keeping (fm_capi.hip): the device slot of the context's next evaluation
+// record (the history grown first), and -- once the evaluation and its fold into that slot are
+// enqueued -- the record counted, with the epoch; out != NULL: the main stream is waited for and
+// the record read back into *out
+double* eval_next_slot(fm_ctx* ctx);
+void eval_commit(fm_ctx* ctx, fm_eval_out* out);
+void eval_read(const double* rec, int64_t epoch, fm_eval_out* out);  // a host copy of a record -> *out
 
 // multi-GPU contexts (fm_group.hip); each runs inside the group context's guarded()
 int group_create(const fm_config* cfg, fm_ctx** out);
@@ -466,6 +503,8 @@ int group_step(fm_ctx* ctx, const fm_csr* csr, int32_t t, double step_size, doub
 int group_step_batch(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_param, fm_step_out* out);
 int group_predict(fm_ctx* ctx, const fm_csr* csr, double lo, double hi, double* pred);
 int group_predict_batch(fm_ctx* ctx, fm_batch* b, double lo, double hi, double* pred);
+int group_evaluate(fm_ctx* ctx, const fm_csr* csr, double lo, double hi, double* pred, fm_eval_out* out);
+int group_evaluate_batch(fm_ctx* ctx, fm_batch* b, double lo, double hi, double* pred, fm_eval_out* out);
 int group_load_tables(fm_ctx* ctx, const int32_t* ids, int64_t n, const double* w, const double* V);
 int group_init_random(fm_ctx* ctx, const int32_t* ids, int64_t n, int64_t id_begin, int64_t id_end);
 int group_init_from_batch(fm_ctx* ctx, fm_batch* b, int64_t* n_present);

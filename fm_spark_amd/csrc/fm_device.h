@@ -87,6 +87,48 @@ __device__ __forceinline__ void block_loss_partial(double loss_acc, double nloss
   }
 }
 
+// Evaluation (kEvaluate, k_shard_evaluate, k_eval_fold): a thread's record of the rows it scored,
+// kEvalRec fp64 sums {rows, rows without a learned entry, sum e, sum |e|, sum e^2} of e = label -
+// prediction.  (The counts are sums of 1.0: exact below 2^53 rows.)
+struct EvalAcc {
+  double v[kEvalRec] = {0.0, 0.0, 0.0, 0.0, 0.0};
+};
+// One row into the record: the prediction is FactorizationMachinesModel.predict's (Model.scala:86,
+// :129-132: w0 unclamped for a row without a learned entry, else the clamped yhat); returns it, so
+// that what a caller stores is the value that was subtracted.
+__device__ __forceinline__ double eval_row(EvalAcc& a, double yhat, bool learned, double w0, double lo, double hi,
+                                           double y) {
+  const double p = learned ? fmin(fmax(yhat, lo), hi) : w0;
+  const double e = y - p;
+  a.v[0] += 1.0;
+  a.v[1] += learned ? 0.0 : 1.0;
+  a.v[2] += e;
+  a.v[3] += fabs(e);
+  a.v[4] += e * e;
+  return p;
+}
+// block_loss_partial's reduction for the record: each sum through the xor tree within a wave, then
+// the waves in order, into out[kEvalRec] (thread 0).  The order depends on the block shape alone.
+__device__ __forceinline__ void block_eval_partial(EvalAcc a, double* __restrict__ out) {
+  const int tid = threadIdx.x;
+  __shared__ double red[kEvalRec][kBlock / 64];
+#pragma unroll
+  for (int i = 0; i < kEvalRec; ++i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a.v[i] += __shfl_xor(a.v[i], o);
+    if ((tid & 63) == 0) red[i][tid >> 6] = a.v[i];
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < kEvalRec; ++i) {
+      double s = 0.0;
+      for (int w = 0; w < kBlock / 64; ++w) s += red[i][w];
+      out[i] = s;
+    }
+  }
+}
+
 __device__ __forceinline__ void st_row4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 __device__ __forceinline__ float shrink_f(float z, double a) {

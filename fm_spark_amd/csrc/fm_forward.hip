@@ -21,6 +21,11 @@
 // MODE kSummary: a row's fp64 summary for fm_rank_* (fm_rank.hip): kPredict's entry handling (ids
 // outside the table dropped, x from the batch's stream, the learned entries counted) with kPartial64's
 // stores: S as [row][kp] doubles, {sum v^2 x^2, sum w*x} as a double2 and the count per row.
+// MODE kEvaluate: kPredict's score of every row (the same entry handling and team shapes) subtracted
+// from the row's fp64 label and reduced: each team keeps {rows, rows without a learned entry, sum e,
+// sum |e|, sum e^2} of the rows it walks, in walking order; each block leaves one record, its teams'
+// in team order; k_eval_fold sums a launch's records in an order that depends on their number alone.
+// The score is stored as well when pred is given.
 // (the modes are FwdMode, fm_internal.h; FwdOut::mode names the one a launch runs)
 #include <atomic>
 
@@ -44,6 +49,11 @@ constexpr int kFwdUNarrow = 3;
 // c2 / c5) against 2048 in round 5, c3 0.859-0.863 against 0.867-0.869 ms, c2 0.161-0.163 against
 // 0.163-0.168, c5 0.178-0.181 against 0.182-0.185 (profiles/r05_ab, r05_ac; 1024 and 32768 slower)
 constexpr int kFwdGrid = 8192;
+// the evaluation's blocks at most: every block pays a barrier, a serial sum over its teams and a record
+// that the one-block fold then reads, so fewer blocks than the forward's suit it.  Device time of
+// "evaluate" (forward + fold) at c5 / c3, medians of 3 alternating reps (profiles/eval/grid_ab.json):
+// 8192: 59 / 269 us, 4096: 51 / 275, 2048: 50 / 295, 1024: 59 / 281, 512: 87 / 453
+constexpr int kEvalGrid = 4096;
 // the fused forward (kTrainFused): 5 passes in flight (40 rows per sample at k = 16, so a 39-entry
 // c3 sample takes one round instead of two): round 5 at 4 waves per SIMD, c3 0.869-0.872 against
 // 0.878-0.883 ms for 3 passes, 4 passes slower (profiles/r05_x); round 3 had taken 3 (-2 to -4 %
@@ -273,6 +283,7 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
   constexpr bool PARTIAL = MODE == kPartial || MODE == kPartial64;
   constexpr bool STASH = MODE == kTrainFused;
   constexpr bool SUMMARY = MODE == kSummary;  // predict's entries, the fp64 partial pass's stores
+  constexpr bool SCORE = MODE == kPredict || MODE == kEvaluate;  // predict's entries and its score per row
   using Stash = SingletonStash<GS, TEAM, STASH>;
   constexpr int RPP = TEAM / GS;  // entries per pass
   constexpr int TPB = kBlock / TEAM;
@@ -283,6 +294,17 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
   const int kp = T.kp;
   const bool qok = g * 4 < kp;
   double loss_acc = 0.0, nloss = 0.0;
+  // kEvaluate: the record of each team's rows, kept by its lane tl == 0 -- in LDS: the five fp64 sums
+  // held in registers across the sample loop took the kernel from kPredict's 56-72 VGPRs to 74-92, two
+  // waves per SIMD fewer (or, held to kPredict's occupancy, were spilled to scratch).  Only that lane
+  // reads or writes its team's slot: no barrier until the block's reduction.
+  __shared__ double ev_team[MODE == kEvaluate ? kEvalRec : 1][MODE == kEvaluate ? TPB : 1];
+  if constexpr (MODE == kEvaluate) {
+    if (tl == 0) {
+#pragma unroll
+      for (int c = 0; c < kEvalRec; ++c) ev_team[c][tid / TEAM] = 0.0;
+    }
+  }
 
   // ---- chunk prologue.  kPartial over one chunk of the pairs: the chunk's pairs numbered source by source
   __shared__ int64_t ch_base[PARTIAL ? kMaxChunkSources + 1 : 1], ch_start[PARTIAL ? kMaxChunkSources : 1];
@@ -348,7 +370,7 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
           // the batch's x stream (4 B per entry); the partial pass's entries carry x themselves
           const float xl = PARTIAL ? __uint_as_float(ent[ec].y) : xs[ec];
           id[j] = ok[j] ? idl : 0u;
-          if (MODE == kPredict || SUMMARY) ok[j] = ok[j] && id[j] < (uint64_t)T.rows;
+          if (SCORE || SUMMARY) ok[j] = ok[j] && id[j] < (uint64_t)T.rows;
           x[j] = ok[j] ? xl : 0.f;
         }
       }
@@ -374,7 +396,7 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         float w;
-        if ((MODE == kPredict || PARTIAL || SUMMARY) && g == 0 && h[j].t >= 0) ++npres;
+        if ((SCORE || PARTIAL || SUMMARY) && g == 0 && h[j].t >= 0) ++npres;
         current_row(h[j], v[j], w, cumE);
         if (MODE == kLossGrad && xo.fill_sd > 0.0 && ok[j] && h[j].t < 0) fill_row(xo, T.k, g, eb + j * RPP, v[j], w);
         const double xd = x[j];
@@ -398,7 +420,7 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
     for (int o = 1; o < TEAM; o <<= 1) {
       vv += __shfl_xor(vv, o);
       wx += __shfl_xor(wx, o);
-      if (MODE == kPredict || PARTIAL || SUMMARY) npres += __shfl_xor(npres, o);
+      if (SCORE || PARTIAL || SUMMARY) npres += __shfl_xor(npres, o);
     }
     // ---- the mode's epilogue
     if (PARTIAL || SUMMARY) {  // vectors [pair][kp] in S_out, scalars {sum v^2 x^2, sum w x} in yl_out
@@ -428,6 +450,18 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
       if (tl == 0) xo.pred[s] = npres == 0 ? w0 : fmin(fmax(yhat, xo.lo), xo.hi);
       continue;
     }
+    if constexpr (MODE == kEvaluate) {
+      // predict's score against the row's label, into this thread's record (a row without entries is a
+      // row: it scores w0); the stored prediction is the one that was subtracted
+      if (tl == 0) {
+        EvalAcc row;
+        const double p = eval_row(row, yhat, npres != 0, w0, xo.lo, xo.hi, label[s]);
+        if (xo.pred) xo.pred[s] = p;
+#pragma unroll
+        for (int c = 0; c < kEvalRec; ++c) ev_team[c][tid / TEAM] += row.v[c];
+      }
+      continue;
+    }
     if (MODE == kLossGrad) {
       loss_grad_walk<GS, RPP>(T, col, xs, e0, e1, rs, g, qok, cumE, yhat, label[s], a0, a1, a2, a3, xo);
       continue;
@@ -452,6 +486,32 @@ void k_forward(TableView T, const int64_t* __restrict__ row_ptr, const uint32_t*
   }
   if (STASH) stash.flush(stash.neighbour_pend());  // the last sample's rows (the whole wave active)
   if constexpr (MODE == kTrain || MODE == kTrainFused) block_loss_partial(loss_acc, nloss, loss_part);
+  // the block's record: its teams' sums in team order (it goes where the step's loss partial goes:
+  // loss_part is [blocks][kEvalRec] doubles here)
+  if constexpr (MODE == kEvaluate) {
+    __syncthreads();
+    if (tid == 0) {
+      double* out = reinterpret_cast<double*>(loss_part) + (int64_t)blockIdx.x * kEvalRec;
+#pragma unroll
+      for (int c = 0; c < kEvalRec; ++c) {
+        double sum = 0.0;
+        for (int t = 0; t < TPB; ++t) sum += ev_team[c][t];
+        out[c] = sum;
+      }
+    }
+  }
+}
+
+// The n per-block records of an evaluation launch -> one record (one block): thread t adds the records
+// t, t + kBlock, ... in that order, then the block reduction.  The order depends on n alone.
+__global__ __launch_bounds__(kBlock) void k_eval_fold(const double* __restrict__ part, int64_t n, double* __restrict__ out) {
+  EvalAcc a;
+#pragma unroll 8
+  for (int64_t i = threadIdx.x; i < n; i += kBlock) {  // (unrolled: the records' loads in flight together, added in order)
+#pragma unroll
+    for (int c = 0; c < kEvalRec; ++c) a.v[c] += part[i * kEvalRec + c];
+  }
+  block_eval_partial(a, out);
 }
 
 // The suite's seam (fm_internal.h, set_forward_grid_cap): the block cap in force, 0 = kFwdGrid, and
@@ -475,7 +535,7 @@ void launch_fwd_m(const TableView& T, const BatchDev& b, StepWork& w, const Step
   constexpr int TPB = kBlock / TEAM;
   int64_t blocks = (b.n_rows + TPB - 1) / TPB;
   const int64_t cap = g_grid_cap.load(std::memory_order_relaxed);  // the suite's seam; 0 = the tuned grid
-  const int64_t grid = cap > 0 ? cap : kFwdGrid;
+  const int64_t grid = cap > 0 ? cap : (MODE == kEvaluate ? kEvalGrid : kFwdGrid);
   if (blocks > grid) blocks = grid;
   if (blocks < 1) blocks = 1;
   *nblk = blocks;
@@ -504,10 +564,17 @@ void launch_fwd_m(const TableView& T, const BatchDev& b, StepWork& w, const Step
     loss_part = w.loss_part.as<double2>();
     if (MODE == kTrainFused) xo.sp = p;  // the singleton rows' updates in the forward
   }
-  // the partial pass's entries carry x themselves; labels: the step and loss-grad
+  if (MODE == kEvaluate) {  // one record per block (every block writes its own, also one without rows)
+    // (through the kernel's loss_part argument: a field more in FwdOut moved the scalar registers of
+    // the loss-grad instantiations)
+    w.eval_part.ensure_slack(sizeof(double) * kEvalRec * (size_t)blocks);
+    loss_part = w.eval_part.as<double2>();
+  }
+  // the partial pass's entries carry x themselves; labels: the step, loss-grad and the evaluation
   hipLaunchKernelGGL((k_forward<GS, TEAM, MODE, U>), dim3((unsigned)blocks), dim3(kBlock), 0, st, T,
                      b.row_ptr.as<int64_t>(), b.col.as<uint32_t>(), b.ent.as<uint2>(),
-                     PARTIAL ? nullptr : b.xs.as<float>(), TRAIN || MODE == kLossGrad ? b.label.as<double>() : nullptr,
+                     PARTIAL ? nullptr : b.xs.as<float>(),
+                     TRAIN || MODE == kLossGrad || MODE == kEvaluate ? b.label.as<double>() : nullptr,
                      b.n_rows, p.w0, p.cumE, S_out, yl_out, sstr, ystr, loss_part, xo);
 }
 
@@ -527,6 +594,11 @@ void launch_fwd_t(const TableView& T, const BatchDev& b, StepWork& w, const Step
       // (predict's team shapes only: the partial pass's narrow teams never summarise)
       if constexpr (TEAM >= kFwdTeam) return launch_fwd_m<GS, TEAM, kSummary, U>(T, b, w, p, st, nblk, partial_out, xo);
       else FM_REQUIRE(false, "the row summary takes predict's team shapes");
+      break;
+    case kEvaluate:
+      // (predict's team shapes only, as the row summary)
+      if constexpr (TEAM >= kFwdTeam) return launch_fwd_m<GS, TEAM, kEvaluate, U>(T, b, w, p, st, nblk, partial_out, xo);
+      else FM_REQUIRE(false, "the evaluation takes predict's team shapes");
       break;
     case kLossGrad: return launch_fwd_m<GS, TEAM, kLossGrad, U>(T, b, w, p, st, nblk, partial_out, xo);
     case kTrainFused:
@@ -606,6 +678,28 @@ void launch_predict(const TableView& T, const BatchDev& b, double cumE, double w
   StepWork unused;
   int64_t nblk = 0;
   launch_forward(T, b, unused, p, st, &nblk, nullptr, &xo);
+}
+
+void launch_eval_fold(const double* part, int64_t n_blocks, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_eval_fold, dim3(1), dim3(kBlock), 0, st, part, n_blocks, out);
+  FM_HIP_CHECK(hipGetLastError());
+}
+
+int64_t launch_evaluate(const TableView& T, const BatchDev& b, StepWork& w, double cumE, double w0, double lo, double hi,
+                        double* pred, hipStream_t st) {
+  FM_REQUIRE(T.shard_count == 1, "fm_evaluate needs the whole table (shard_count == 1)");
+  FM_REQUIRE(b.n_rows > 0, "nothing to evaluate");
+  StepParams p{};
+  p.cumE = cumE;
+  p.w0 = w0;
+  FwdOut xo{};
+  xo.mode = kEvaluate;
+  xo.lo = lo;
+  xo.hi = hi;
+  xo.pred = pred;
+  int64_t nblk = 0;
+  launch_forward(T, b, w, p, st, &nblk, nullptr, &xo);
+  return nblk;
 }
 
 void launch_summary(const TableView& T, const BatchDev& b, double cumE, double* summary, uint32_t* present,

@@ -975,8 +975,11 @@ int step_group_batch(fm_ctx* ctx, GroupBatch& gb, int32_t t, double step_size, d
 
 // FactorizationMachinesModel.transform over a sharded table: route (ids outside the model
 // dropped) -> entries to the owners -> owner partial sums with present counts -> back ->
-// predict epilogue per sample.  pred: host [gb.rows].
-void predict_sharded(fm_ctx* ctx, Group& g, GroupBatch& gb, double lo, double hi, double* pred) {
+// predict epilogue per sample.  pred: host [gb.rows].  ev != nullptr (fm_evaluate*): the flow ends
+// in the evaluation epilogue instead -- ev[l] = local rank l's record (zero for a rank without rows),
+// each also appended to its member's own device history -- and pred is optional.
+void predict_sharded(fm_ctx* ctx, Group& g, GroupBatch& gb, double lo, double hi, double* pred,
+                     fm_eval_out* ev = nullptr) {
   const int L = g.L, kp = ctx->kp, W = kp + 2;
   const size_t pw = wire_bytes(ctx);
   gb.prefetched = false;  // the route below replaces any pending training plan of this batch
@@ -1011,12 +1014,48 @@ void predict_sharded(fm_ctx* ctx, Group& g, GroupBatch& gb, double lo, double hi
     Rank& r = g.ranks[l];
     GPart& p = gb.parts[l];
     on(r, [&] {
-      shard_combine_predict(r.m, p.b, r.part_in.p, r.pc_in.as<uint32_t>(), lo, hi, r.pred.as<double>());
-      if (p.rows > 0)
+      if (ev && p.rows > 0)
+        shard_combine_evaluate(r.m, p.b, r.part_in.p, r.pc_in.as<uint32_t>(), lo, hi, pred ? r.pred.as<double>() : nullptr,
+                               eval_next_slot(r.m));
+      else if (!ev)
+        shard_combine_predict(r.m, p.b, r.part_in.p, r.pc_in.as<uint32_t>(), lo, hi, r.pred.as<double>());
+      if (p.rows > 0 && pred)
         FM_HIP_CHECK(hipMemcpyAsync(pred + p.row0, r.pred.p, sizeof(double) * p.rows, hipMemcpyDeviceToHost, r.m->stream));
+      if (ev && p.rows > 0) eval_commit(r.m, &ev[l]);  // waits for the rank's main stream
     });
   }
   for (auto& r : g.ranks) on(r, [&] { FM_HIP_CHECK(hipStreamSynchronize(r.m->stream)); });
+}
+
+// fm_evaluate* on a multi-GPU context: every local rank's record of its part of the batch (replicated:
+// the member's own evaluation; sharded: predict_sharded's flow), added in local-rank order on the
+// host and appended to the context's host-side history.
+int evaluate_group_batch(fm_ctx* ctx, GroupBatch& gb, double lo, double hi, double* pred, fm_eval_out* out) {
+  Group& g = grp(ctx);
+  FM_REQUIRE(out != nullptr,
+             "a multi-GPU context evaluates synchronously: pass out (only a single-table context's fm_evaluate_batch "
+             "enqueues without one)");
+  *out = fm_eval_out{};
+  if (gb.rows == 0) return FM_NOTHING_TO_DO;
+  std::vector<fm_eval_out> ev(g.L, fm_eval_out{});
+  if (g.sharded()) {
+    predict_sharded(ctx, g, gb, lo, hi, pred, ev.data());
+  } else {
+    for (int l = 0; l < g.L; ++l)
+      if (gb.parts[l].rows > 0)
+        mcheck(fm_evaluate_batch(g.ranks[l].m, gb.parts[l].b, lo, hi, pred ? pred + gb.parts[l].row0 : nullptr, &ev[l]),
+               "fm_evaluate_batch");
+  }
+  for (const fm_eval_out& e : ev) {
+    out->n_rows += e.n_rows;
+    out->n_unlearned += e.n_unlearned;
+    out->sum_err += e.sum_err;
+    out->sum_abs_err += e.sum_abs_err;
+    out->sum_sq_err += e.sum_sq_err;
+  }
+  out->epoch = ctx->epoch;
+  ctx->eval_host.push_back(*out);
+  return FM_OK;
 }
 
 void predict_group_batch(fm_ctx* ctx, GroupBatch& gb, double lo, double hi, double* pred) {
@@ -1409,6 +1448,18 @@ int group_predict_batch(fm_ctx* ctx, fm_batch* b, double lo, double hi, double* 
   FM_REQUIRE(b == nullptr || b->split_rows.empty(), "a dataset made by fm_batch_create_splits is predicted by split");
   predict_group_batch(ctx, gbatch(ctx, b), lo, hi, pred);
   return FM_OK;
+}
+
+int group_evaluate(fm_ctx* ctx, const fm_csr* csr, double lo, double hi, double* pred, fm_eval_out* out) {
+  FM_REQUIRE(csr != nullptr, "null argument");
+  fm_batch* b = host_slot(ctx);
+  upload_parts(grp(ctx), csr, b, false);
+  return evaluate_group_batch(ctx, *b->grp, lo, hi, pred, out);
+}
+
+int group_evaluate_batch(fm_ctx* ctx, fm_batch* b, double lo, double hi, double* pred, fm_eval_out* out) {
+  FM_REQUIRE(b == nullptr || b->split_rows.empty(), "a dataset made by fm_batch_create_splits is evaluated by split");
+  return evaluate_group_batch(ctx, gbatch(ctx, b), lo, hi, pred, out);
 }
 
 int group_load_tables(fm_ctx* ctx, const int32_t* ids, int64_t n, const double* w, const double* V) {

@@ -187,6 +187,7 @@ struct StepWork {
   DevBuf loss_part; // [n_fwd_blocks] double2 {loss, n_loss}
   DevBuf part;      // [ceil(N / 256) * 2 * (kp+2)] double partial gradients (one range per update wave)
   DevBuf ucnt;      // [n_update_blocks] uint32 distinct-id counts per block
+  DevBuf eval_part; // [n_eval_blocks][kEvalRec] double: an evaluation's per-block records (grown to the largest launch)
   SortWork sort;
 };
 
@@ -206,12 +207,19 @@ struct StepParams {
 // fused in; the sharded owner's partial pass with the fp32 or the fp64 wire; predict (clamp bounds,
 // fp64 score per sample into pred); calcLossGrad (fp64 pred / loss / dw per entry, dv [entries][k],
 // the absent-id flag); a row's fp64 summary for ranking (predict's entry handling, the fp64 partial
-// pass's stores: S, {sum v^2 x^2, sum w x} and the learned-entry count per row)
-enum FwdMode : int { kTrain = 0, kPartial = 1, kPredict = 2, kLossGrad = 3, kTrainFused = 4, kPartial64 = 5, kSummary = 6 };
+// pass's stores: S, {sum v^2 x^2, sum w x} and the learned-entry count per row); evaluation (predict's
+// score of every row reduced against its fp64 label into one kEvalRec record per block, and stored as
+// well if pred is given)
+enum FwdMode : int {
+  kTrain = 0, kPartial = 1, kPredict = 2, kLossGrad = 3, kTrainFused = 4, kPartial64 = 5, kSummary = 6, kEvaluate = 7
+};
+// doubles of an evaluation record: {rows, rows without a learned entry, sum e, sum |e|, sum e^2},
+// e = label - prediction (fm_device.h, EvalAcc)
+constexpr int kEvalRec = 5;
 struct FwdOut {
   int mode = kTrain;  // a FwdMode; launch_forward sets the partial modes itself (partial_out / partial_wide)
   double lo = 0.0, hi = 0.0;
-  double* pred = nullptr;
+  double* pred = nullptr;  // kEvaluate: optional (the prediction that was subtracted from the label)
   double* loss = nullptr;
   double* dw = nullptr;
   double* dv = nullptr;
@@ -322,6 +330,16 @@ void launch_gather_rows(const TableView& T, const int32_t* ids, int64_t n, doubl
 void launch_table_reset(const TableView& T, hipStream_t st);
 void launch_predict(const TableView& T, const BatchDev& b, double cumE, double w0, double lo, double hi,
                     double* pred, hipStream_t st);
+// fm_evaluate*: predict's score of every row against its label, reduced on the device.  The forward
+// (team shapes and entry handling of launch_predict; b.n_rows > 0) leaves one record per block in
+// w.eval_part and returns the number of blocks; launch_eval_fold sums the n_blocks records of a launch
+// (of the forward, or of the sharded requester's k_shard_evaluate) into out[kEvalRec] (device): one
+// block, thread t the records t, t + kBlock, ... in order, then the block reduction -- an order that
+// depends on n_blocks alone.  pred (device, optional): the predictions.  No atomics: equal inputs give
+// equal bits.
+int64_t launch_evaluate(const TableView& T, const BatchDev& b, StepWork& w, double cumE, double w0, double lo, double hi,
+                        double* pred, hipStream_t st);
+void launch_eval_fold(const double* part, int64_t n_blocks, double* out, hipStream_t st);
 // fm_rank_*: every row's summary (FwdOut::summary's layout) and its count of learned entries, with
 // predict's team shapes; ids outside the table or absent from the model contribute nothing
 void launch_summary(const TableView& T, const BatchDev& b, double cumE, double* summary, uint32_t* present,

@@ -512,6 +512,33 @@ __global__ __launch_bounds__(kBlock) void k_shard_predict(const int32_t* __restr
   }
 }
 
+// k_shard_predict's scores against this rank's labels, reduced (fm_evaluate* over a sharded table): each
+// team's lane 0 adds its rows to its thread's record, each block leaves one record in part
+// [gridDim.x][kEvalRec] (block_eval_partial), folded by launch_eval_fold; pred (optional) gets the
+// score that was subtracted.
+template <int GS, typename W>
+__global__ __launch_bounds__(kBlock) void k_shard_evaluate(const int32_t* __restrict__ pairidx,
+                                                           const int64_t* __restrict__ poff, int R, int64_t B,
+                                                           const W* __restrict__ part_vec,
+                                                           const wire2<W>* __restrict__ part_sc, int kp, double w0,
+                                                           const uint32_t* __restrict__ pcnt, double lo, double hi,
+                                                           const double* __restrict__ label, double* __restrict__ pred,
+                                                           double* __restrict__ part) {
+  constexpr int TPB = kBlock / GS;
+  const int tid = threadIdx.x, g = tid % GS;
+  const ReqIn<W> in{poff, part_vec, part_sc, kp, w0};
+  EvalAcc ev;
+  for (int64_t s = (int64_t)blockIdx.x * TPB + tid / GS; s < B; s += (int64_t)gridDim.x * TPB) {
+    uint32_t cnt = 0;
+    const double yhat = sample_yhat<GS, false>(OwnerWalk{pairidx + s * R, poff, R}, in, g, pcnt, nullptr, cnt);
+    if (g == 0) {
+      const double p = eval_row(ev, yhat, cnt != 0, w0, lo, hi, label[s]);
+      if (pred) pred[s] = p;
+    }
+  }
+  block_eval_partial(ev, part + (int64_t)blockIdx.x * kEvalRec);
+}
+
 inline int team_for(int nq) {
   int G = 1;
   while (G < nq && G < 16) G <<= 1;
@@ -580,20 +607,23 @@ ShardBatchState& shard_state(fm_ctx* ctx, fm_batch* b) {
 constexpr int kSlotRegs = 8;  // up to this many owners the combine keeps the sample's pair slots in registers
 
 // The requester kernel of a wire and team width: the combine (slots in registers or owner by
-// owner) or the predict (owner by owner).  For one W and kind every instantiation has one type.
-template <int GS, typename W, bool kPredict>
+// owner), the predict or the evaluation (owner by owner).  For one W and kind every instantiation
+// has one type.
+enum ReqKind : int { kReqCombine = 0, kReqPredict = 1, kReqEvaluate = 2 };
+template <int GS, typename W, int KIND>
 auto requester_kernel_g(int R) {
-  if constexpr (kPredict) return &k_shard_predict<GS, W>;
+  if constexpr (KIND == kReqPredict) return &k_shard_predict<GS, W>;
+  else if constexpr (KIND == kReqEvaluate) return &k_shard_evaluate<GS, W>;
   else return R <= kSlotRegs ? &k_shard_combine<GS, kSlotRegs, W> : &k_shard_combine<GS, 0, W>;
 }
-template <typename W, bool kPredict>
+template <typename W, int KIND>
 auto requester_kernel(int GS, int R) {
   switch (GS) {
-    case 1: return requester_kernel_g<1, W, kPredict>(R);
-    case 2: return requester_kernel_g<2, W, kPredict>(R);
-    case 4: return requester_kernel_g<4, W, kPredict>(R);
-    case 8: return requester_kernel_g<8, W, kPredict>(R);
-    default: return requester_kernel_g<16, W, kPredict>(R);
+    case 1: return requester_kernel_g<1, W, KIND>(R);
+    case 2: return requester_kernel_g<2, W, KIND>(R);
+    case 4: return requester_kernel_g<4, W, KIND>(R);
+    case 8: return requester_kernel_g<8, W, KIND>(R);
+    default: return requester_kernel_g<16, W, KIND>(R);
   }
 }
 
@@ -628,14 +658,14 @@ ReqPlan requester_plan(fm_ctx* ctx, fm_batch* b, const ShardBatchState& S) {
   return q;
 }
 
-// The combine or predict kernel of the context's wire on the main stream; tail: the kernel's own
-// arguments after the ones both take.
-template <bool kPredict, typename... Tail>
+// The combine, predict or evaluation kernel of the context's wire on the main stream; tail: the
+// kernel's own arguments after the ones all take.
+template <int KIND, typename... Tail>
 void launch_requester(fm_ctx* ctx, const ReqPlan& q, const void* partials_in, Tail... tail) {
   auto go = [&](auto word) {
     using W = decltype(word);
     const W* vec = reinterpret_cast<const W*>(partials_in);
-    auto kern = requester_kernel<W, kPredict>(q.GS, q.R);
+    auto kern = requester_kernel<W, KIND>(q.GS, q.R);
     hipLaunchKernelGGL(kern, dim3(q.blocks), dim3(kBlock), 0, ctx->stream, q.pi, q.poff, q.R, q.B, vec,
                        wire_scalars<const wire2<W>>(vec, q.Ps, q.kp), q.kp, ctx->cfg.w0, tail...);
   };
@@ -880,7 +910,21 @@ void shard_combine_predict(fm_ctx* ctx, fm_batch* b, const void* partials_in, co
   const ReqPlan q = requester_plan(ctx, b, shard_state(ctx, b));
   if (q.B == 0) return;
   FM_REQUIRE(q.Ps == 0 || (partials_in && present_in), "null buffer");
-  launch_requester<true>(ctx, q, partials_in, present_in, lo, hi, pred_dev);
+  launch_requester<kReqPredict>(ctx, q, partials_in, present_in, lo, hi, pred_dev);
+}
+
+void shard_combine_evaluate(fm_ctx* ctx, fm_batch* b, const void* partials_in, const uint32_t* present_in,
+                            double lo, double hi, double* pred_dev, double* rec_dev) {
+  const ReqPlan q = requester_plan(ctx, b, shard_state(ctx, b));
+  if (q.B == 0) return;
+  FM_REQUIRE(q.Ps == 0 || (partials_in && present_in), "null buffer");
+  FM_REQUIRE(rec_dev != nullptr, "null buffer");
+  hipEvent_t e0 = ctx->prof_begin(ctx->stream);
+  ctx->work.eval_part.ensure_slack(sizeof(double) * kEvalRec * kLossPartBlocks);  // the grid's cap: no growth later
+  launch_requester<kReqEvaluate>(ctx, q, partials_in, present_in, lo, hi, b->dev.label.as<const double>(), pred_dev,
+                                 ctx->work.eval_part.as<double>());
+  launch_eval_fold(ctx->work.eval_part.as<double>(), q.blocks, rec_dev, ctx->stream);
+  ctx->prof_end("evaluate", e0, ctx->stream);
 }
 
 }  // namespace fmhip
@@ -896,7 +940,7 @@ int fm_shard_combine(fm_ctx* ctx, fm_batch* b, const void* partials_in, void* s_
     hipEvent_t e0 = ctx->prof_begin(st);
     ctx->work.loss_part.ensure(sizeof(double2) * kLossPartBlocks);  // reserve_work's size: no reallocation later
     float* s_vec = reinterpret_cast<float*>(s_send);
-    launch_requester<false>(ctx, q, partials_in, b->dev.label.as<double>(), s_vec,
+    launch_requester<kReqCombine>(ctx, q, partials_in, b->dev.label.as<double>(), s_vec,
                             wire_scalars<float2>(s_vec, q.Ps, q.kp), ctx->work.loss_part.as<double2>());
     ctx->prof_end("combine", e0, st);
     S.loss_blocks = q.blocks;

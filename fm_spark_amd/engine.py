@@ -22,6 +22,47 @@ class StepOut:
     executed: bool = True
 
 
+@dataclass(frozen=True)
+class EvalSums:
+    """One evaluation record (fm_eval_out): the sums of e = label - prediction over the rows of a
+    batch, formed on the device in fp64, and the metrics RegressionEvaluator derives from them."""
+
+    n_rows: int
+    n_unlearned: int
+    epoch: int
+    sum_err: float
+    sum_abs_err: float
+    sum_sq_err: float
+    executed: bool = True
+
+    @staticmethod
+    def from_struct(o: "N.fm_eval_out", executed: bool = True) -> "EvalSums":
+        return EvalSums(int(o.n_rows), int(o.n_unlearned), int(o.epoch), float(o.sum_err), float(o.sum_abs_err),
+                        float(o.sum_sq_err), executed)
+
+    @property
+    def mae(self) -> float:
+        return self.sum_abs_err / self.n_rows
+
+    @property
+    def mse(self) -> float:
+        return self.sum_sq_err / self.n_rows
+
+    @property
+    def rmse(self) -> float:
+        return float(np.sqrt(self.mse))
+
+    @property
+    def bias(self) -> float:
+        """mean (label - prediction)"""
+        return self.sum_err / self.n_rows
+
+    def r2(self, ss_tot: float) -> float:
+        """1 - SS_err / SS_tot; SS_tot = sum (y - mean y)^2 comes from the caller's labels (two-pass,
+        on the host: include/fm_hip.h, fm_eval_out)."""
+        return 1.0 - self.sum_sq_err / ss_tot
+
+
 class DeviceBatch:
     """A CSR mini-batch resident in HBM (fm_batch_create)."""
 
@@ -318,6 +359,43 @@ class FMContext:
         N.check(self._lib.fm_predict_batch(self.handle, b.handle, float(min_label), float(max_label),
                                            N.ptr(out, C.c_double)), "fm_predict_batch")
         return out[: b.n_rows]
+
+    def evaluate(self, csr: N.CSRHost, min_label: float, max_label: float, want_pred: bool = False):
+        """The error sums of predict(csr) against csr's labels, reduced on the device (fm_evaluate):
+        EvalSums, or (EvalSums, predictions) with want_pred."""
+        return self._evaluate(self._lib.fm_evaluate, "fm_evaluate", C.byref(csr.c), csr.n_rows, min_label, max_label,
+                              True, want_pred)
+
+    def evaluate_batch(self, b: DeviceBatch, min_label: float, max_label: float, sync: bool = True,
+                       want_pred: bool = False):
+        """The same over a device-resident batch (fm_evaluate_batch).  sync=False only enqueues (a
+        single-table context; the record is read later through eval_history) and returns None."""
+        if not sync and want_pred:
+            raise ValueError("want_pred needs sync=True")
+        return self._evaluate(self._lib.fm_evaluate_batch, "fm_evaluate_batch", b.handle, b.n_rows, min_label,
+                              max_label, sync, want_pred)
+
+    def _evaluate(self, fn, what, rows, n_rows, min_label, max_label, sync, want_pred):
+        pred = np.zeros(max(n_rows, 1)) if want_pred else None
+        pp = N.ptr(pred, C.c_double) if want_pred else None
+        if not sync:
+            N.check(fn(self.handle, rows, float(min_label), float(max_label), None, None), what)
+            return None
+        out = N.fm_eval_out()
+        rc = N.check(fn(self.handle, rows, float(min_label), float(max_label), pp, C.byref(out)), what)
+        sums = EvalSums.from_struct(out, executed=rc != N.FM_NOTHING_TO_DO)
+        return (sums, pred[:n_rows]) if want_pred else sums
+
+    def eval_history(self) -> list:
+        """Every evaluation record of this context so far, in order (fm_eval_history; waits for the
+        main stream)."""
+        n = C.c_int64()
+        N.check(self._lib.fm_eval_history(self.handle, None, 0, C.byref(n)), "fm_eval_history")
+        if not n.value:
+            return []
+        buf = (N.fm_eval_out * n.value)()
+        N.check(self._lib.fm_eval_history(self.handle, buf, n.value, C.byref(n)), "fm_eval_history")
+        return [EvalSums.from_struct(o) for o in buf[: n.value]]
 
     def rank(self, contexts: N.CSRHost, candidates: N.CSRHost, n_top: int, min_label: float, max_label: float):
         """For every context row the n_top candidate rows with the largest FM score of the two rows'

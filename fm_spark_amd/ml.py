@@ -26,7 +26,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _native as N
-from .engine import FMContext
+from .engine import EvalSums, FMContext
 from .linalg import DenseVector, Vector, Vectors, active_map
 
 log = logging.getLogger("org.apache.spark.ml.fm")
@@ -167,6 +167,8 @@ class FactorizationMachinesModel:
         self._params = {"sampleIdCol": "sampleId", "featuresCol": "features", "predictionCol": "prediction",
                         "labelCol": "label", "minLabel": 0.0, "maxLabel": 1.0}  # Model.scala:54-61
         self.parent = None
+        # fit with setValidationData: [(iteration, EvalSums)] of the held-out frame during the fit
+        self.validationHistory = []
         if ctx is not None:
             self._ctx = ctx
         else:
@@ -204,6 +206,7 @@ class FactorizationMachinesModel:
         m._params = dict(self._params)
         m._params.update(extra or {})
         m.parent = self.parent
+        m.validationHistory = list(self.validationHistory)
         return m
 
     # tables ------------------------------------------------------------------------------
@@ -230,6 +233,17 @@ class FactorizationMachinesModel:
         csr = N.CSRHost(rp, col, val, np.zeros(dataset.count()))
         pred = self._ctx.predict(csr, self.getMinLabel(), self.getMaxLabel())
         return dataset.with_column(self._params["predictionCol"], [float(p) for p in pred])
+
+    def evaluate(self, dataset: DataFrame) -> EvalSums:
+        """The error sums of transform(dataset) against labelCol, reduced on the device in one pass
+        (fm_evaluate): no prediction column is built or downloaded.  The predictions are transform's
+        (clamped to [minLabel, maxLabel], globalBias for a row without a learned feature); mae, mse,
+        rmse and bias are properties of the result, r2 takes SS_tot from the caller's labels."""
+        fcol, lcol = self._params["featuresCol"], self._params["labelCol"]
+        _check_schema(dataset, fcol, lcol)
+        rp, col, val = _explode(dataset[fcol])
+        csr = N.CSRHost(rp, col, val, np.asarray(dataset[lcol], dtype=np.float64))
+        return self._ctx.evaluate(csr, self.getMinLabel(), self.getMaxLabel())
 
     def recommend(self, contexts: DataFrame, candidates: DataFrame, numItems: int) -> DataFrame:
         """The numItems best rows of `candidates` for every row of `contexts` (the shape of
@@ -308,6 +322,8 @@ class FactorizationMachinesSGD:
         # not in the reference: the table over several GPUs of this process (include/fm_hip.h
         # fm_config.parallel), in place of Spark's hash-partitioned model Datasets
         "parallel": None, "nGpus": 1, "devices": None, "transport": "auto", "wire": "fp32",
+        # not in the reference: a held-out frame evaluated on the device during fit, (frame, every)
+        "validationData": None,
     }
 
     def __init__(self, uid: str | None = None):
@@ -350,6 +366,21 @@ class FactorizationMachinesSGD:
         self._set("nGpus", int(n_gpus))
         self._set("devices", None if devices is None else [int(d) for d in devices])
         return self._set("transport", transport)
+
+    def setValidationData(self, dataset: DataFrame | None, every: int = 1):
+        """A held-out frame (featuresCol, labelCol) evaluated during fit, on the device: after every
+        `every`-th executed iteration and after the last, its error sums against the model as it
+        stands (FactorizationMachinesModel.evaluate's, clamped to this estimator's [minLabel,
+        maxLabel]) are appended to the fitted model's ``validationHistory`` as (iteration, EvalSums),
+        and one log line per entry follows the loss lines.  The frame is uploaded once; ids the
+        training data lacks drop out, as in transform.  The pipelined fit only enqueues the
+        evaluations (fm_evaluate_batch without out) and reads them when the loop has run; the
+        synchronous fit and multi-GPU estimators evaluate synchronously.  None (default): off."""
+        if dataset is None:
+            return self._set("validationData", None)
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or int(every) < 1:
+            raise ValueError("every must be an integer >= 1")
+        return self._set("validationData", (dataset, int(every)))
 
     def getDimFactorization(self): return self._params["dimFactorization"]
     def getMaxIter(self): return self._params["maxIter"]
@@ -437,13 +468,20 @@ class FactorizationMachinesSGD:
             # createInitialModel (:224-241): the draw for every distinct active feature id, on the
             # device over the whole dataset's entries
             ctx.init_from_batch(data)
+        val_run = None
+        if p["validationData"] is not None:
+            val_run = _Validation.upload(ctx, p["validationData"], p["featuresCol"], p["labelCol"], F, p["minLabel"],
+                                         p["maxLabel"])
         if pipelined:
             if data is not None:
-                run_minibatch_sgd_splits(ctx, data, p["stepSize"], p["regParam"], n_iter=p["maxIter"])
+                run_minibatch_sgd_splits(ctx, data, p["stepSize"], p["regParam"], n_iter=p["maxIter"],
+                                         validation=val_run)
             else:
                 for i in range(p["maxIter"]):
                     log.warning("Iteration (%d/%d). The size of sampled batch is zero", i + 1, p["maxIter"])
         else:
+            n_exec = sum(1 for rows in splits if len(rows))
+            j = 0
             for i, rows in enumerate(splits):
                 it = i + 1  # iter = index + 1 (:119)
                 if len(rows) == 0:
@@ -452,10 +490,73 @@ class FactorizationMachinesSGD:
                 csr = _select_csr(rp, col, val, labels, rows)
                 out = ctx.step(csr, it, p["stepSize"], p["regParam"])
                 log.info("Loss of Iteration (%d/%d): %s", it, p["maxIter"], out.loss_sum)
+                j += 1
+                if val_run is not None and val_run.due(j, n_exec):
+                    val_run.evaluate(ctx, it, sync=True)
+            if val_run is not None:
+                val_run.finish(ctx, p["maxIter"])
         model = FactorizationMachinesModel(self.uid, k, 0.0, ctx=ctx)
         model.setMinLabel(p["minLabel"]).setMaxLabel(p["maxLabel"])
         model.parent = self
+        if val_run is not None:
+            model.validationHistory = val_run.history
+            val_run.close()
         return model
+
+
+class _Validation:
+    """fit's held-out frame (setValidationData): one device batch of the fit's context, the iterations
+    at which it was evaluated and, once the loop has run, their records."""
+
+    def __init__(self, batch, lo: float, hi: float, every: int):
+        self.batch, self.lo, self.hi, self.every = batch, lo, hi, every
+        self.history = []   # [(iteration, EvalSums)]
+        self._queued = []   # iterations whose evaluation was only enqueued
+        self._h0 = 0        # the context's evaluation records before this fit's first
+
+    @staticmethod
+    def upload(ctx: FMContext, spec, features_col: str, label_col: str, num_features: int, lo: float, hi: float):
+        df, every = spec
+        _check_schema(df, features_col, label_col)
+        rp, col, val = _explode(df[features_col])
+        # ids the table cannot hold are dropped by the evaluation as by transform; the upload of a
+        # resident batch refuses them, so they drop out here
+        keep = col < num_features
+        if not keep.all():
+            rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))[keep]
+            rp = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=len(rp) - 1))]).astype(np.int64)
+            col, val = col[keep], val[keep]
+        y = np.asarray(df[label_col], dtype=np.float64)
+        batch = ctx.batch(N.CSRHost(rp, col, val, y)) if len(y) else None
+        v = _Validation(batch, float(lo), float(hi), every)
+        v._h0 = len(ctx.eval_history())
+        return v
+
+    def due(self, n_done: int, n_total: int) -> bool:
+        """after the n_done-th executed iteration of n_total"""
+        return self.batch is not None and (n_done % self.every == 0 or n_done == n_total)
+
+    def evaluate(self, ctx: FMContext, iteration: int, sync: bool):
+        if sync:
+            self.history.append((iteration, ctx.evaluate_batch(self.batch, self.lo, self.hi)))
+        else:
+            ctx.evaluate_batch(self.batch, self.lo, self.hi, sync=False)
+            self._queued.append(iteration)
+
+    def finish(self, ctx: FMContext, n_iter: int):
+        """The enqueued evaluations' records read (one host synchronisation), and the log lines."""
+        if self._queued:
+            recs = ctx.eval_history()[self._h0:]
+            self.history.extend(zip(self._queued, recs))
+            self._queued = []
+        for it, s in self.history:
+            log.info("Validation of Iteration (%d/%d): mae %s rmse %s bias %s (%d rows, %d without a learned feature)",
+                     it, n_iter, s.mae, s.rmse, s.bias, s.n_rows, s.n_unlearned)
+
+    def close(self):
+        if self.batch is not None:
+            self.batch.close()
+            self.batch = None
 
 
 def _select_csr(rp, col, val, labels, rows) -> N.CSRHost:
@@ -526,7 +627,7 @@ def _log_losses(ctx, e0, iters, n_splits, n_iter):
 
 
 def run_minibatch_sgd_splits(ctx: FMContext, data, step_size: float, reg_param: float, n_iter: int | None = None,
-                             bufs: list | None = None):
+                             bufs: list | None = None, validation: "_Validation | None" = None):
     """The foldLeft of runMiniBatchSGD (FactorizationMachinesSGD.scala:114-211) over a dataset kept on
     the device laid out split after split (`data`, FMContext.batch_splits: dfData.cache() at :93 with
     the randomSplit splits of :111-112 in iteration order): iteration i steps split i in place
@@ -536,7 +637,10 @@ def run_minibatch_sgd_splits(ctx: FMContext, data, step_size: float, reg_param: 
     written in iteration order after the loop.  n_iter: the iterations are splits 0 .. n_iter - 1
     (default: every split; fit's dataset ends with a split of the rows no iteration samples and
     passes maxIter).  `bufs`: a list of two views (or Nones) to re-point and leave open for the
-    caller.  Returns the loss sums of the executed iterations."""
+    caller.  `validation` (fit's setValidationData): its frame is evaluated between the steps it names,
+    on the main stream behind the step -- enqueued only on a single-table context (the records are
+    read once, after the loop), synchronously on a multi-GPU one; its log lines follow the loss
+    lines.  Returns the loss sums of the executed iterations."""
     sizes = np.diff(np.asarray(data.split_rows))
     n_iter = len(sizes) if n_iter is None else int(n_iter)
     if n_iter > len(sizes):
@@ -559,8 +663,12 @@ def run_minibatch_sgd_splits(ctx: FMContext, data, step_size: float, reg_param: 
         if j + 1 < len(work):
             view(j + 1)  # re-points the batch step j - 1 read (its sort waits for that step)
             bufs[(j + 1) % nb].prepare()  # sorted on the side stream while this step runs
+        if validation is not None and validation.due(j + 1, len(work)):
+            validation.evaluate(ctx, i + 1, sync=ctx.parallel is not None)
     ctx.sync()
     out = _log_losses(ctx, e0, work, n_iter, n_iter)
+    if validation is not None:
+        validation.finish(ctx, n_iter)
     if own:
         for b in bufs:
             if b is not None:

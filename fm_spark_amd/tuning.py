@@ -116,6 +116,22 @@ class RegressionEvaluator:
         ss_tot = float(np.sum((y - y.mean()) ** 2))
         return 1.0 - float(np.sum(err * err)) / ss_tot  # r2
 
+    def evaluateModel(self, model, dataset: DataFrame) -> float:
+        """The metric of model.transform(dataset) from the error sums the device reduces
+        (model.evaluate -> fm_evaluate): no prediction column is built.  The model's labelCol is the
+        label; r2 takes SS_tot from the frame's labels here, with evaluate's two-pass formula.  The
+        value differs from evaluate(model.transform(dataset)) by the summation order only."""
+        s = model.evaluate(dataset)
+        m = self._params["metricName"]
+        if m == "mae":
+            return float(s.mae)
+        if m == "mse":
+            return float(s.mse)
+        if m == "rmse":
+            return float(s.rmse)
+        y = np.asarray(dataset[model._params["labelCol"]], dtype=np.float64)
+        return float(s.r2(float(np.sum((y - y.mean()) ** 2))))
+
 
 def k_fold(dataset: DataFrame, num_folds: int, seed: int):
     """MLUtils.kFold replay: [(training, validation)] per fold, partitions preserved."""
@@ -166,6 +182,17 @@ class CrossValidator:
         self.uid = uid or "cv"
         self._params = {"numFolds": 3, "seed": java_string_hash("org.apache.spark.ml.tuning.CrossValidator")}
         self._est = self._epm = self._eval = None
+        self._on_device = False
+
+    def setEvaluateOnDevice(self, value: bool):
+        """True: each fold's metric comes from evaluator.evaluateModel(model, validation) -- the error
+        sums reduced on the device -- instead of evaluator.evaluate(model.transform(validation)).
+        Default False: the two differ in summation order, so the default path stays as it is."""
+        self._on_device = bool(value)
+        return self
+
+    def getEvaluateOnDevice(self) -> bool:
+        return self._on_device
 
     def setEstimator(self, est):
         self._est = est
@@ -199,7 +226,10 @@ class CrossValidator:
             for i, pm in enumerate(epm):
                 model = est.copy(pm).fit(training)
                 mparams = {k: v for k, v in pm.items() if k in model._params}  # copyValues: the model's own params
-                metrics[i] += ev.evaluate(model.copy(mparams).transform(validation))
+                if self._on_device:
+                    metrics[i] += ev.evaluateModel(model.copy(mparams), validation)
+                else:
+                    metrics[i] += ev.evaluate(model.copy(mparams).transform(validation))
         metrics /= self._params["numFolds"]
         best = int(np.argmax(metrics)) if ev.isLargerBetter() else int(np.argmin(metrics))
         best_model = est.copy(epm[best]).fit(dataset)

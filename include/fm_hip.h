@@ -307,6 +307,55 @@ int fm_predict(fm_ctx* ctx, const fm_csr* csr, double min_label, double max_labe
 /* The same on a device-resident batch (fm_batch_create): transform over a cached DataFrame
  * without re-uploading it.  pred is a host buffer of fm_batch_rows(batch) doubles. */
 int fm_predict_batch(fm_ctx* ctx, fm_batch* batch, double min_label, double max_label, double* pred);
+/* Evaluation on the device: the sums RegressionEvaluator / RegressionMetrics take over (prediction,
+ * label) -- FactorizationMachinesSample.scala:41-70 drives a CrossValidator over
+ * RegressionEvaluator("mae") -- without downloading the predictions.  prediction is fm_predict's value
+ * for the row (ids >= num_features or absent dropped, lazy L1 caught up on read, w0 unclamped for a
+ * row without a learned entry, else clamp(yhat, min_label, max_label)); the errors e = label -
+ * prediction are formed and summed in fp64.  A row without entries is a row: it scores w0 and counts
+ * in n_rows and n_unlearned (transform's rule, not the training loss's).
+ *   sums  : reduced in a fixed order (per thread, per block, then one fold over the blocks), no
+ *           atomics: two evaluations of the same batch on the same table give bitwise equal records.
+ *           The order differs from a host sum over the predictions by fp64 rounding only.
+ *   labels: the label moments are deliberately not reduced here.  r2's SS_tot formed from sum y and
+ *           sum y^2 cancels; the labels are host data wherever a frame exists, so the caller computes
+ *           SS_tot there with the two-pass formula, and r2 = 1 - sum_sq_err / SS_tot.
+ *   pred  : optional host buffer of n_rows doubles -- transform and evaluate in one pass; the value
+ *           stored for a row is the one that was subtracted from its label.
+ *   history: every evaluation of a non-empty batch appends one record to the context's evaluation
+ *           history (fm_eval_history), which stays on the device until asked for, as the loss
+ *           history.  fm_evaluate_batch with out == NULL and pred == NULL only enqueues (no host
+ *           synchronisation: a validation curve during a pipelined fit); out == NULL with pred !=
+ *           NULL is FM_ERR_ARG.  fm_eval_history waits for the main stream; call it with cap 0 to
+ *           size (*n = records so far).
+ *   order : on the main stream behind every queued step; a batch refilled by fm_batch_from_rows is
+ *           waited for.  The table, the epoch, the loss history and fm_last_stats are unchanged.
+ *   arguments : zero rows: FM_NOTHING_TO_DO, *out zeroed, nothing appended.  A dataset made by
+ *           fm_batch_create_splits is FM_ERR_ARG (evaluated by split: its split views are accepted).
+ *           A null or foreign batch, a null context and the CSR are treated as by fm_predict.
+ *   memory: the history starts at 4096 records and doubles; the per-block records and the
+ *           synchronous call's device predictions are kept with the context and grow to the largest
+ *           call (two equal calls leave fm_device_bytes_live / fm_device_allocs_live equal).
+ *   multi-GPU : synchronous only -- out == NULL is FM_ERR_ARG ("a multi-GPU context evaluates
+ *           synchronously").  Replicated: every local rank evaluates its part of the batch; sharded:
+ *           fm_predict's route -> owner partials -> exchange, ending in the evaluation instead of the
+ *           predict epilogue.  The ranks' records are added on the host in local-rank order and kept
+ *           in a host-side history that fm_eval_history answers; pred is placed as fm_predict places
+ *           it.  With n_procs > 1 a call evaluates this process's rows only, as fm_predict does.  The
+ *           manual fm_shard_* phases have no evaluation phase.
+ * Profile name: "evaluate" (the kernel and the fold). */
+typedef struct fm_eval_out {
+  int64_t n_rows;       /* rows evaluated (every row of the batch, empty rows included) */
+  int64_t n_unlearned;  /* of those, rows without a learned entry: predicted w0, unclamped */
+  int64_t epoch;        /* fm_epoch() when the evaluation was enqueued */
+  double sum_err;       /* sum (label - prediction) */
+  double sum_abs_err;   /* sum |label - prediction|  -> mae  = / n_rows */
+  double sum_sq_err;    /* sum (label - prediction)^2 -> mse, rmse; r2's SS_err */
+} fm_eval_out;
+int fm_evaluate(fm_ctx* ctx, const fm_csr* csr, double min_label, double max_label, double* pred, fm_eval_out* out);
+int fm_evaluate_batch(fm_ctx* ctx, fm_batch* batch, double min_label, double max_label, double* pred,
+                      fm_eval_out* out);
+int fm_eval_history(fm_ctx* ctx, fm_eval_out* out, int64_t cap, int64_t* n);
 /* Top-N ranking, the serving side of transform (the shape of ALSModel.recommendForUserSubset): for
  * every row of `contexts` (a user and their history, a page view) the n_top rows of `candidates`
  * (movies, ads) with the largest FM score of the two rows' entries taken together, without
