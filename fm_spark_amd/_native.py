@@ -22,6 +22,7 @@ FM_MAX_LOCAL = 16
 FM_FUSE_DEFAULT, FM_FUSE_ON, FM_FUSE_OFF = 0, 1, -1
 FM_WIRE_FP32, FM_WIRE_FP64 = 0, 1
 FM_RANK_MAX_TOP = 1024
+FM_RANK_SELECT_ALL, FM_RANK_SELECT_ONLY, FM_RANK_SELECT_EXCEPT = 0, 1, 2
 
 
 class FMError(RuntimeError):
@@ -124,6 +125,10 @@ SIGNATURES = {
     "fm_rank_candidates": (C.c_int, [_P, C.POINTER(fm_csr), C.POINTER(fm_csr), C.c_int32, C.c_double, C.c_double,
                                      _I32P, _DP]),
     "fm_rank_batch": (C.c_int, [_P, _P, _P, C.c_int32, C.c_double, C.c_double, _I32P, _DP]),
+    "fm_rank_candidates_select": (C.c_int, [_P, C.POINTER(fm_csr), C.POINTER(fm_csr), C.c_int32, _I64P, _I32P, C.c_int32,
+                                            C.c_double, C.c_double, _I32P, _DP]),
+    "fm_rank_batch_select": (C.c_int, [_P, _P, _P, C.c_int32, _I64P, _I32P, C.c_int32, C.c_double, C.c_double, _I32P,
+                                       _DP]),
     "fm_init_from_batch": (C.c_int, [_P, _P, _I64P]),
     "fm_loss_grad": (C.c_int, [_P, C.POINTER(fm_csr), _DP, _DP, _DP, _DP]),
     "fm_calc_loss_grad": (C.c_int, [_P, C.POINTER(fm_csr), C.c_double, C.c_uint64, _DP, _DP, _DP, _DP]),

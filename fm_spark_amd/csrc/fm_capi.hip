@@ -1093,8 +1093,10 @@ int fm_eval_history(fm_ctx* ctx, fm_eval_out* out, int64_t cap, int64_t* n) {
 
 // fm_rank_candidates / fm_rank_batch on one whole table: the two row sets' summaries, then the score
 // and merge passes over the contexts in tiles whose split lists fit the budget (fm_rank.hip).
+// sel: the per-context lists of the _select calls (checked by rank_select_check); FM_RANK_SELECT_ALL
+// takes the unrestricted score kernel.
 static int rank_impl(fm_ctx* ctx, const BatchDev& bu, const BatchDev& bc, int32_t n_top, double lo, double hi,
-                     int32_t* top_index, double* top_score) {
+                     int32_t* top_index, double* top_score, const RankSelect& sel = RankSelect{}) {
   const int64_t U = bu.n_rows, Cn = bc.n_rows;
   const int kp = ctx->kp;
   RankWork& w = ctx->rank;
@@ -1105,13 +1107,21 @@ static int rank_impl(fm_ctx* ctx, const BatchDev& bu, const BatchDev& bc, int32_
   w.cnt_c.ensure_slack(sizeof(uint32_t) * Cn);
   w.bias_u.ensure_slack(sizeof(double) * U);
   w.bias_c.ensure_slack(sizeof(double) * Cn);
-  const int splits = rank_splits(Cn, U);
+  // FM_RANK_SELECT_ONLY cuts each context's list, not the candidates: the longest list sets the splits
+  const int splits = rank_splits(sel.mode == FM_RANK_SELECT_ONLY ? sel.longest : Cn, U);
   const int64_t tile = std::min<int64_t>(U, rank_ctx_tile(splits, n_top));
   w.lkey.ensure_slack(sizeof(uint64_t) * (size_t)(tile * splits * n_top));
   w.lidx.ensure_slack(sizeof(uint32_t) * (size_t)(tile * splits * n_top));
   w.out_idx.ensure_slack(sizeof(int32_t) * (size_t)(U * n_top));
   w.out_score.ensure_slack(sizeof(double) * (size_t)(U * n_top));
   hipStream_t st = ctx->stream;
+  if (sel.mode != FM_RANK_SELECT_ALL) {
+    const size_t n_sel = (size_t)sel.ptr[U];
+    w.sel_ptr.ensure_slack(sizeof(int64_t) * (size_t)(U + 1));
+    w.sel_rows.ensure_slack(sizeof(int32_t) * n_sel);
+    FM_HIP_CHECK(hipMemcpyAsync(w.sel_ptr.p, sel.ptr, sizeof(int64_t) * (size_t)(U + 1), hipMemcpyHostToDevice, st));
+    if (n_sel) FM_HIP_CHECK(hipMemcpyAsync(w.sel_rows.p, sel.rows, sizeof(int32_t) * n_sel, hipMemcpyHostToDevice, st));
+  }
   const TableView T = ctx->view();
   const double cumE = ctx->cum_host.back(), w0 = ctx->cfg.w0;
   hipEvent_t e0 = ctx->prof_begin(st);
@@ -1123,9 +1133,15 @@ static int rank_impl(fm_ctx* ctx, const BatchDev& bu, const BatchDev& bc, int32_
   for (int64_t u0 = 0; u0 < U; u0 += tile) {
     const int64_t Ut = std::min<int64_t>(tile, U - u0);
     e0 = ctx->prof_begin(st);
-    launch_rank_score(w.sum_u.as<double>() + u0 * kp, w.bias_u.as<double>() + u0, w.cnt_u.as<uint32_t>() + u0, Ut,
-                      w.sum_c.as<double>(), w.bias_c.as<double>(), w.cnt_c.as<uint32_t>(), Cn, kp, splits, n_top, w0,
-                      w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), st);
+    if (sel.mode == FM_RANK_SELECT_ALL)
+      launch_rank_score(w.sum_u.as<double>() + u0 * kp, w.bias_u.as<double>() + u0, w.cnt_u.as<uint32_t>() + u0, Ut,
+                        w.sum_c.as<double>(), w.bias_c.as<double>(), w.cnt_c.as<uint32_t>(), Cn, kp, splits, n_top, w0,
+                        w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), st);
+    else  // the tile's offsets: sel_ptr + u0 (they index the whole call's sel_rows)
+      launch_rank_score_select(sel.mode, w.sum_u.as<double>() + u0 * kp, w.bias_u.as<double>() + u0,
+                               w.cnt_u.as<uint32_t>() + u0, Ut, w.sum_c.as<double>(), w.bias_c.as<double>(),
+                               w.cnt_c.as<uint32_t>(), Cn, w.sel_ptr.as<int64_t>() + u0, w.sel_rows.as<int32_t>(), kp, splits,
+                               n_top, w0, w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), st);
     ctx->prof_end("rank_score", e0, st);
     e0 = ctx->prof_begin(st);
     launch_rank_merge(w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), Ut, splits, n_top, w.cnt_u.as<uint32_t>() + u0,
@@ -1150,6 +1166,86 @@ static bool rank_check(const fm_ctx* ctx, int64_t U, int64_t Cn, int32_t n_top, 
   FM_REQUIRE(n_top >= 1 && n_top <= FM_RANK_MAX_TOP && n_top <= Cn, "n_top must be in [1, min(candidate rows, FM_RANK_MAX_TOP)]");
   FM_REQUIRE(top_index != nullptr && top_score != nullptr, "null argument");
   return true;
+}
+
+// The list rules of the _select calls for U contexts and Cn candidates, in one pass over the host
+// arrays, before anything is enqueued or sized; fills sel (the longest list with it).
+static void rank_select_check(int32_t select, const int64_t* sel_ptr, const int32_t* sel_rows, int64_t U, int64_t Cn,
+                              RankSelect& sel) {
+  FM_REQUIRE(select == FM_RANK_SELECT_ALL || select == FM_RANK_SELECT_ONLY || select == FM_RANK_SELECT_EXCEPT,
+             "select must be FM_RANK_SELECT_ALL, _ONLY or _EXCEPT, got " + std::to_string(select));
+  sel = RankSelect{};
+  if (select == FM_RANK_SELECT_ALL) return;
+  FM_REQUIRE(sel_ptr != nullptr, "null sel_ptr with FM_RANK_SELECT_ONLY / _EXCEPT");
+  FM_REQUIRE(sel_ptr[0] == 0, "sel_ptr[0] must be 0, got " + std::to_string(sel_ptr[0]));
+  for (int64_t u = 0; u < U; ++u) {
+    FM_REQUIRE(sel_ptr[u + 1] >= sel_ptr[u],
+               "sel_ptr must be non-decreasing: sel_ptr[" + std::to_string(u + 1) + "] < sel_ptr[" + std::to_string(u) + "]");
+    FM_REQUIRE(sel_ptr[u + 1] < (int64_t(1) << 31), "sel_ptr[" + std::to_string(u + 1) + "] must be < 2^31");
+  }
+  FM_REQUIRE(sel_ptr[U] == 0 || sel_rows != nullptr, "null sel_rows with a list that is not empty");
+  for (int64_t u = 0; u < U; ++u) {
+    for (int64_t e = sel_ptr[u]; e < sel_ptr[u + 1]; ++e) {
+      const int64_t r = sel_rows[e];
+      const bool in_range = r >= 0 && r < Cn, in_order = e == sel_ptr[u] || sel_rows[e - 1] < r;
+      if (in_range && in_order) continue;
+      const std::string at = "context " + std::to_string(u) + ", position " + std::to_string(e - sel_ptr[u]) + ": row " +
+                             std::to_string(r);
+      FM_REQUIRE(in_range, at + " is out of range [0, " + std::to_string(Cn) + ")");
+      FM_REQUIRE(in_order, at + " after row " + std::to_string(sel_rows[e - 1]) + ": a list must be strictly ascending");
+    }
+    sel.longest = std::max(sel.longest, sel_ptr[u + 1] - sel_ptr[u]);
+  }
+  sel.mode = select;
+  sel.ptr = sel_ptr;
+  sel.rows = sel_rows;
+}
+
+int fm_rank_candidates_select(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, int32_t select,
+                              const int64_t* sel_ptr, const int32_t* sel_rows, int32_t n_top, double lo, double hi,
+                              int32_t* top_index, double* top_score) {
+  if (ctx && ctx->group) {
+    // a replicated group's replicas are identical: member 0 answers, with the group locked (as fm_loss_grad)
+    return guarded(ctx, [&]() -> int {
+      FM_REQUIRE(ctx->cfg.parallel == FM_PARALLEL_REPLICATED,
+                 "fm_rank needs the whole table on one device (a replicated or single-table context): a row-sharded "
+                 "table is not ranked yet");
+      return fm_rank_candidates_select(group_member0(ctx), contexts, candidates, select, sel_ptr, sel_rows, n_top, lo, hi,
+                                       top_index, top_score);
+    });
+  }
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
+    if (!rank_check(ctx, contexts->n_rows, candidates->n_rows, n_top, top_index, top_score)) return FM_OK;
+    RankSelect sel;
+    rank_select_check(select, sel_ptr, sel_rows, contexts->n_rows, candidates->n_rows, sel);
+    fm_batch* bu = host_batch(ctx);
+    if (!ctx->host_batch2) ctx->host_batch2.reset(new fm_batch());
+    fm_batch* bc = ctx->host_batch2.get();
+    upload_batch(ctx, contexts, bu, false);
+    upload_batch(ctx, candidates, bc, false);
+    return rank_impl(ctx, bu->dev, bc->dev, n_top, lo, hi, top_index, top_score, sel);
+  });
+}
+
+int fm_rank_batch_select(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t select, const int64_t* sel_ptr,
+                         const int32_t* sel_rows, int32_t n_top, double lo, double hi, int32_t* top_index,
+                         double* top_score) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
+    FM_REQUIRE(contexts->owner == ctx && candidates->owner == ctx, "batch belongs to another context");
+    FM_REQUIRE(!ctx->group && !contexts->grp && !candidates->grp,
+               "fm_rank_batch needs both row sets whole on one device: a multi-GPU context's batches are cut over its "
+               "ranks (fm_rank_candidates takes host rows)");
+    FM_REQUIRE(contexts->split_rows.empty() && candidates->split_rows.empty(),
+               "a dataset made by fm_batch_create_splits is ranked through its split views");
+    if (!rank_check(ctx, contexts->dev.n_rows, candidates->dev.n_rows, n_top, top_index, top_score)) return FM_OK;
+    RankSelect sel;
+    rank_select_check(select, sel_ptr, sel_rows, contexts->dev.n_rows, candidates->dev.n_rows, sel);
+    wait_built(contexts, ctx->stream);
+    wait_built(candidates, ctx->stream);
+    return rank_impl(ctx, contexts->dev, candidates->dev, n_top, lo, hi, top_index, top_score, sel);
+  });
 }
 
 int fm_rank_candidates(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, int32_t n_top, double lo, double hi,

@@ -380,6 +380,14 @@ struct RankWork {
   DevBuf bias_u, bias_c;  // double a_r = L + (|S|^2 - Q) / 2 per row
   DevBuf lkey, lidx;      // the context tile's split lists: uint64 keys, uint32 candidate rows
   DevBuf out_idx, out_score;  // int32 / double [U][n_top]
+  DevBuf sel_ptr, sel_rows;   // fm_rank_*_select: the call's lists, int64 [U + 1] offsets and int32 candidate rows
+};
+// a call's per-context row lists (host arrays, validated): mode FM_RANK_SELECT_*, ptr[U + 1], rows[ptr[U]]
+struct RankSelect {
+  int32_t mode = FM_RANK_SELECT_ALL;
+  const int64_t* ptr = nullptr;
+  const int32_t* rows = nullptr;
+  int64_t longest = 0;  // the longest list of the call
 };
 // candidate splits of a call of U contexts (whole chunks each; fewer as the contexts alone fill the
 // chip) and the contexts one pass of the score kernel takes (the list budget)
@@ -392,8 +400,17 @@ void launch_rank_bias(const double* summary, int64_t n, int kp, double* bias, hi
 void launch_rank_score(const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut,
                        const double* sum_c, const double* bias_c, const uint32_t* cnt_c, int64_t C, int kp, int splits,
                        int n_top, double w0, uint64_t* lkey, uint32_t* lidx, hipStream_t st);
+// the same under per-context lists (device: sel_ptr[Ut + 1] of this tile, offsets into sel_rows; rows in
+// [0, C), strictly ascending per list).  FM_RANK_SELECT_EXCEPT: a listed row enters as padding, splits as
+// above.  FM_RANK_SELECT_ONLY: the splits (rank_splits of the call's longest list) cut each context's
+// list; a split without a chunk writes n_top padding entries.
+void launch_rank_score_select(int select, const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut,
+                              const double* sum_c, const double* bias_c, const uint32_t* cnt_c, int64_t C,
+                              const int64_t* sel_ptr, const int32_t* sel_rows, int kp, int splits, int n_top, double w0,
+                              uint64_t* lkey, uint32_t* lidx, hipStream_t st);
 // the splits' lists merged in split order; the first n_top per context into out_idx / out_score
-// (w0 for a pair without a learned entry, else the key's value clamped to [lo, hi])
+// (w0 for a pair without a learned entry, else the key's value clamped to [lo, hi]; row -1 and NaN
+// where a list's entry is padding: fewer eligible rows than n_top)
 void launch_rank_merge(const uint64_t* lkey, const uint32_t* lidx, int64_t Ut, int splits, int n_top,
                        const uint32_t* cnt_u, const uint32_t* cnt_c, double w0, double lo, double hi, int32_t* out_idx,
                        double* out_score, hipStream_t st);

@@ -1,4 +1,5 @@
-// Top-N candidate ranking for gfx950 (MI355X): fm_rank_candidates / fm_rank_batch (include/fm_hip.h).
+// Top-N candidate ranking for gfx950 (MI355X): fm_rank_candidates / fm_rank_batch and their _select
+// forms (include/fm_hip.h).
 //
 // The FM score of a context row u and a candidate row c, their entries taken together, separates:
 //   yhat(u, c) = w0 + a_u + b_c + <S_u, S_c>,   a_r = b_r = L_r + (|S_r|^2 - Q_r) / 2
@@ -28,6 +29,10 @@
 // exceed kRankMaxSplits * kRankChunk * 12 B = 768 KiB.  Nothing grows with U * C.  A call of many
 // contexts takes fewer splits (rank_splits: about kRankTargetBlocks blocks in all), so its blocks
 // stream several chunks each and the merge folds fewer lists.
+//
+// fm_rank_candidates_select / fm_rank_batch_select restrict each context to (or away from) a list of
+// candidate rows: k_rank_score_sel takes k_rank_score's place between the same summaries and the
+// same merge (its comment below); a list's device copy is [U + 1] offsets and the rows, 4 bytes each.
 #include <algorithm>
 
 #include "fm_device.h"
@@ -175,6 +180,141 @@ __global__ __launch_bounds__(kBlock) void k_rank_score(const double* __restrict_
   }
 }
 
+// ---- per-context row lists (fm_rank_*_select).  k_rank_score above is left as it was; the kernel
+// below scores with the same expression in the same order (score_row), so a pair has the same bits
+// in both, and hands the same sort, fold and merge the same (key, row) entries.
+constexpr int kSelOnly = FM_RANK_SELECT_ONLY, kSelExcept = FM_RANK_SELECT_EXCEPT;
+constexpr int kMaskWords = kRankChunk / 32;
+
+// the key of context (su, base, learned_u) and candidate row c: k_rank_score's, operation for operation
+__device__ __forceinline__ uint64_t score_row(const double* su, double base, bool learned_u, const double* __restrict__ sum_c,
+                                              const double* __restrict__ bias_c, const uint32_t* __restrict__ cnt_c,
+                                              int64_t c, int kp, double w0) {
+  const double2* Sc = reinterpret_cast<const double2*>(sum_c + c * kp);
+  double dot = 0.0;
+  // one chain either way; unrolled further, the four rows of a thread hold 83 to 90 VGPRs (5 waves per SIMD)
+#pragma unroll 2
+  for (int f = 0; f < kp / 2; ++f) {
+    const double2 v = Sc[f];
+    dot = fma(su[2 * f], v.x, dot);
+    dot = fma(su[2 * f + 1], v.y, dot);
+  }
+  double y = (base + bias_c[c]) + dot;
+  if (!learned_u && cnt_c[c] == 0) y = w0;  // no learned entry on either side ranks at w0
+  return key_of(y + 0.0);
+}
+
+// Block b: context b / splits, split b % splits.  The list of context u is sel_rows[sel_ptr[u] ..
+// sel_ptr[u + 1]), candidate rows in [0, C), strictly ascending (the host has checked all of it).
+//   kSelExcept  the splits cut the candidate chunks as k_rank_score's do.  The list's cursor starts at
+//               the first entry >= the split's first row (binary search) and moves on by the entries
+//               each chunk marks in its 1024-bit LDS mask (atomicOr: any order of arrival gives the
+//               same mask; ascending rows make the chunk's entries one run, its length the mask's
+//               population).  A marked row enters the chunk as the padding does.
+//   kSelOnly    the splits cut the chunks of the context's *list*, kRankChunk entries each; a thread
+//               gathers the summaries of its listed rows and carries the candidate row as the
+//               tie-break.  The split count comes from the call's longest list, so a shorter list
+//               leaves splits without a chunk: those write n_top padding entries.
+template <int kMode>
+__global__ __launch_bounds__(kBlock) void k_rank_score_sel(const double* __restrict__ sum_u, const double* __restrict__ bias_u,
+                                                           const uint32_t* __restrict__ cnt_u, const double* __restrict__ sum_c,
+                                                           const double* __restrict__ bias_c, const uint32_t* __restrict__ cnt_c,
+                                                           int64_t C, const int64_t* __restrict__ sel_ptr,
+                                                           const int32_t* __restrict__ sel_rows, int kp, int splits, int n_top,
+                                                           double w0, uint64_t* __restrict__ lkey, uint32_t* __restrict__ lidx) {
+  __shared__ double su[256];  // the context's S (kp <= 256)
+  __shared__ uint64_t bkey[kRankChunk], ckey[kRankChunk];
+  __shared__ uint32_t brow[kRankChunk], crow[kRankChunk];
+  __shared__ uint32_t mask[kMaskWords];
+  const int tid = threadIdx.x;
+  const int64_t u = blockIdx.x / splits;
+  const int s = blockIdx.x % splits;
+  const int l0 = (int)sel_ptr[u], l1 = (int)sel_ptr[u + 1];  // sel_ptr[U] < 2^31
+  const int64_t n = kMode == kSelOnly ? l1 - l0 : C;  // what the splits cut: the list, or the candidates
+  const int64_t nch = (n + kRankChunk - 1) / kRankChunk;
+  const int64_t ch0 = nch * s / splits, ch1 = nch * (s + 1) / splits;
+  const int64_t o = ((int64_t)u * splits + s) * n_top;
+  if (ch0 == ch1) {  // kSelOnly: no chunk of a shorter list falls into this split
+    for (int i = tid; i < n_top; i += kBlock) {
+      lkey[o + i] = kWorstKey;
+      lidx[o + i] = kNoRow;
+    }
+    return;
+  }
+  for (int f = tid; f < kp; f += kBlock) su[f] = sum_u[u * kp + f];
+  const int W = list_width(n_top);
+  const double base = w0 + bias_u[u];
+  const bool learned_u = cnt_u[u] != 0;
+  int cur = l0;  // kSelExcept: the first list entry at or after the chunk's first row
+  if (kMode == kSelExcept) {
+    int hi = l1;
+    const int64_t first = ch0 * kRankChunk;
+    while (cur < hi) {
+      const int mid = cur + (hi - cur) / 2;
+      if (sel_rows[mid] < first) cur = mid + 1; else hi = mid;
+    }
+  }
+  __syncthreads();
+  for (int64_t ch = ch0; ch < ch1; ++ch) {
+    uint64_t* key = ch == ch0 ? bkey : ckey;  // the split's first chunk is its running list
+    uint32_t* row = ch == ch0 ? brow : crow;
+    const int64_t c0 = ch * kRankChunk;
+    if (kMode == kSelExcept) {
+      // the last reads of the mask lie before the barriers of the chunk's sort
+      if (tid < kMaskWords) mask[tid] = 0;
+      __syncthreads();
+      for (int e = cur + tid; e < l1; e += kBlock) {
+        const int64_t d = (int64_t)sel_rows[e] - c0;
+        if (d >= kRankChunk) break;
+        if (d >= 0) atomicOr(&mask[d >> 5], 1u << (d & 31));
+      }
+      __syncthreads();
+      int marked = __popc(mask[tid & (kMaskWords - 1)]);  // every 32 lanes hold the 32 words: their sum, in each lane
+      for (int d = kMaskWords / 2; d > 0; d >>= 1) marked += __shfl_xor(marked, d);
+      cur += __builtin_amdgcn_readfirstlane(marked);
+    }
+#pragma unroll
+    for (int j = 0; j < kRankPer; ++j) {
+      const int i = tid + j * kBlock;
+      uint64_t k = kWorstKey;
+      uint32_t r = kNoRow;
+      if (kMode == kSelOnly) {
+        if (c0 + i < n) {
+          r = (uint32_t)sel_rows[l0 + c0 + i];
+          k = score_row(su, base, learned_u, sum_c, bias_c, cnt_c, r, kp, w0);
+        }
+      } else {
+        const int64_t c = c0 + i;
+        if (c < C) {
+          k = score_row(su, base, learned_u, sum_c, bias_c, cnt_c, c, kp, w0);
+          r = (uint32_t)c;
+        }
+      }
+      key[i] = k;
+      row[i] = r;
+    }
+    if (kMode == kSelExcept) {
+      // a listed row was scored like the rest (the scoring loop stays k_rank_score's); its owner
+      // now enters it as padding
+#pragma unroll
+      for (int j = 0; j < kRankPer; ++j) {
+        const int i = tid + j * kBlock;
+        if ((mask[i >> 5] >> (i & 31)) & 1u) {
+          key[i] = kWorstKey;
+          row[i] = kNoRow;
+        }
+      }
+    }
+    __syncthreads();
+    bitonic_sort(key, row);
+    if (ch != ch0) fold_sorted(bkey, brow, ckey, crow, W);
+  }
+  for (int i = tid; i < n_top; i += kBlock) {
+    lkey[o + i] = bkey[i];
+    lidx[o + i] = brow[i];
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void k_rank_merge(const uint64_t* __restrict__ lkey, const uint32_t* __restrict__ lidx,
                                                        int splits, int n_top, const uint32_t* __restrict__ cnt_u,
                                                        const uint32_t* __restrict__ cnt_c, double w0, double lo, double hi,
@@ -199,7 +339,8 @@ __global__ __launch_bounds__(kBlock) void k_rank_merge(const uint64_t* __restric
   for (int i = tid; i < n_top; i += kBlock) {
     const uint32_t c = brow[i];
     double y = w0;  // a pair without a learned entry: globalBias, unclamped (Model.scala:86)
-    if (c != kNoRow && (learned_u || cnt_c[c] != 0)) y = fmin(fmax(value_of(bkey[i]), lo), hi);
+    if (c == kNoRow) y = __longlong_as_double(0x7FF8000000000000ll);  // fewer eligible rows than n_top (the _select calls): NaN
+    else if (learned_u || cnt_c[c] != 0) y = fmin(fmax(value_of(bkey[i]), lo), hi);
     out_idx[u * n_top + i] = (int32_t)c;
     out_score[u * n_top + i] = y;
   }
@@ -235,6 +376,26 @@ void launch_rank_score(const double* sum_u, const double* bias_u, const uint32_t
   FM_REQUIRE(Ut * splits < (int64_t(1) << 31), "rank: context tile too large");
   hipLaunchKernelGGL(k_rank_score, dim3((unsigned)(Ut * splits)), dim3(kBlock), 0, st, sum_u, bias_u, cnt_u, sum_c, bias_c,
                      cnt_c, C, kp, splits, n_top, w0, lkey, lidx);
+  FM_HIP_CHECK(hipGetLastError());
+}
+
+void launch_rank_score_select(int select, const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut,
+                              const double* sum_c, const double* bias_c, const uint32_t* cnt_c, int64_t C,
+                              const int64_t* sel_ptr, const int32_t* sel_rows, int kp, int splits, int n_top, double w0,
+                              uint64_t* lkey, uint32_t* lidx, hipStream_t st) {
+  FM_REQUIRE(kp <= 256, "dimFactorization > 256 is not supported");
+  FM_REQUIRE(select == kSelOnly || select == kSelExcept, "rank: bad select");
+  FM_REQUIRE(Ut >= 1 && C >= 1 && n_top >= 1 && n_top <= kRankChunk && n_top <= C, "rank: bad shape");
+  FM_REQUIRE(splits >= 1 && splits <= kRankMaxSplits, "rank: bad split count");
+  FM_REQUIRE(select == kSelOnly || splits <= (C + kRankChunk - 1) / kRankChunk, "rank: every split needs a chunk");
+  FM_REQUIRE(Ut * splits < (int64_t(1) << 31), "rank: context tile too large");
+  const dim3 grid((unsigned)(Ut * splits)), block(kBlock);
+  if (select == kSelOnly)
+    hipLaunchKernelGGL(k_rank_score_sel<kSelOnly>, grid, block, 0, st, sum_u, bias_u, cnt_u, sum_c, bias_c, cnt_c, C, sel_ptr,
+                       sel_rows, kp, splits, n_top, w0, lkey, lidx);
+  else
+    hipLaunchKernelGGL(k_rank_score_sel<kSelExcept>, grid, block, 0, st, sum_u, bias_u, cnt_u, sum_c, bias_c, cnt_c, C, sel_ptr,
+                       sel_rows, kp, splits, n_top, w0, lkey, lidx);
   FM_HIP_CHECK(hipGetLastError());
 }
 

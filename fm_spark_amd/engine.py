@@ -127,6 +127,40 @@ def comm_unique_id() -> bytes:
     return bytes(buf)
 
 
+def normalize_row_lists(lists, n_ctx: int):
+    """The per-context row lists of rank(only= / exclude=) as the C-ABI takes them: (ptr int64
+    [n_ctx + 1], rows int32), every list sorted and without duplicates.  ``lists``: a sequence of
+    n_ctx integer sequences, or a CSR pair (ptr, rows) -- a tuple of two 1-D NumPy arrays whose
+    first holds n_ctx + 1 offsets (so two contexts' lists go in a list, not a tuple).  A wrong number of
+    lists, entries that are not integers, or rows outside int32 raise ValueError; whether a row is a
+    candidate row is the library's check."""
+    if (isinstance(lists, tuple) and len(lists) == 2 and all(isinstance(a, np.ndarray) and a.ndim == 1 for a in lists)
+            and len(lists[0]) == n_ctx + 1):
+        ptr, flat = lists
+        if ptr.dtype.kind not in "iu" or (flat.size and flat.dtype.kind not in "iu"):
+            raise ValueError("row lists must hold integers")
+        ptr = ptr.astype(np.int64)
+        if ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != flat.size:
+            raise ValueError("(ptr, rows): ptr must start at 0, not decrease and end at len(rows)")
+        parts = [flat[ptr[u]:ptr[u + 1]] for u in range(n_ctx)]
+    else:
+        parts = [np.asarray(r) for r in lists]
+        if len(parts) != n_ctx:
+            raise ValueError(f"expected one row list per context ({n_ctx}), got {len(parts)}")
+    out = []
+    for u, r in enumerate(parts):
+        if r.ndim != 1 or (r.size and r.dtype.kind not in "iu"):
+            raise ValueError(f"row list of context {u} must be a flat sequence of integers")
+        r = np.unique(r.astype(np.int64))
+        if r.size and (r[0] < -2**31 or r[-1] >= 2**31):
+            raise ValueError(f"row list of context {u} holds a row outside int32")
+        out.append(r.astype(np.int32))
+    ptr = np.zeros(n_ctx + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in out], out=ptr[1:])
+    rows = np.concatenate(out) if out else np.zeros(0, np.int32)
+    return ptr, np.ascontiguousarray(rows, dtype=np.int32)
+
+
 class FMContext:
     """One fm_ctx.  ``parallel`` = "sharded" / "replicated": the context drives ``n_gpus`` local
     ranks on ``devices`` (default device, device + 1, ...) of a job of ``n_procs`` processes and runs
@@ -397,26 +431,42 @@ class FMContext:
         N.check(self._lib.fm_eval_history(self.handle, buf, n.value, C.byref(n)), "fm_eval_history")
         return [EvalSums.from_struct(o) for o in buf[: n.value]]
 
-    def rank(self, contexts: N.CSRHost, candidates: N.CSRHost, n_top: int, min_label: float, max_label: float):
+    def rank(self, contexts: N.CSRHost, candidates: N.CSRHost, n_top: int, min_label: float, max_label: float, *,
+             only=None, exclude=None):
         """For every context row the n_top candidate rows with the largest FM score of the two rows'
         entries together (fm_rank_candidates): (index [U, n_top] int32, score [U, n_top] float64), by
-        the unclamped score descending, ties by ascending candidate row."""
-        return self._rank(self._lib.fm_rank_candidates, "fm_rank_candidates", C.byref(contexts.c),
-                          C.byref(candidates.c), contexts.n_rows, n_top, min_label, max_label)
+        the unclamped score descending, ties by ascending candidate row.
+
+        only / exclude (one of them): per context a list of candidate rows, as a sequence of U integer
+        sequences or a CSR pair (ptr [U + 1], rows).  ``only``: context u ranks the rows of its list
+        alone; ``exclude``: every row except them (fm_rank_candidates_select).  The lists are sorted
+        and de-duplicated here; rows outside the candidates are refused by the library.  Where fewer
+        than n_top rows are eligible the remaining slots hold index -1 and score NaN."""
+        return self._rank(self._lib.fm_rank_candidates, self._lib.fm_rank_candidates_select, "fm_rank_candidates",
+                          C.byref(contexts.c), C.byref(candidates.c), contexts.n_rows, n_top, min_label, max_label,
+                          only, exclude)
 
     def rank_batch(self, contexts: DeviceBatch, candidates: DeviceBatch, n_top: int, min_label: float,
-                   max_label: float):
-        """rank over device-resident batches of this context (fm_rank_batch)."""
-        return self._rank(self._lib.fm_rank_batch, "fm_rank_batch", contexts.handle, candidates.handle,
-                          contexts.n_rows, n_top, min_label, max_label)
+                   max_label: float, *, only=None, exclude=None):
+        """rank over device-resident batches of this context (fm_rank_batch / fm_rank_batch_select)."""
+        return self._rank(self._lib.fm_rank_batch, self._lib.fm_rank_batch_select, "fm_rank_batch", contexts.handle,
+                          candidates.handle, contexts.n_rows, n_top, min_label, max_label, only, exclude)
 
-    def _rank(self, fn, what, contexts, candidates, n_ctx, n_top, min_label, max_label):
+    def _rank(self, fn, fn_select, what, contexts, candidates, n_ctx, n_top, min_label, max_label, only, exclude):
+        if only is not None and exclude is not None:
+            raise ValueError("give only= or exclude=, not both")
         n_top = int(n_top)
         n = max(n_ctx * max(n_top, 0), 1)
         idx = np.zeros(n, dtype=np.int32)
         score = np.zeros(n)
-        N.check(fn(self.handle, contexts, candidates, n_top, float(min_label), float(max_label),
-                   N.ptr(idx, C.c_int32), N.ptr(score, C.c_double)), what)
+        out = (n_top, float(min_label), float(max_label), N.ptr(idx, C.c_int32), N.ptr(score, C.c_double))
+        if only is None and exclude is None:
+            N.check(fn(self.handle, contexts, candidates, *out), what)
+        else:
+            ptr, rows = normalize_row_lists(exclude if only is None else only, n_ctx)
+            mode = N.FM_RANK_SELECT_EXCEPT if only is None else N.FM_RANK_SELECT_ONLY
+            N.check(fn_select(self.handle, contexts, candidates, mode, N.ptr(ptr, C.c_int64), N.ptr(rows, C.c_int32), *out),
+                    what + "_select")
         m = n_ctx * n_top
         return idx[:m].reshape(n_ctx, n_top), score[:m].reshape(n_ctx, n_top)
 

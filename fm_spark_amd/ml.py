@@ -245,15 +245,24 @@ class FactorizationMachinesModel:
         csr = N.CSRHost(rp, col, val, np.asarray(dataset[lcol], dtype=np.float64))
         return self._ctx.evaluate(csr, self.getMinLabel(), self.getMaxLabel())
 
-    def recommend(self, contexts: DataFrame, candidates: DataFrame, numItems: int) -> DataFrame:
+    def recommend(self, contexts: DataFrame, candidates: DataFrame, numItems: int, exclude=None, only=None) -> DataFrame:
         """The numItems best rows of `candidates` for every row of `contexts` (the shape of
         ALSModel.recommendForUserSubset): both frames carry featuresCol; the result is `contexts` plus
         a ``recommendations`` column, per row a list of (candidate_row, prediction) in rank order.  A
         pair's prediction is transform's for the row made of the two rows' entries, clamped to
         [minLabel, maxLabel]; the order is that of the unclamped score, ties by candidate row
         (fm_rank_candidates, include/fm_hip.h).  numItems outside [1, min(len(candidates), 1024)]
-        raises ValueError; a model whose table is row-sharded refuses with FMError, as calcLossGrad."""
+        raises ValueError; a model whose table is row-sharded refuses with FMError, as calcLossGrad.
+
+        exclude / only (one of them; giving both raises ValueError): per row of `contexts` a list of
+        row indices of `candidates` -- ``exclude``: rows never recommended to that context (what the
+        user has already rated); ``only``: the rows ranked for it (a retrieval stage's candidates).
+        The restriction is applied before the selection (fm_rank_candidates_select), so a context gets
+        numItems recommendations whenever it has that many eligible rows; with fewer, its list is
+        shorter.  Without the arguments the call and its result are the unrestricted ones."""
         fcol = self._params["featuresCol"]
+        if exclude is not None and only is not None:
+            raise ValueError("give exclude= or only=, not both")
         n_cand = candidates.count()
         if isinstance(numItems, bool) or not isinstance(numItems, (int, np.integer)):
             raise ValueError("numItems must be an integer")
@@ -265,8 +274,12 @@ class FactorizationMachinesModel:
         for df in (contexts, candidates):
             rp, col, val = _explode(df[fcol])
             rows.append(N.CSRHost(rp, col, val, np.zeros(df.count())))
-        idx, score = self._ctx.rank(rows[0], rows[1], int(numItems), self.getMinLabel(), self.getMaxLabel())
-        recs = [[(int(i), float(s)) for i, s in zip(ri, rs)] for ri, rs in zip(idx, score)]
+        if exclude is None and only is None:
+            idx, score = self._ctx.rank(rows[0], rows[1], int(numItems), self.getMinLabel(), self.getMaxLabel())
+        else:
+            idx, score = self._ctx.rank(rows[0], rows[1], int(numItems), self.getMinLabel(), self.getMaxLabel(),
+                                        exclude=exclude, only=only)
+        recs = [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
         return contexts.with_column("recommendations", recs)
 
     def calcLossGrad(self, dfSampleIndexed: DataFrame, initialSd: float, seed: int = 0) -> DataFrame:

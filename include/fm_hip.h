@@ -172,7 +172,8 @@ int fm_sync(fm_ctx* ctx);
  * per-batch routing state and wire buffers, and fm_step's two upload slots, each of which grows to
  * the largest host batch it has held (steady after every batch size has passed through both).  The
  * scratch of fm_rank_candidates / fm_rank_batch is not covered either: it is sized by the two row
- * sets and n_top at the call, and kept. */
+ * sets and n_top at the call, and kept; nor are the device copies of the lists of
+ * fm_rank_candidates_select / fm_rank_batch_select, sized by U and the lists' total length. */
 int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz);
 
 /* ---- tables (C9: Strength / FactorizedInteraction, Model.scala:275-289) ------------ */
@@ -395,6 +396,39 @@ int fm_rank_candidates(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candid
  * for a refilled batch's gather. */
 int fm_rank_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t n_top,
                   double min_label, double max_label, int32_t* top_index, double* top_score);
+/* Ranking within per-context candidate lists: context u carries a list of candidate rows,
+ * sel_rows[sel_ptr[u] .. sel_ptr[u + 1]), and ranks only those rows (FM_RANK_SELECT_ONLY: second-stage
+ * ranking of a retrieval's candidates out of one shared pool) or every row except those
+ * (FM_RANK_SELECT_EXCEPT: top-N unseen; the exclusion happens before the selection, so n_top results
+ * survive it).  FM_RANK_SELECT_ALL ignores the lists (they may be NULL) and is fm_rank_candidates /
+ * fm_rank_batch, bit for bit.
+ *   lists : host arrays.  sel_ptr has U + 1 entries, sel_ptr[0] == 0, non-decreasing, sel_ptr[U] <
+ *           2^31; a list's entries are candidate rows in [0, C), strictly ascending.  The host checks
+ *           all of it in one pass before anything is enqueued; a violation is FM_ERR_ARG with the
+ *           context and the position in fm_last_error() ("... ascending ...", "... out of range ...",
+ *           "sel_ptr ...", "select ...", "null ..."), and a refused call changes nothing on the device.
+ *   score, order : an eligible pair's key and score are fm_rank_candidates' for that pair, bit for bit;
+ *           ties go to the ascending candidate row.  A context's result depends on the rows, the table
+ *           and its own list alone.
+ *   fewer eligible rows than n_top : the eligible rows come first, in order; the remaining slots hold
+ *           top_index = -1 and top_score = NaN (a context with nothing eligible: all of them).  n_top
+ *           keeps its rule, 1 <= n_top <= min(C, FM_RANK_MAX_TOP), whatever the lists hold.
+ *   cost : FM_RANK_SELECT_EXCEPT scores all U x C pairs, as the unrestricted call; FM_RANK_SELECT_ONLY
+ *           scores the listed pairs alone (work proportional to the list lengths).
+ * Everything else as fm_rank_candidates / fm_rank_batch: U = 0, C = 0, null pointers, the CSRs, batches
+ * of another context, split datasets, a replicated group (host rows only, answered by its first
+ * rank), a row-sharded table (FM_ERR_ARG), synchronous on the main stream, nothing of the context's
+ * state changed.  The device copies of the lists are scratch of the context like the rest and grow to
+ * the largest call. */
+#define FM_RANK_SELECT_ALL 0     /* lists ignored (may be NULL): fm_rank_candidates' result, bit for bit */
+#define FM_RANK_SELECT_ONLY 1    /* context u ranks only the candidate rows of its list */
+#define FM_RANK_SELECT_EXCEPT 2  /* context u ranks every candidate row except those of its list */
+int fm_rank_candidates_select(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, int32_t select,
+                              const int64_t* sel_ptr, const int32_t* sel_rows, int32_t n_top,
+                              double min_label, double max_label, int32_t* top_index, double* top_score);
+int fm_rank_batch_select(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t select,
+                         const int64_t* sel_ptr, const int32_t* sel_rows, int32_t n_top,
+                         double min_label, double max_label, int32_t* top_index, double* top_score);
 /* calcLossGrad (Model.scala:135-234), per active entry e in CSR order:
  * pred[e] = yhat of its row (unclamped), loss[e] = (yhat - y)^2, delta_w[e] = x,
  * delta_v[e*k + f] = vfxiSum_f * x - (v_f * x) * x.  Any output may be NULL.
