@@ -129,6 +129,9 @@ SIGNATURES = {
                                             C.c_double, C.c_double, _I32P, _DP]),
     "fm_rank_batch_select": (C.c_int, [_P, _P, _P, C.c_int32, _I64P, _I32P, C.c_int32, C.c_double, C.c_double, _I32P,
                                        _DP]),
+    "fm_rank_positions": (C.c_int, [_P, C.POINTER(fm_csr), C.POINTER(fm_csr), _I64P, _I32P, _I64P, _I32P, C.c_double,
+                                    C.c_double, _I32P, _DP]),
+    "fm_rank_positions_batch": (C.c_int, [_P, _P, _P, _I64P, _I32P, _I64P, _I32P, C.c_double, C.c_double, _I32P, _DP]),
     "fm_init_from_batch": (C.c_int, [_P, _P, _I64P]),
     "fm_loss_grad": (C.c_int, [_P, C.POINTER(fm_csr), _DP, _DP, _DP, _DP]),
     "fm_calc_loss_grad": (C.c_int, [_P, C.POINTER(fm_csr), C.c_double, C.c_uint64, _DP, _DP, _DP, _DP]),

@@ -1168,8 +1168,37 @@ static bool rank_check(const fm_ctx* ctx, int64_t U, int64_t Cn, int32_t n_top, 
   return true;
 }
 
-// The list rules of the _select calls for U contexts and Cn candidates, in one pass over the host
-// arrays, before anything is enqueued or sized; fills sel (the longest list with it).
+// The rules of one set of per-context row lists (ptr[U + 1], rows[ptr[U]]; ptr not null) for Cn candidates,
+// in one pass over the host arrays, before anything is enqueued or sized: returns the longest list.
+// what: put before every message (the list's name where a call takes several); pname / rname: the
+// arguments' names.
+static int64_t rank_list_check(const std::string& what, const std::string& pname, const std::string& rname,
+                               const int64_t* ptr, const int32_t* rows, int64_t U, int64_t Cn) {
+  FM_REQUIRE(ptr[0] == 0, what + pname + "[0] must be 0, got " + std::to_string(ptr[0]));
+  for (int64_t u = 0; u < U; ++u) {
+    FM_REQUIRE(ptr[u + 1] >= ptr[u], what + pname + " must be non-decreasing: " + pname + "[" + std::to_string(u + 1) +
+                                         "] < " + pname + "[" + std::to_string(u) + "]");
+    FM_REQUIRE(ptr[u + 1] < (int64_t(1) << 31), what + pname + "[" + std::to_string(u + 1) + "] must be < 2^31");
+  }
+  FM_REQUIRE(ptr[U] == 0 || rows != nullptr, what + "null " + rname + " with a list that is not empty");
+  int64_t longest = 0;
+  for (int64_t u = 0; u < U; ++u) {
+    for (int64_t e = ptr[u]; e < ptr[u + 1]; ++e) {
+      const int64_t r = rows[e];
+      const bool in_range = r >= 0 && r < Cn, in_order = e == ptr[u] || rows[e - 1] < r;
+      if (in_range && in_order) continue;
+      const std::string at = what + "context " + std::to_string(u) + ", position " + std::to_string(e - ptr[u]) + ": row " +
+                             std::to_string(r);
+      FM_REQUIRE(in_range, at + " is out of range [0, " + std::to_string(Cn) + ")");
+      FM_REQUIRE(in_order, at + " after row " + std::to_string(rows[e - 1]) + ": a list must be strictly ascending");
+    }
+    longest = std::max(longest, ptr[u + 1] - ptr[u]);
+  }
+  return longest;
+}
+
+// The list rules of the _select calls for U contexts and Cn candidates (rank_list_check); fills sel
+// (the longest list with it).
 static void rank_select_check(int32_t select, const int64_t* sel_ptr, const int32_t* sel_rows, int64_t U, int64_t Cn,
                               RankSelect& sel) {
   FM_REQUIRE(select == FM_RANK_SELECT_ALL || select == FM_RANK_SELECT_ONLY || select == FM_RANK_SELECT_EXCEPT,
@@ -1177,25 +1206,7 @@ static void rank_select_check(int32_t select, const int64_t* sel_ptr, const int3
   sel = RankSelect{};
   if (select == FM_RANK_SELECT_ALL) return;
   FM_REQUIRE(sel_ptr != nullptr, "null sel_ptr with FM_RANK_SELECT_ONLY / _EXCEPT");
-  FM_REQUIRE(sel_ptr[0] == 0, "sel_ptr[0] must be 0, got " + std::to_string(sel_ptr[0]));
-  for (int64_t u = 0; u < U; ++u) {
-    FM_REQUIRE(sel_ptr[u + 1] >= sel_ptr[u],
-               "sel_ptr must be non-decreasing: sel_ptr[" + std::to_string(u + 1) + "] < sel_ptr[" + std::to_string(u) + "]");
-    FM_REQUIRE(sel_ptr[u + 1] < (int64_t(1) << 31), "sel_ptr[" + std::to_string(u + 1) + "] must be < 2^31");
-  }
-  FM_REQUIRE(sel_ptr[U] == 0 || sel_rows != nullptr, "null sel_rows with a list that is not empty");
-  for (int64_t u = 0; u < U; ++u) {
-    for (int64_t e = sel_ptr[u]; e < sel_ptr[u + 1]; ++e) {
-      const int64_t r = sel_rows[e];
-      const bool in_range = r >= 0 && r < Cn, in_order = e == sel_ptr[u] || sel_rows[e - 1] < r;
-      if (in_range && in_order) continue;
-      const std::string at = "context " + std::to_string(u) + ", position " + std::to_string(e - sel_ptr[u]) + ": row " +
-                             std::to_string(r);
-      FM_REQUIRE(in_range, at + " is out of range [0, " + std::to_string(Cn) + ")");
-      FM_REQUIRE(in_order, at + " after row " + std::to_string(sel_rows[e - 1]) + ": a list must be strictly ascending");
-    }
-    sel.longest = std::max(sel.longest, sel_ptr[u + 1] - sel_ptr[u]);
-  }
+  sel.longest = rank_list_check("", "sel_ptr", "sel_rows", sel_ptr, sel_rows, U, Cn);
   sel.mode = select;
   sel.ptr = sel_ptr;
   sel.rows = sel_rows;
@@ -1285,6 +1296,145 @@ int fm_rank_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t
     wait_built(contexts, ctx->stream);
     wait_built(candidates, ctx->stream);
     return rank_impl(ctx, contexts->dev, candidates->dev, n_top, lo, hi, top_index, top_score);
+  });
+}
+
+// fm_rank_positions / fm_rank_positions_batch: the lists of a call, checked (rank_positions_check)
+struct RankTargets {
+  const int64_t* tgt_ptr = nullptr;
+  const int32_t* tgt_rows = nullptr;
+  const int64_t* ex_ptr = nullptr;  // null: nothing excluded
+  const int32_t* ex_rows = nullptr;
+  int64_t longest = 0;  // the longest target list
+};
+
+// the argument rules both entry points share, as rank_check's; false: nothing to do
+static bool rank_positions_check(const fm_ctx* ctx, int64_t U, int64_t Cn, const int64_t* tgt_ptr, const int32_t* tgt_rows,
+                                 const int64_t* excl_ptr, const int32_t* excl_rows, const int32_t* position,
+                                 const double* score, RankTargets& t) {
+  FM_REQUIRE(ctx->cfg.shard_count == 1,
+             "fm_rank needs the whole table on one device (shard_count == 1): a row-sharded table is not ranked yet");
+  if (U == 0) return false;
+  FM_REQUIRE(Cn >= 1, "fm_rank needs at least one candidate row");
+  FM_REQUIRE(Cn < (int64_t(1) << 31), "fm_rank takes fewer than 2^31 candidate rows");
+  FM_REQUIRE(position != nullptr && score != nullptr, "null argument");
+  FM_REQUIRE(tgt_ptr != nullptr, "null tgt_ptr: fm_rank_positions needs the target lists");
+  t = RankTargets{};
+  t.longest = rank_list_check("target list: ", "tgt_ptr", "tgt_rows", tgt_ptr, tgt_rows, U, Cn);
+  if (excl_ptr) {
+    rank_list_check("exclude list: ", "excl_ptr", "excl_rows", excl_ptr, excl_rows, U, Cn);
+    t.ex_ptr = excl_ptr;
+    t.ex_rows = excl_rows;
+  }
+  t.tgt_ptr = tgt_ptr;
+  t.tgt_rows = tgt_rows;
+  return tgt_ptr[U] != 0;
+}
+
+// On one whole table: the two row sets' summaries as rank_impl takes them, then the counting pass over
+// the contexts, a launch per rank_position_ctx_tile() of them (fm_rank.hip).  No scratch but the lists'
+// copies and the results: the splits add their counts onto the zeroed positions.
+static int rank_positions_impl(fm_ctx* ctx, const BatchDev& bu, const BatchDev& bc, const RankTargets& t, double lo, double hi,
+                               int32_t* position, double* score) {
+  const int64_t U = bu.n_rows, Cn = bc.n_rows;
+  const int kp = ctx->kp;
+  const size_t n_tgt = (size_t)t.tgt_ptr[U];
+  RankWork& w = ctx->rank;
+  const size_t srow = sizeof(double) * (size_t)(kp + 2);
+  w.sum_u.ensure_slack(srow * U);
+  w.sum_c.ensure_slack(srow * Cn);
+  w.cnt_u.ensure_slack(sizeof(uint32_t) * U);
+  w.cnt_c.ensure_slack(sizeof(uint32_t) * Cn);
+  w.bias_u.ensure_slack(sizeof(double) * U);
+  w.bias_c.ensure_slack(sizeof(double) * Cn);
+  w.tgt_ptr.ensure_slack(sizeof(int64_t) * (size_t)(U + 1));
+  w.tgt_rows.ensure_slack(sizeof(int32_t) * n_tgt);
+  w.position.ensure_slack(sizeof(int32_t) * n_tgt);
+  w.pos_score.ensure_slack(sizeof(double) * n_tgt);
+  hipStream_t st = ctx->stream;
+  FM_HIP_CHECK(hipMemcpyAsync(w.tgt_ptr.p, t.tgt_ptr, sizeof(int64_t) * (size_t)(U + 1), hipMemcpyHostToDevice, st));
+  FM_HIP_CHECK(hipMemcpyAsync(w.tgt_rows.p, t.tgt_rows, sizeof(int32_t) * n_tgt, hipMemcpyHostToDevice, st));
+  if (t.ex_ptr) {
+    const size_t n_ex = (size_t)t.ex_ptr[U];
+    w.sel_ptr.ensure_slack(sizeof(int64_t) * (size_t)(U + 1));
+    w.sel_rows.ensure_slack(sizeof(int32_t) * n_ex);
+    FM_HIP_CHECK(hipMemcpyAsync(w.sel_ptr.p, t.ex_ptr, sizeof(int64_t) * (size_t)(U + 1), hipMemcpyHostToDevice, st));
+    if (n_ex) FM_HIP_CHECK(hipMemcpyAsync(w.sel_rows.p, t.ex_rows, sizeof(int32_t) * n_ex, hipMemcpyHostToDevice, st));
+  }
+  FM_HIP_CHECK(hipMemsetAsync(w.position.p, 0, sizeof(int32_t) * n_tgt, st));
+  const TableView T = ctx->view();
+  const double cumE = ctx->cum_host.back(), w0 = ctx->cfg.w0;
+  hipEvent_t e0 = ctx->prof_begin(st);
+  launch_summary(T, bu, cumE, w.sum_u.as<double>(), w.cnt_u.as<uint32_t>(), st);
+  launch_summary(T, bc, cumE, w.sum_c.as<double>(), w.cnt_c.as<uint32_t>(), st);
+  launch_rank_bias(w.sum_u.as<double>(), U, kp, w.bias_u.as<double>(), st);
+  launch_rank_bias(w.sum_c.as<double>(), Cn, kp, w.bias_c.as<double>(), st);
+  ctx->prof_end("rank_summary", e0, st);
+  const int splits = rank_splits(Cn, U);
+  const int64_t tile = rank_position_ctx_tile();
+  for (int64_t u0 = 0; u0 < U; u0 += tile) {
+    const int64_t Ut = std::min<int64_t>(tile, U - u0);
+    e0 = ctx->prof_begin(st);
+    // the tile's offsets: tgt_ptr + u0, sel_ptr + u0 (they index the whole call's rows and results)
+    launch_rank_position(w.sum_u.as<double>() + u0 * kp, w.bias_u.as<double>() + u0, w.cnt_u.as<uint32_t>() + u0, Ut,
+                         w.sum_c.as<double>(), w.bias_c.as<double>(), w.cnt_c.as<uint32_t>(), Cn, w.tgt_ptr.as<int64_t>() + u0,
+                         w.tgt_rows.as<int32_t>(), t.longest, t.ex_ptr ? w.sel_ptr.as<int64_t>() + u0 : nullptr,
+                         w.sel_rows.as<int32_t>(), kp, splits, w0, lo, hi, w.position.as<int32_t>(),
+                         w.pos_score.as<double>(), st);
+    ctx->prof_end("rank_position", e0, st);
+  }
+  FM_HIP_CHECK(hipMemcpyAsync(position, w.position.p, sizeof(int32_t) * n_tgt, hipMemcpyDeviceToHost, st));
+  FM_HIP_CHECK(hipMemcpyAsync(score, w.pos_score.p, sizeof(double) * n_tgt, hipMemcpyDeviceToHost, st));
+  FM_HIP_CHECK(hipStreamSynchronize(st));
+  return FM_OK;
+}
+
+int fm_rank_positions(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, const int64_t* tgt_ptr,
+                      const int32_t* tgt_rows, const int64_t* excl_ptr, const int32_t* excl_rows, double lo, double hi,
+                      int32_t* position, double* score) {
+  if (ctx && ctx->group) {
+    // a replicated group's replicas are identical: member 0 answers, with the group locked (as fm_loss_grad)
+    return guarded(ctx, [&]() -> int {
+      FM_REQUIRE(ctx->cfg.parallel == FM_PARALLEL_REPLICATED,
+                 "fm_rank needs the whole table on one device (a replicated or single-table context): a row-sharded "
+                 "table is not ranked yet");
+      return fm_rank_positions(group_member0(ctx), contexts, candidates, tgt_ptr, tgt_rows, excl_ptr, excl_rows, lo, hi,
+                               position, score);
+    });
+  }
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
+    RankTargets t;
+    if (!rank_positions_check(ctx, contexts->n_rows, candidates->n_rows, tgt_ptr, tgt_rows, excl_ptr, excl_rows, position,
+                              score, t))
+      return FM_OK;
+    fm_batch* bu = host_batch(ctx);
+    if (!ctx->host_batch2) ctx->host_batch2.reset(new fm_batch());
+    fm_batch* bc = ctx->host_batch2.get();
+    upload_batch(ctx, contexts, bu, false);
+    upload_batch(ctx, candidates, bc, false);
+    return rank_positions_impl(ctx, bu->dev, bc->dev, t, lo, hi, position, score);
+  });
+}
+
+int fm_rank_positions_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, const int64_t* tgt_ptr,
+                            const int32_t* tgt_rows, const int64_t* excl_ptr, const int32_t* excl_rows, double lo, double hi,
+                            int32_t* position, double* score) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
+    FM_REQUIRE(contexts->owner == ctx && candidates->owner == ctx, "batch belongs to another context");
+    FM_REQUIRE(!ctx->group && !contexts->grp && !candidates->grp,
+               "fm_rank_positions_batch needs both row sets whole on one device: a multi-GPU context's batches are cut "
+               "over its ranks (fm_rank_positions takes host rows)");
+    FM_REQUIRE(contexts->split_rows.empty() && candidates->split_rows.empty(),
+               "a dataset made by fm_batch_create_splits is ranked through its split views");
+    RankTargets t;
+    if (!rank_positions_check(ctx, contexts->dev.n_rows, candidates->dev.n_rows, tgt_ptr, tgt_rows, excl_ptr, excl_rows,
+                              position, score, t))
+      return FM_OK;
+    wait_built(contexts, ctx->stream);
+    wait_built(candidates, ctx->stream);
+    return rank_positions_impl(ctx, contexts->dev, candidates->dev, t, lo, hi, position, score);
   });
 }
 

@@ -362,7 +362,8 @@ struct fm_ctx {
                       &route_sort.counts, &route_sort.digit_tot,
                       &sh_okey, &sh_mask, &sh_tcnt, &sh_tot, &sh_pay, &sh_skey, &sh_ent2, &repl_cnt,
                       &split_work.cnt, &split_work.off, &rank.sum_u, &rank.sum_c, &rank.cnt_u, &rank.cnt_c,
-                      &rank.bias_u, &rank.bias_c, &rank.lkey, &rank.lidx, &rank.out_idx, &rank.out_score};
+                      &rank.bias_u, &rank.bias_c, &rank.lkey, &rank.lidx, &rank.out_idx, &rank.out_score,
+                      &rank.sel_ptr, &rank.sel_rows, &rank.tgt_ptr, &rank.tgt_rows, &rank.position, &rank.pos_score};
     for (auto* b : bufs) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }

@@ -381,6 +381,9 @@ struct RankWork {
   DevBuf lkey, lidx;      // the context tile's split lists: uint64 keys, uint32 candidate rows
   DevBuf out_idx, out_score;  // int32 / double [U][n_top]
   DevBuf sel_ptr, sel_rows;   // fm_rank_*_select: the call's lists, int64 [U + 1] offsets and int32 candidate rows
+                              // (fm_rank_positions: its exclude lists)
+  DevBuf tgt_ptr, tgt_rows;   // fm_rank_positions: the target lists, laid out as sel_ptr / sel_rows
+  DevBuf position, pos_score;  // ... and its results, int32 / double per target
 };
 // a call's per-context row lists (host arrays, validated): mode FM_RANK_SELECT_*, ptr[U + 1], rows[ptr[U]]
 struct RankSelect {
@@ -414,6 +417,17 @@ void launch_rank_score_select(int select, const double* sum_u, const double* bia
 void launch_rank_merge(const uint64_t* lkey, const uint32_t* lidx, int64_t Ut, int splits, int n_top,
                        const uint32_t* cnt_u, const uint32_t* cnt_c, double w0, double lo, double hi, int32_t* out_idx,
                        double* out_score, hipStream_t st);
+// fm_rank_positions: contexts [0, Ut) of the given arrays (Ut <= rank_position_ctx_tile()) against all C
+// candidates.  Device lists as launch_rank_score_select takes them: tgt_ptr[Ut + 1] / tgt_rows, the
+// longest of the tile's target lists `longest` >= 1; ex_ptr / ex_rows the exclude lists, ex_ptr null for
+// none.  Per target e the rows of this launch's splits that rank before it are added onto position[e]
+// (zeroed by the caller; integer atomics) and score[e] is written: k_rank_merge's score of the pair;
+// -1 / NaN for a target on its context's exclude list.
+int64_t rank_position_ctx_tile();
+void launch_rank_position(const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut, const double* sum_c,
+                          const double* bias_c, const uint32_t* cnt_c, int64_t C, const int64_t* tgt_ptr,
+                          const int32_t* tgt_rows, int64_t longest, const int64_t* ex_ptr, const int32_t* ex_rows, int kp,
+                          int splits, double w0, double lo, double hi, int32_t* position, double* score, hipStream_t st);
 
 // fm_batch_from_rows: dst row s = src row rows[s] (device rows[B]); row_ptr_in[B + 1] (device) is the
 // result's row_ptr, computed by the host from the source's

@@ -33,6 +33,9 @@
 // fm_rank_candidates_select / fm_rank_batch_select restrict each context to (or away from) a list of
 // candidate rows: k_rank_score_sel takes k_rank_score's place between the same summaries and the
 // same merge (its comment below); a list's device copy is [U + 1] offsets and the rows, 4 bytes each.
+//
+// fm_rank_positions / fm_rank_positions_batch count instead of sorting: k_rank_position (its comment
+// below) behind the same summaries, with no split lists at all.
 #include <algorithm>
 
 #include "fm_device.h"
@@ -346,7 +349,199 @@ __global__ __launch_bounds__(kBlock) void k_rank_merge(const uint64_t* __restric
   }
 }
 
+// ---- exact positions (fm_rank_positions / fm_rank_positions_batch).  The position of a target row t
+// of context u among u's eligible rows is a count, #{eligible c : (key(u, c), c) before (key(u, t), t)},
+// so nothing is sorted but the targets themselves, once per block.
+//
+// Block (x, y): context y of the launch; x = tile * splits + s, tile a run of kRankChunk of the
+// context's targets (tgt_rows[tgt_ptr[u] ..), strictly ascending), s a split of the candidate chunks cut
+// as k_rank_score's.  A context with fewer tiles leaves its further blocks without work.
+//   prologue  the tile's keys by score_row (the bits the ranking kernels sort), each with its index in
+//             the tile as the tie-break -- the rows of a list ascend, so among targets the index orders
+//             as the row does -- sorted descending over the power of two that holds them; the padding
+//             sorts last.  lrow keeps the rows by index for the compare with a candidate.
+//   chunks    the exclude list enters as k_rank_score_sel's kSelExcept does (two masks in turn, so a
+//             chunk's mask is cleared while the last one is still read).  An eligible row finds by
+//             binary search the first sorted target it ranks before: it beats that one and all behind
+//             it, and not itself.  p = 0 (all of them) is counted in a register, p = m (none) not at
+//             all, the rest by an integer LDS atomic on hist[p]: any order of arrival, the same counts.
+//   epilogue  the inclusive prefix sum of hist is each sorted target's count in this split.  The
+//             splits add theirs onto the zeroed output with an integer atomic; split 0 writes the
+//             score.  A target found in the context's own exclude list gets -1 / NaN from split 0 and
+//             no count from anyone.
+constexpr int kPosCtxTile = 65535;  // contexts of one launch: the grid's y extent
+
+__device__ __forceinline__ void bitonic_sort_n(uint64_t* key, uint32_t* row, int n) {
+  for (int kk = 2; kk <= n; kk <<= 1)
+    for (int j = kk >> 1; j > 0; j >>= 1) bitonic_stage(key, row, j, kk, n);
+}
+
+__global__ __launch_bounds__(kBlock) void k_rank_position(
+    const double* __restrict__ sum_u, const double* __restrict__ bias_u, const uint32_t* __restrict__ cnt_u,
+    const double* __restrict__ sum_c, const double* __restrict__ bias_c, const uint32_t* __restrict__ cnt_c, int64_t C,
+    const int64_t* __restrict__ tgt_ptr, const int32_t* __restrict__ tgt_rows, const int64_t* __restrict__ ex_ptr,
+    const int32_t* __restrict__ ex_rows, int kp, int splits, double w0, double lo, double hi, int32_t* __restrict__ position,
+    double* __restrict__ score) {
+  __shared__ double su[256];  // the context's S (kp <= 256)
+  __shared__ uint64_t tkey[kRankChunk];   // the tile's keys, sorted descending
+  __shared__ uint32_t tidx[kRankChunk];   // ... and each one's index in the tile
+  __shared__ uint32_t lrow[kRankChunk];   // the tile's candidate rows by index
+  __shared__ uint32_t hist[kRankChunk];   // hist[p]: rows whose first beaten target is sorted entry p
+  __shared__ uint32_t mask[2][kMaskWords];
+  __shared__ uint32_t wsum[kBlock / 64];
+  const int tid = threadIdx.x;
+  const int64_t u = blockIdx.y;
+  const int tile = blockIdx.x / splits, s = blockIdx.x % splits;
+  const int64_t t0 = tgt_ptr[u] + (int64_t)tile * kRankChunk;
+  if (t0 >= tgt_ptr[u + 1]) return;  // the whole block: a context with fewer targets than the call's longest list
+  const int m = tgt_ptr[u + 1] - t0 < kRankChunk ? (int)(tgt_ptr[u + 1] - t0) : kRankChunk;
+  int n = 1;
+  while (n < m) n <<= 1;
+  const bool ex = ex_ptr != nullptr;
+  const int l0 = ex ? (int)ex_ptr[u] : 0, l1 = ex ? (int)ex_ptr[u + 1] : 0;  // ex_ptr[U] < 2^31
+  const int64_t nch = (C + kRankChunk - 1) / kRankChunk;
+  const int64_t ch0 = nch * s / splits, ch1 = nch * (s + 1) / splits;
+  for (int f = tid; f < kp; f += kBlock) su[f] = sum_u[u * kp + f];
+  const double base = w0 + bias_u[u];
+  const bool learned_u = cnt_u[u] != 0;
+  __syncthreads();
+  for (int i = tid; i < kRankChunk; i += kBlock) {
+    uint64_t k = kWorstKey;
+    uint32_t x = kNoRow;
+    if (i < m) {
+      const uint32_t r = (uint32_t)tgt_rows[t0 + i];
+      lrow[i] = r;
+      k = score_row(su, base, learned_u, sum_c, bias_c, cnt_c, r, kp, w0);
+      x = (uint32_t)i;
+    }
+    tkey[i] = k;
+    tidx[i] = x;
+    hist[i] = 0;
+  }
+  __syncthreads();
+  bitonic_sort_n(tkey, tidx, n);
+
+  int cur = l0;  // the first exclude entry at or after the chunk's first row
+  if (ex) {
+    int top = l1;
+    const int64_t first = ch0 * kRankChunk;
+    while (cur < top) {
+      const int mid = cur + (top - cur) / 2;
+      if (ex_rows[mid] < first) cur = mid + 1; else top = mid;
+    }
+  }
+  uint32_t all = 0;  // rows of this thread that rank before every target of the tile
+  for (int64_t ch = ch0; ch < ch1; ++ch) {
+    const int64_t c0 = ch * kRankChunk;
+    const uint32_t* mk = mask[(ch - ch0) & 1];
+    if (ex) {
+      uint32_t* mw = mask[(ch - ch0) & 1];
+      if (tid < kMaskWords) mw[tid] = 0;
+      __syncthreads();
+      for (int e = cur + tid; e < l1; e += kBlock) {
+        const int64_t d = (int64_t)ex_rows[e] - c0;
+        if (d >= kRankChunk) break;
+        if (d >= 0) atomicOr(&mw[d >> 5], 1u << (d & 31));
+      }
+      __syncthreads();
+      int marked = __popc(mk[tid & (kMaskWords - 1)]);  // every 32 lanes hold the 32 words: their sum, in each lane
+      for (int d = kMaskWords / 2; d > 0; d >>= 1) marked += __shfl_xor(marked, d);
+      cur += __builtin_amdgcn_readfirstlane(marked);
+    }
+    uint64_t key[kRankPer];
+    bool live[kRankPer];
+#pragma unroll
+    for (int j = 0; j < kRankPer; ++j) {
+      const int i = tid + j * kBlock;
+      const int64_t c = c0 + i;
+      live[j] = c < C && !(ex && ((mk[i >> 5] >> (i & 31)) & 1u));
+      key[j] = live[j] ? score_row(su, base, learned_u, sum_c, bias_c, cnt_c, c, kp, w0) : kWorstKey;
+    }
+#pragma unroll
+    for (int j = 0; j < kRankPer; ++j) {
+      if (!live[j]) continue;
+      const uint32_t c = (uint32_t)(c0 + tid + j * kBlock);
+      int p = 0, q = m;  // the first sorted target in [0, m) that (key, c) ranks before; m: none
+      while (p < q) {
+        const int mid = (p + q) >> 1;
+        const uint64_t kt = tkey[mid];
+        if (key[j] > kt || (key[j] == kt && c < lrow[tidx[mid]])) q = mid; else p = mid + 1;
+      }
+      if (p == 0) ++all;
+      else if (p < m) atomicAdd(&hist[p], 1u);
+    }
+  }
+  for (int d = 32; d > 0; d >>= 1) all += __shfl_xor(all, d);
+  if ((tid & 63) == 0 && all) atomicAdd(&hist[0], all);
+  __syncthreads();
+
+  // inclusive prefix sum of hist: entry i of the sorted tile is beaten by count(i) rows of this split
+  uint32_t h[kRankPer], run = 0;
+#pragma unroll
+  for (int j = 0; j < kRankPer; ++j) {
+    run += hist[tid * kRankPer + j];
+    h[j] = run;
+  }
+  uint32_t x = run;
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t y = __shfl_up(x, d);
+    if ((tid & 63) >= d) x += y;
+  }
+  if ((tid & 63) == 63) wsum[tid >> 6] = x;
+  __syncthreads();
+  uint32_t off = x - run;
+  for (int wv = 0; wv < (tid >> 6); ++wv) off += wsum[wv];
+#pragma unroll
+  for (int j = 0; j < kRankPer; ++j) {
+    const int i = tid * kRankPer + j;
+    if (i >= m) continue;  // the padding sorted behind the m targets
+    const uint32_t x_t = tidx[i];
+    const uint32_t r = lrow[x_t];
+    bool out = false;  // the target is on the context's own exclude list
+    if (ex) {
+      int a = l0, b = l1;
+      while (a < b) {
+        const int mid = a + (b - a) / 2;
+        if ((uint32_t)ex_rows[mid] < r) a = mid + 1; else b = mid;
+      }
+      out = a < l1 && (uint32_t)ex_rows[a] == r;
+    }
+    const int64_t e = t0 + x_t;
+    if (out) {
+      if (s == 0) {
+        position[e] = -1;
+        score[e] = __longlong_as_double(0x7FF8000000000000ll);
+      }
+      continue;
+    }
+    const uint32_t count = off + h[j];
+    if (count) atomicAdd(&position[e], (int32_t)count);
+    if (s == 0) {
+      double y = w0;  // a pair without a learned entry: globalBias, unclamped (k_rank_merge's rule)
+      if (learned_u || cnt_c[r] != 0) y = fmin(fmax(value_of(tkey[i]), lo), hi);
+      score[e] = y;
+    }
+  }
+}
+
 }  // namespace
+
+int64_t rank_position_ctx_tile() { return kPosCtxTile; }
+
+void launch_rank_position(const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut, const double* sum_c,
+                          const double* bias_c, const uint32_t* cnt_c, int64_t C, const int64_t* tgt_ptr,
+                          const int32_t* tgt_rows, int64_t longest, const int64_t* ex_ptr, const int32_t* ex_rows, int kp,
+                          int splits, double w0, double lo, double hi, int32_t* position, double* score, hipStream_t st) {
+  FM_REQUIRE(kp <= 256, "dimFactorization > 256 is not supported");
+  FM_REQUIRE(Ut >= 1 && Ut <= kPosCtxTile && C >= 1 && C < (int64_t(1) << 31) && longest >= 1 && longest <= C,
+             "rank positions: bad shape");
+  FM_REQUIRE(splits >= 1 && splits <= kRankMaxSplits && splits <= (C + kRankChunk - 1) / kRankChunk,
+             "rank positions: every split needs a chunk");
+  const int64_t tiles = (longest + kRankChunk - 1) / kRankChunk;  // < 2^21, times splits <= 64: below 2^31
+  hipLaunchKernelGGL(k_rank_position, dim3((unsigned)(tiles * splits), (unsigned)Ut), dim3(kBlock), 0, st, sum_u, bias_u, cnt_u,
+                     sum_c, bias_c, cnt_c, C, tgt_ptr, tgt_rows, ex_ptr, ex_rows, kp, splits, w0, lo, hi, position, score);
+  FM_HIP_CHECK(hipGetLastError());
+}
 
 int rank_splits(int64_t C, int64_t U) {
   const int64_t nch = (C + kRankChunk - 1) / kRankChunk;

@@ -470,6 +470,39 @@ class FMContext:
         m = n_ctx * n_top
         return idx[:m].reshape(n_ctx, n_top), score[:m].reshape(n_ctx, n_top)
 
+    def rank_positions(self, contexts: N.CSRHost, candidates: N.CSRHost, targets, min_label: float, max_label: float, *,
+                       exclude=None):
+        """Where each context's target rows land in its order over its eligible candidate rows
+        (fm_rank_positions): (ptr int64 [U + 1], rows int32, position int32, score float64), the last
+        three per target, context u's at ptr[u] .. ptr[u + 1].  position is the 0-based rank among all
+        candidate rows except the context's ``exclude`` list -- exact for any number of candidates --
+        by rank()'s key and tie-break; score is rank()'s for the pair.  A target that is itself
+        excluded has position -1 and score NaN.
+
+        targets / exclude: per context a list of candidate rows, as rank(only= / exclude=) takes them;
+        they are sorted and de-duplicated here, so ``rows`` tells which target each result belongs to."""
+        return self._rank_positions(self._lib.fm_rank_positions, "fm_rank_positions", C.byref(contexts.c),
+                                    C.byref(candidates.c), contexts.n_rows, targets, min_label, max_label, exclude)
+
+    def rank_positions_batch(self, contexts: DeviceBatch, candidates: DeviceBatch, targets, min_label: float,
+                             max_label: float, *, exclude=None):
+        """rank_positions over device-resident batches of this context (fm_rank_positions_batch)."""
+        return self._rank_positions(self._lib.fm_rank_positions_batch, "fm_rank_positions_batch", contexts.handle,
+                                    candidates.handle, contexts.n_rows, targets, min_label, max_label, exclude)
+
+    def _rank_positions(self, fn, what, contexts, candidates, n_ctx, targets, min_label, max_label, exclude):
+        if targets is None:
+            raise ValueError("targets: one list of candidate rows per context")
+        ptr, rows = normalize_row_lists(targets, n_ctx)
+        ex = (None, None) if exclude is None else normalize_row_lists(exclude, n_ctx)
+        n = max(len(rows), 1)
+        position = np.zeros(n, dtype=np.int32)
+        score = np.zeros(n)
+        N.check(fn(self.handle, contexts, candidates, N.ptr(ptr, C.c_int64), N.ptr(rows, C.c_int32),
+                   None if ex[0] is None else N.ptr(ex[0], C.c_int64), None if ex[1] is None else N.ptr(ex[1], C.c_int32),
+                   float(min_label), float(max_label), N.ptr(position, C.c_int32), N.ptr(score, C.c_double)), what)
+        return ptr, rows, position[: len(rows)], score[: len(rows)]
+
     def loss_grad(self, csr: N.CSRHost, initial_sd: float | None = None, seed: int = 0):
         """calcLossGrad per entry (pred, loss, deltaWi, deltaVi).  initial_sd: ids the model lacks
         get their own N(0, initial_sd^2) draws per entry (fm_calc_loss_grad, keyed by seed); None:

@@ -26,7 +26,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _native as N
-from .engine import EvalSums, FMContext
+from .engine import EvalSums, FMContext, normalize_row_lists
 from .linalg import DenseVector, Vector, Vectors, active_map
 
 log = logging.getLogger("org.apache.spark.ml.fm")
@@ -281,6 +281,36 @@ class FactorizationMachinesModel:
                                         exclude=exclude, only=only)
         recs = [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
         return contexts.with_column("recommendations", recs)
+
+    def rankPositions(self, contexts: DataFrame, candidates: DataFrame, targets, exclude=None) -> DataFrame:
+        """Where each context's target rows (its held-out positives, say) rank among the rows of
+        `candidates` it has not seen: one row per target with the columns ``context`` (row of
+        `contexts`), ``candidate`` (row of `candidates`), ``position`` (0-based rank in recommend's order
+        over all candidate rows except the context's ``exclude`` list; exact however many candidates
+        there are) and ``score`` (recommend's prediction for the pair).  targets / exclude: per row of
+        `contexts` a list of row indices of `candidates`, as recommend's lists.  A target that is also
+        excluded has position -1 and score NaN.  One device call (fm_rank_positions); a row-sharded
+        model refuses with FMError, as recommend."""
+        ptr, rows, position, score, _ = self._rank_positions(contexts, candidates, targets, exclude)
+        ctx_of = np.repeat(np.arange(len(ptr) - 1), np.diff(ptr))
+        return DataFrame({"context": ctx_of.tolist(), "candidate": rows.tolist(), "position": position.tolist(),
+                          "score": score.tolist()})
+
+    def _rank_positions(self, contexts, candidates, targets, exclude):
+        """rankPositions' arrays (ptr, rows, position, score) and each context's number of eligible rows."""
+        fcol = self._params["featuresCol"]
+        _check_schema(contexts, fcol, None)
+        _check_schema(candidates, fcol, None)
+        rows = []
+        for df in (contexts, candidates):
+            rp, col, val = _explode(df[fcol])
+            rows.append(N.CSRHost(rp, col, val, np.zeros(df.count())))
+        n_ctx, n_cand = contexts.count(), candidates.count()
+        out = self._ctx.rank_positions(rows[0], rows[1], targets, self.getMinLabel(), self.getMaxLabel(), exclude=exclude)
+        n_eligible = np.full(n_ctx, n_cand, dtype=np.int64)
+        if exclude is not None:
+            n_eligible -= np.diff(normalize_row_lists(exclude, n_ctx)[0])
+        return (*out, n_eligible)
 
     def calcLossGrad(self, dfSampleIndexed: DataFrame, initialSd: float, seed: int = 0) -> DataFrame:
         """Model.scala:135-234: one row per active entry with columns label, sampleId,

@@ -23,7 +23,8 @@ import numpy as np
 from .ml import DataFrame, Param
 from .sampler import next_doubles
 
-__all__ = ["Param", "ParamGridBuilder", "CrossValidator", "CrossValidatorModel", "RegressionEvaluator", "k_fold"]
+__all__ = ["Param", "ParamGridBuilder", "CrossValidator", "CrossValidatorModel", "RegressionEvaluator", "RankingEvaluator",
+           "ranking_metric", "k_fold"]
 
 
 def java_string_hash(s: str) -> int:
@@ -131,6 +132,107 @@ class RegressionEvaluator:
             return float(s.rmse)
         y = np.asarray(dataset[model._params["labelCol"]], dtype=np.float64)
         return float(s.r2(float(np.sum((y - y.mean()) ** 2))))
+
+
+RANKING_METRICS = ("ndcgAtK", "precisionAtK", "recallAtK", "hitRateAtK", "meanAveragePrecision", "meanReciprocalRank",
+                   "auc")
+
+
+def ranking_metric(name: str, k: int, ptr, position, n_eligible):
+    """(mean over the contexts used, number of contexts used) of one ranking metric, from exact
+    positions: context u's targets sit at ptr[u] .. ptr[u + 1] of ``position`` (0-based ranks among the
+    context's n_eligible[u] eligible rows; -1: a target that is not eligible, left out).  Relevance is
+    binary: a row is relevant where it is a target (the definitions of Spark's RankingMetrics).
+    With p_0 < p_1 < ... the T positions of a context's eligible targets:
+      precisionAtK          #{p_j < k} / k
+      recallAtK             #{p_j < k} / T
+      hitRateAtK            1 where some p_j < k
+      ndcgAtK               sum_{p_j < k} 1 / log2(p_j + 2)  over  sum_{i < min(k, T)} 1 / log2(i + 2)
+      meanAveragePrecision  (1 / T) sum_j (j + 1) / (p_j + 1), over the full ranking
+      meanReciprocalRank    1 / (p_0 + 1)
+      auc                   the share of (target, eligible non-target) pairs with the target ranked
+                            first: sum_j ((N - 1 - p_j) - (T - 1 - j)) / (T (N - T)), N = n_eligible[u]
+    A context without an eligible target -- for auc also one without an eligible non-target -- is
+    left out of the mean; with no context left the value is NaN."""
+    if name not in RANKING_METRICS:
+        raise ValueError(f"unsupported metric {name!r}")
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    ptr = np.asarray(ptr, dtype=np.int64)
+    position = np.asarray(position, dtype=np.int64)
+    n_eligible = np.asarray(n_eligible, dtype=np.int64)
+    if ptr.ndim != 1 or len(ptr) < 1 or len(n_eligible) != len(ptr) - 1 or ptr[0] != 0 or ptr[-1] != len(position):
+        raise ValueError("ptr must hold one offset per context and one more, from 0 to len(position)")
+    total, used = 0.0, 0
+    for u in range(len(ptr) - 1):
+        p = position[ptr[u]:ptr[u + 1]]
+        p = np.sort(p[p >= 0])
+        T, n = len(p), int(n_eligible[u])
+        if T == 0 or (name == "auc" and n <= T):
+            continue
+        hits = int(np.sum(p < k))
+        if name == "precisionAtK":
+            v = hits / k
+        elif name == "recallAtK":
+            v = hits / T
+        elif name == "hitRateAtK":
+            v = float(hits > 0)
+        elif name == "ndcgAtK":
+            v = float(np.sum(1.0 / np.log2(p[:hits] + 2.0)) / np.sum(1.0 / np.log2(np.arange(min(k, T)) + 2.0)))
+        elif name == "meanAveragePrecision":
+            v = float(np.mean((np.arange(T) + 1.0) / (p + 1.0)))
+        elif name == "meanReciprocalRank":
+            v = 1.0 / (float(p[0]) + 1.0)
+        else:  # auc: non-targets behind target j = rows behind it minus targets behind it
+            v = float(np.sum((n - 1 - p) - (T - 1 - np.arange(T)))) / (T * (n - T))
+        total += v
+        used += 1
+    return (total / used if used else float("nan")), used
+
+
+class RankingEvaluator:
+    """Ranking quality of held-out rows from their exact positions (fm_rank_positions): for every
+    context, where its targets land among everything it has not seen.  metricName: ndcgAtK (default),
+    precisionAtK, recallAtK, hitRateAtK, meanAveragePrecision, meanReciprocalRank, auc
+    (``ranking_metric`` has the definitions); k (default 10) for the AtK ones.  After an evaluation
+    ``numContextsUsed`` holds the number of contexts the mean was taken over."""
+
+    def __init__(self):
+        self._params = {"metricName": "ndcgAtK", "k": 10}
+        self.numContextsUsed = None
+
+    def setMetricName(self, v):
+        if v not in RANKING_METRICS:
+            raise ValueError(f"unsupported metric {v!r}")
+        self._params["metricName"] = v
+        return self
+
+    def getMetricName(self):
+        return self._params["metricName"]
+
+    def setK(self, v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError("k must be an integer >= 1")
+        self._params["k"] = int(v)
+        return self
+
+    def getK(self) -> int:
+        return self._params["k"]
+
+    def isLargerBetter(self) -> bool:
+        return True
+
+    def evaluatePositions(self, ptr, position, n_eligible) -> float:
+        """The metric from positions alone (pure NumPy, see ranking_metric)."""
+        value, self.numContextsUsed = ranking_metric(self._params["metricName"], self._params["k"], ptr, position, n_eligible)
+        return value
+
+    def evaluateModel(self, model, contexts: DataFrame, candidates: DataFrame, targets, exclude=None) -> float:
+        """The metric of `model` for the contexts' target rows among `candidates` minus each context's
+        ``exclude`` list (the arguments of model.rankPositions): one device call for the positions."""
+        ptr, _, position, _, n_eligible = model._rank_positions(contexts, candidates, targets, exclude)
+        return self.evaluatePositions(ptr, position, n_eligible)
 
 
 def k_fold(dataset: DataFrame, num_folds: int, seed: int):

@@ -173,7 +173,9 @@ int fm_sync(fm_ctx* ctx);
  * the largest host batch it has held (steady after every batch size has passed through both).  The
  * scratch of fm_rank_candidates / fm_rank_batch is not covered either: it is sized by the two row
  * sets and n_top at the call, and kept; nor are the device copies of the lists of
- * fm_rank_candidates_select / fm_rank_batch_select, sized by U and the lists' total length. */
+ * fm_rank_candidates_select / fm_rank_batch_select, sized by U and the lists' total length; nor the
+ * scratch of fm_rank_positions / fm_rank_positions_batch: the same row summaries, the device copies of
+ * its target and exclude lists and its results, 12 bytes per target. */
 int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz);
 
 /* ---- tables (C9: Strength / FactorizedInteraction, Model.scala:275-289) ------------ */
@@ -429,6 +431,41 @@ int fm_rank_candidates_select(fm_ctx* ctx, const fm_csr* contexts, const fm_csr*
 int fm_rank_batch_select(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t select,
                          const int64_t* sel_ptr, const int32_t* sel_rows, int32_t n_top,
                          double min_label, double max_label, int32_t* top_index, double* top_score);
+/* Exact rank positions, the evaluation side of ranking: where do a context's held-out rows land among
+ * everything it has not seen?  Context u's targets are the candidate rows tgt_rows[tgt_ptr[u] ..
+ * tgt_ptr[u + 1]), its excluded rows (what it rated in training) excl_rows[excl_ptr[u] .. excl_ptr[u + 1]);
+ * excl_ptr == NULL excludes nothing (excl_rows is then ignored).  For e over tgt_rows (host buffers of
+ * tgt_ptr[U] elements):
+ *   position[e] : the 0-based position of that target in the context's order over its eligible rows --
+ *           all candidate rows except its excluded ones: the number of eligible rows that rank before
+ *           it.  The key and the order are fm_rank_candidates': the unclamped yhat descending, a pair
+ *           without a learned entry at w0, ties by ascending candidate row.  Exact for any C (a count,
+ *           not a sort: nothing is limited by FM_RANK_MAX_TOP), and a sum of integers, so equal calls
+ *           give equal bits.  The order of NaN keys is unspecified.
+ *   score[e] : what top_score holds for the pair: the clamped value, w0 unclamped where nothing is learned.
+ *   a target that is itself excluded : position -1, score NaN; the other targets are not affected.
+ *   the defining property : for every target with 0 <= position[e] < n_top,
+ *           fm_rank_*_select(FM_RANK_SELECT_EXCEPT, the same exclude lists, n_top) -- with excl_ptr ==
+ *           NULL the unrestricted call -- returns that row at top_index[u * n_top + position[e]] with
+ *           top_score equal to score[e] bit for bit.
+ *   lists : both obey the _select list rules (offsets from 0, non-decreasing, below 2^31; rows in [0, C),
+ *           strictly ascending per list), checked in one pass before anything is enqueued, with the same
+ *           messages behind "target list: " or "exclude list: " and the arguments' names (tgt_ptr,
+ *           excl_ptr, ...).  tgt_ptr == NULL is FM_ERR_ARG.  A refused call changes nothing on the
+ *           device.
+ * U = 0 is FM_OK with nothing written, and so is tgt_ptr[U] == 0 (valid lists, no target).  Everything
+ * else as fm_rank_candidates / fm_rank_batch: C = 0 with U >= 1 and C >= 2^31 are FM_ERR_ARG, null
+ * pointers, the CSRs, batches of another context, split datasets, a replicated group (host rows only,
+ * answered by its first rank), a row-sharded table (FM_ERR_ARG), synchronous on the main stream behind
+ * every queued step; the table, the epoch, the loss and evaluation histories and fm_last_stats are
+ * unchanged.  The lists' device copies and the results are scratch of the context like the rest and
+ * grow to the largest call. */
+int fm_rank_positions(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, const int64_t* tgt_ptr,
+                      const int32_t* tgt_rows, const int64_t* excl_ptr, const int32_t* excl_rows,
+                      double min_label, double max_label, int32_t* position, double* score);
+int fm_rank_positions_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, const int64_t* tgt_ptr,
+                            const int32_t* tgt_rows, const int64_t* excl_ptr, const int32_t* excl_rows,
+                            double min_label, double max_label, int32_t* position, double* score);
 /* calcLossGrad (Model.scala:135-234), per active entry e in CSR order:
  * pred[e] = yhat of its row (unclamped), loss[e] = (yhat - y)^2, delta_w[e] = x,
  * delta_v[e*k + f] = vfxiSum_f * x - (v_f * x) * x.  Any output may be NULL.
