@@ -108,6 +108,9 @@ SIGNATURES = {
     "fm_batch_destroy": (None, [_P]),
     "fm_batch_prepare": (C.c_int, [_P, _P]),
     "fm_batch_from_rows": (C.c_int, [_P, _P, _I64P, C.c_int64, C.POINTER(_P)]),
+    "fm_batch_from_pairs": (C.c_int, [_P, _P, _P, _I32P, _I32P, _DP, C.c_int64, C.POINTER(_P)]),
+    "fm_batch_sample_pairs": (C.c_int, [_P, _P, _P, _I32P, _I32P, C.c_int64, C.c_int32, _I64P, _I32P, C.c_double,
+                                        C.c_double, C.c_uint64, C.POINTER(_P), _I32P]),
     "fm_batch_create_splits": (C.c_int, [_P, C.POINTER(fm_csr), C.c_int32, _I64P, C.POINTER(_P)]),
     "fm_batch_layout_splits": (C.c_int, [_P, C.POINTER(fm_csr), C.c_int32, _I64P, _I64P, C.POINTER(_P)]),
     "fm_batch_split_view": (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P)]),

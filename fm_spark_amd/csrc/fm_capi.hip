@@ -1181,18 +1181,38 @@ static int64_t rank_list_check(const std::string& what, const std::string& pname
     FM_REQUIRE(ptr[u + 1] < (int64_t(1) << 31), what + pname + "[" + std::to_string(u + 1) + "] must be < 2^31");
   }
   FM_REQUIRE(ptr[U] == 0 || rows != nullptr, what + "null " + rname + " with a list that is not empty");
+  // The rows, context chunk after context chunk on the pool's threads once the lists are long (fm_batch_sample_pairs
+  // hands over every context's list at every call: 13.1M rows took 9.7 ms on one thread, tools/pair_bench.py); a
+  // few short lists run inline.  Each chunk stops at its first offending entry; the lowest one is reported, as by
+  // one pass in order.
+  const int64_t T = std::min<int64_t>(chunk_count(ptr[U], int64_t(1) << 18), std::max<int64_t>(U, 1));
+  std::vector<int64_t> bad_u(T, -1), bad_e(T, -1), longest_of(T, 0);
+  parallel_chunks_t(U, T, [&](int64_t t, int64_t u0, int64_t u1) {
+    int64_t lg = 0;
+    for (int64_t u = u0; u < u1; ++u) {
+      for (int64_t e = ptr[u]; e < ptr[u + 1]; ++e) {
+        const int64_t r = rows[e];
+        const bool in_range = r >= 0 && r < Cn, in_order = e == ptr[u] || rows[e - 1] < r;
+        if (in_range && in_order) continue;
+        bad_u[t] = u;
+        bad_e[t] = e;
+        return;
+      }
+      lg = std::max(lg, ptr[u + 1] - ptr[u]);
+    }
+    longest_of[t] = lg;
+  });
   int64_t longest = 0;
-  for (int64_t u = 0; u < U; ++u) {
-    for (int64_t e = ptr[u]; e < ptr[u + 1]; ++e) {
-      const int64_t r = rows[e];
-      const bool in_range = r >= 0 && r < Cn, in_order = e == ptr[u] || rows[e - 1] < r;
-      if (in_range && in_order) continue;
+  for (int64_t t = 0; t < T; ++t) {
+    if (bad_u[t] >= 0) {
+      const int64_t u = bad_u[t], e = bad_e[t], r = rows[e];
+      const bool in_range = r >= 0 && r < Cn;
       const std::string at = what + "context " + std::to_string(u) + ", position " + std::to_string(e - ptr[u]) + ": row " +
                              std::to_string(r);
       FM_REQUIRE(in_range, at + " is out of range [0, " + std::to_string(Cn) + ")");
-      FM_REQUIRE(in_order, at + " after row " + std::to_string(rows[e - 1]) + ": a list must be strictly ascending");
+      FM_REQUIRE(false, at + " after row " + std::to_string(rows[e - 1]) + ": a list must be strictly ascending");
     }
-    longest = std::max(longest, ptr[u + 1] - ptr[u]);
+    longest = std::max(longest, longest_of[t]);
   }
   return longest;
 }
@@ -1435,6 +1455,241 @@ int fm_rank_positions_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidate
     wait_built(contexts, ctx->stream);
     wait_built(candidates, ctx->stream);
     return rank_positions_impl(ctx, contexts->dev, candidates->dev, t, lo, hi, position, score);
+  });
+}
+
+// ---- pair batches (fm_batch_from_pairs / fm_batch_sample_pairs; fm_pairs.hip) ----
+// the rules both calls share for their two sources and lists of n pairs
+static void pair_args_check(const fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, fm_batch** out,
+                            const void* list_a, const void* list_b, int64_t n, const char* call) {
+  FM_REQUIRE(out != nullptr && contexts != nullptr && candidates != nullptr, "null argument");
+  FM_REQUIRE(contexts->owner == ctx && candidates->owner == ctx, "contexts / candidates belong to another context");
+  FM_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "n out of range");
+  FM_REQUIRE(n == 0 || (list_a != nullptr && list_b != nullptr), "null pair lists");
+  FM_REQUIRE(!ctx->group && !contexts->grp && !candidates->grp,
+             std::string(call) + " needs both row sets whole on one device: a multi-GPU context's batches are cut over its "
+                                 "ranks (not built from pairs yet)");
+  FM_REQUIRE((int64_t)contexts->host_rp.size() == contexts->dev.n_rows + 1 &&
+                 (int64_t)candidates->host_rp.size() == candidates->dev.n_rows + 1,
+             "contexts and candidates must be batches made by fm_batch_create");
+}
+
+// out_batch for two sources
+static OutBatch pair_out_batch(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, fm_batch** out) {
+  FM_REQUIRE(*out != contexts && *out != candidates, "out must be a batch of this context other than contexts and candidates");
+  return out_batch(ctx, contexts, out, false);
+}
+
+// pairs (pc[i], pd[i]), i < n, of two datasets (their host row_ptrs, U and Cn rows) -> rp[n + 1], the row_ptr
+// of the concatenated rows, on the pool's threads as selection_row_ptr; 0, or 1 / 2 for an index of pc / pd
+// out of range
+static int pair_row_ptr(const int64_t* urp, int64_t U, const int64_t* crp, int64_t Cn, const int32_t* pc, const int32_t* pd,
+                        int64_t n, int64_t* rp) {
+  rp[0] = 0;
+  const int64_t T = chunk_count(n, 8192);
+  std::vector<int64_t> tot(T + 1, 0);
+  std::atomic<int> bad{0};
+  parallel_chunks_t(n, T, [&](int64_t t, int64_t lo, int64_t hi) {
+    int64_t acc = 0;
+    for (int64_t i = lo; i < hi; ++i) {
+      const int64_t u = pc[i], c = pd[i];
+      if (u < 0 || u >= U || c < 0 || c >= Cn) {
+        bad.fetch_or(u < 0 || u >= U ? 1 : 2);
+        return;
+      }
+      acc += (urp[u + 1] - urp[u]) + (crp[c + 1] - crp[c]);
+      rp[i + 1] = acc;
+    }
+    tot[t + 1] = acc;
+  });
+  if (bad.load()) return (bad.load() & 1) ? 1 : 2;
+  for (int64_t t = 0; t < T; ++t) tot[t + 1] += tot[t];  // the chunks' offsets
+  if (T > 1)
+    parallel_chunks_t(n, T, [&](int64_t t, int64_t lo, int64_t hi) {
+      const int64_t add = tot[t];
+      if (add)
+        for (int64_t i = lo; i < hi; ++i) rp[i + 1] += add;
+    });
+  return 0;
+}
+
+// b is about to be refilled on the copy stream (as fm_batch_from_rows refills its result): a split view
+// detached, the events made, and the stream waiting for every queued read of the batch
+static hipStream_t pair_refill_begin(fm_ctx* ctx, fm_batch* b) {
+  b->detach_view();
+  b->ensure_events(ctx->stream);
+  if (!b->built) {
+    FM_HIP_CHECK(hipEventCreateWithFlags(&b->built, hipEventDisableTiming));
+    FM_HIP_CHECK(hipEventCreateWithFlags(&b->sel_copied, hipEventDisableTiming));
+    FM_HIP_CHECK(hipEventRecord(b->sel_copied, ctx->side));
+  }
+  if (!ctx->copy_stream) FM_HIP_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+  hipStream_t gs = ctx->copy_stream;
+  FM_HIP_CHECK(hipStreamWaitEvent(gs, b->last_use, 0));
+  if (b->sh && b->sh->last_use) FM_HIP_CHECK(hipStreamWaitEvent(gs, b->sh->last_use, 0));
+  if (b->prepared && b->ready) FM_HIP_CHECK(hipStreamWaitEvent(gs, b->ready, 0));
+  return gs;
+}
+
+static void pair_refill_end(fm_batch* b, const fm_batch* contexts, const fm_batch* candidates, hipStream_t gs) {
+  FM_HIP_CHECK(hipEventRecord(b->built, gs));
+  b->max_id = std::max(contexts->max_id, candidates->max_id);
+  b->prepared = false;  // a refilled batch is sorted again by its own fm_batch_prepare
+  b->host_rp.clear();   // not itself a dataset
+}
+
+int fm_batch_from_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, const int32_t* pair_ctx,
+                        const int32_t* pair_cand, const double* label, int64_t n, fm_batch** out) {
+  return guarded(ctx, [&]() -> int {
+    pair_args_check(ctx, contexts, candidates, out, pair_ctx, pair_cand, n, "fm_batch_from_pairs");
+    FM_REQUIRE(n == 0 || label != nullptr, "null label");
+    OutBatch res = pair_out_batch(ctx, contexts, candidates, out);
+    fm_batch* b = res.b;
+    // the staging of this batch's previous selection has been copied out
+    if (b->sel_copied) FM_HIP_CHECK(hipEventSynchronize(b->sel_copied));
+    // staging {row_ptr int64 [n + 1], label double [n], pair_ctx int32 [n], pair_cand int32 [n]}: the result's
+    // row_ptr straight into it from the two datasets' host row_ptrs (the indices validated on the way)
+    const size_t img = sizeof(int64_t) * ((size_t)n + 1) + sizeof(double) * (size_t)n + 2 * sizeof(int32_t) * (size_t)n;
+    b->sel_pin.ensure_slack(img);
+    int64_t* rp = reinterpret_cast<int64_t*>(b->sel_pin.p);
+    double* hl = reinterpret_cast<double*>(rp + n + 1);
+    int32_t* hc = reinterpret_cast<int32_t*>(hl + n);
+    int32_t* hd = hc + n;
+    const int bad = pair_row_ptr(contexts->host_rp.data(), contexts->dev.n_rows, candidates->host_rp.data(),
+                                 candidates->dev.n_rows, pair_ctx, pair_cand, n, rp);
+    FM_REQUIRE(bad != 1, "pair_ctx index out of [0, rows of contexts)");
+    FM_REQUIRE(bad != 2, "pair_cand index out of [0, rows of candidates)");
+    const int64_t N = rp[n];
+    FM_REQUIRE(N < (int64_t(1) << 31), "nnz must be < 2^31 per batch");
+    if (n > 0) {
+      std::memcpy(hl, label, sizeof(double) * (size_t)n);
+      std::memcpy(hc, pair_ctx, sizeof(int32_t) * (size_t)n);
+      std::memcpy(hd, pair_cand, sizeof(int32_t) * (size_t)n);
+    }
+    // batch-only work on the copy stream, behind every queued read of the batch (fm_batch_from_rows)
+    hipStream_t gs = pair_refill_begin(ctx, b);
+    size_batch(b->dev, n, N);
+    b->up.ensure_slack(img + 16);
+    FM_HIP_CHECK(hipMemcpyAsync(b->up.p, b->sel_pin.p, img, hipMemcpyHostToDevice, gs));
+    FM_HIP_CHECK(hipEventRecord(b->sel_copied, gs));
+    const int64_t* drp = b->up.as<int64_t>();
+    hipEvent_t e0 = ctx->prof_begin(gs);
+    if (n > 0) {
+      const double* dl = reinterpret_cast<const double*>(drp + n + 1);
+      const int32_t* dc = reinterpret_cast<const int32_t*>(dl + n);
+      launch_pair_rows(dc, dc + n, drp, dl, contexts->dev, candidates->dev, n, b->dev, gs);
+    } else {
+      FM_HIP_CHECK(hipMemcpyAsync(b->dev.row_ptr.p, drp, sizeof(int64_t), hipMemcpyDeviceToDevice, gs));
+    }
+    ctx->prof_end("pair_gather", e0, gs);
+    pair_refill_end(b, contexts, candidates, gs);
+    res.commit();
+    return FM_OK;
+  });
+}
+
+int fm_batch_sample_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, const int32_t* pos_ctx,
+                          const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, const int64_t* excl_ptr,
+                          const int32_t* excl_rows, double pos_label, double neg_label, uint64_t seed, fm_batch** out,
+                          int32_t* sampled) {
+  return guarded(ctx, [&]() -> int {
+    pair_args_check(ctx, contexts, candidates, out, pos_ctx, pos_cand, n_pos, "fm_batch_sample_pairs");
+    FM_REQUIRE(n_neg >= 0 && n_neg <= 1024, "n_neg must be in [0, 1024], got " + std::to_string(n_neg));
+    const int64_t per = (int64_t)n_neg + 1, B = n_pos * per;
+    FM_REQUIRE(B < (int64_t(1) << 31), "n_pos * (1 + n_neg) must be < 2^31");
+    const int64_t U = contexts->dev.n_rows, Cn = candidates->dev.n_rows;
+    FM_REQUIRE(Cn < (int64_t(1) << 31) && U < (int64_t(1) << 31), "fewer than 2^31 rows per source");
+    // (profile: the host phases of the lists beside the device phases, tools/pair_bench.py)
+    const auto host_ms = [](std::chrono::steady_clock::time_point t0) {
+      return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    };
+    auto t0 = std::chrono::steady_clock::now();
+    if (excl_ptr) rank_list_check("exclude list: ", "excl_ptr", "excl_rows", excl_ptr, excl_rows, U, Cn);
+    ctx->prof_host("pair_lists_check", host_ms(t0));
+    for (int64_t i = 0; i < n_pos; ++i) {
+      const int64_t u = pos_ctx[i], c = pos_cand[i];
+      FM_REQUIRE(u >= 0 && u < U, "pos_ctx index out of [0, rows of contexts)");
+      FM_REQUIRE(c >= 0 && c < Cn, "pos_cand index out of [0, rows of candidates)");
+      const int64_t L = excl_ptr ? excl_ptr[u + 1] - excl_ptr[u] : 0;
+      FM_REQUIRE(Cn - L >= 1, "context " + std::to_string(u) + " (positive " + std::to_string(i) +
+                                  ") has no eligible candidate row: its exclude list holds every row");
+    }
+    OutBatch res = pair_out_batch(ctx, contexts, candidates, out);
+    fm_batch* b = res.b;
+    // The draw, the lengths, the scan and the read-back of the entry count run in the context's scratch on
+    // the copy stream before *out is touched or waited for: the one host wait of this call is for them (and
+    // for what the copy stream held before: earlier gathers), never for the main or the side stream.
+    if (!ctx->copy_stream) FM_HIP_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    hipStream_t gs = ctx->copy_stream;
+    PairWork& w = ctx->pairs;
+    const size_t n_ex = excl_ptr ? (size_t)excl_ptr[U] : 0;
+    // staging: {total int64, pad} | excl_ptr int64 [U + 1] | pos_ctx, pos_cand int32 [n_pos] | excl_rows int32 [n_ex]
+    // | the drawn pairs' candidate rows int32 [B] on their way back (sampled != NULL)
+    const size_t o_ptr = 16, o_pc = o_ptr + sizeof(int64_t) * (excl_ptr ? (size_t)U + 1 : 0);
+    const size_t o_pd = o_pc + sizeof(int32_t) * (size_t)n_pos, o_ex = o_pd + sizeof(int32_t) * (size_t)n_pos;
+    const size_t o_back = (o_ex + sizeof(int32_t) * n_ex + 15) / 16 * 16;
+    const size_t lists_bytes = o_back - o_ptr;
+    ctx->pair_pin.ensure_slack(o_back + (sampled ? sizeof(int32_t) * (size_t)B : 0));
+    char* pin = reinterpret_cast<char*>(ctx->pair_pin.p);
+    t0 = std::chrono::steady_clock::now();
+    if (excl_ptr) std::memcpy(pin + o_ptr, excl_ptr, sizeof(int64_t) * ((size_t)U + 1));
+    if (n_pos > 0) {
+      std::memcpy(pin + o_pc, pos_ctx, sizeof(int32_t) * (size_t)n_pos);
+      std::memcpy(pin + o_pd, pos_cand, sizeof(int32_t) * (size_t)n_pos);
+    }
+    if (n_ex)
+      parallel_chunks((int64_t)n_ex, 1 << 20, [&](int64_t lo, int64_t hi) {
+        std::memcpy(pin + o_ex + sizeof(int32_t) * (size_t)lo, excl_rows + lo, sizeof(int32_t) * (size_t)(hi - lo));
+      });
+    ctx->prof_host("pair_lists_stage", host_ms(t0));
+    const size_t rows = (size_t)std::max<int64_t>(B, 1);
+    const size_t nchunks = (size_t)std::max<int64_t>(pair_scan_chunks(B), 1);
+    w.lists.ensure_slack(lists_bytes + 16);
+    w.pair_ctx.ensure_slack(sizeof(int32_t) * rows);
+    w.pair_cand.ensure_slack(sizeof(int32_t) * rows);
+    w.label.ensure_slack(sizeof(double) * rows);
+    w.len.ensure_slack(sizeof(uint32_t) * rows);
+    w.row_ptr.ensure_slack(sizeof(int64_t) * (rows + 1));
+    w.chunk_tot.ensure_slack(sizeof(int64_t) * nchunks);
+    w.chunk_off.ensure_slack(sizeof(int64_t) * nchunks);
+    w.total.ensure(sizeof(int64_t));
+    hipEvent_t e0 = ctx->prof_begin(gs);
+    if (lists_bytes) FM_HIP_CHECK(hipMemcpyAsync(w.lists.p, pin + o_ptr, lists_bytes, hipMemcpyHostToDevice, gs));
+    ctx->prof_end("pair_lists_upload", e0, gs);
+    e0 = ctx->prof_begin(gs);
+    const char* dl = w.lists.as<char>();  // the staging from o_ptr on
+    launch_pair_sample(reinterpret_cast<const int32_t*>(dl + (o_pc - o_ptr)), reinterpret_cast<const int32_t*>(dl + (o_pd - o_ptr)),
+                       n_pos, n_neg, excl_ptr ? reinterpret_cast<const int64_t*>(dl) : nullptr,
+                       reinterpret_cast<const int32_t*>(dl + (o_ex - o_ptr)), pos_label, neg_label, seed, contexts->dev,
+                       candidates->dev,
+                       w.pair_ctx.as<int32_t>(), w.pair_cand.as<int32_t>(), w.label.as<double>(), w.len.as<uint32_t>(),
+                       w.row_ptr.as<int64_t>(), w.chunk_tot.as<int64_t>(), w.chunk_off.as<int64_t>(), w.total.as<int64_t>(),
+                       gs);
+    ctx->prof_end("pair_draw", e0, gs);
+    FM_HIP_CHECK(hipMemcpyAsync(pin, w.total.p, sizeof(int64_t), hipMemcpyDeviceToHost, gs));
+    if (sampled && B > 0)
+      FM_HIP_CHECK(hipMemcpyAsync(pin + o_back, w.pair_cand.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, gs));
+    FM_HIP_CHECK(hipStreamSynchronize(gs));
+    const int64_t N = *reinterpret_cast<const int64_t*>(pin);
+    FM_REQUIRE(N < (int64_t(1) << 31), "nnz must be < 2^31 per batch");
+    if (sampled) {
+      const int32_t* back = reinterpret_cast<const int32_t*>(pin + o_back);
+      for (int64_t i = 0; i < n_pos; ++i)
+        for (int64_t j = 0; j < n_neg; ++j) sampled[i * n_neg + j] = back[i * per + 1 + j];
+    }
+    // only now is *out sized and refilled, behind every queued read of it (fm_batch_from_rows)
+    gs = pair_refill_begin(ctx, b);
+    size_batch(b->dev, B, N);
+    e0 = ctx->prof_begin(gs);
+    if (B > 0)
+      launch_pair_rows(w.pair_ctx.as<int32_t>(), w.pair_cand.as<int32_t>(), w.row_ptr.as<int64_t>(), w.label.as<double>(),
+                       contexts->dev, candidates->dev, B, b->dev, gs);
+    else
+      FM_HIP_CHECK(hipMemcpyAsync(b->dev.row_ptr.p, w.row_ptr.p, sizeof(int64_t), hipMemcpyDeviceToDevice, gs));
+    ctx->prof_end("pair_gather", e0, gs);
+    pair_refill_end(b, contexts, candidates, gs);
+    res.commit();
+    return FM_OK;
   });
 }
 

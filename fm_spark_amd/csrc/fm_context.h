@@ -206,6 +206,8 @@ struct fm_ctx {
   HostSlot hslot[2];                     // fm_step's double-buffered uploads
   int hnext = 0;
   hipStream_t copy_stream = nullptr;     // their host -> device copies
+  PairWork pairs;                        // fm_batch_sample_pairs scratch (fm_pairs.hip), copy stream only
+  Pinned pair_pin;                       // ... its lists' staging and read-backs (free again when the call returns)
   // profiling
   bool prof = false;
   std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -283,6 +285,7 @@ struct fm_ctx {
     if (pending.empty()) return;
     FM_HIP_CHECK(hipStreamSynchronize(stream));
     FM_HIP_CHECK(hipStreamSynchronize(side));
+    if (copy_stream) FM_HIP_CHECK(hipStreamSynchronize(copy_stream));  // the pair batches' phases (fm_pairs.hip)
     for (auto& pe : pending) {
       float ms = 0.f;
       FM_HIP_CHECK(hipEventElapsedTime(&ms, pe.second.first, pe.second.second));
@@ -363,7 +366,9 @@ struct fm_ctx {
                       &sh_okey, &sh_mask, &sh_tcnt, &sh_tot, &sh_pay, &sh_skey, &sh_ent2, &repl_cnt,
                       &split_work.cnt, &split_work.off, &rank.sum_u, &rank.sum_c, &rank.cnt_u, &rank.cnt_c,
                       &rank.bias_u, &rank.bias_c, &rank.lkey, &rank.lidx, &rank.out_idx, &rank.out_score,
-                      &rank.sel_ptr, &rank.sel_rows, &rank.tgt_ptr, &rank.tgt_rows, &rank.position, &rank.pos_score};
+                      &rank.sel_ptr, &rank.sel_rows, &rank.tgt_ptr, &rank.tgt_rows, &rank.position, &rank.pos_score,
+                      &pairs.lists, &pairs.pair_ctx, &pairs.pair_cand, &pairs.label, &pairs.len, &pairs.row_ptr,
+                      &pairs.chunk_tot, &pairs.chunk_off, &pairs.total};
     for (auto* b : bufs) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }

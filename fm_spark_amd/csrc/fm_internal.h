@@ -433,6 +433,32 @@ void launch_rank_position(const double* sum_u, const double* bias_u, const uint3
 // result's row_ptr, computed by the host from the source's
 void launch_select_rows(const BatchDev& src, const int64_t* rows, const int64_t* row_ptr_in, int64_t B, BatchDev& dst,
                         hipStream_t st);
+// ---------------------------------------------------------------- pair batches (fm_pairs.hip)
+// Scratch of fm_batch_sample_pairs, kept with the context (grown, never shrunk) and touched on the copy
+// stream alone (fm_pairs.hip's header).
+struct PairWork {
+  DevBuf lists;                // the call's lists: int64 excl_ptr [U + 1], then int32 pos_ctx, pos_cand [n_pos], excl_rows
+  DevBuf pair_ctx, pair_cand;  // int32 [B]: every output row's pair
+  DevBuf label;                // double [B]
+  DevBuf len;                  // uint32 [B]: every output row's entries
+  DevBuf row_ptr;              // int64 [B + 1]: their exclusive scan
+  DevBuf chunk_tot, chunk_off;  // int64 per scan chunk
+  DevBuf total;                // int64 [1]: the result's entries, read back by the host
+};
+// fm_batch_from_pairs / fm_batch_sample_pairs: dst row s = contexts row pair_ctx[s] followed by candidates
+// row pair_cand[s] (device lists [B]); row_ptr_in [B + 1] and label_in [B] (device) are the result's
+void launch_pair_rows(const int32_t* pair_ctx, const int32_t* pair_cand, const int64_t* row_ptr_in, const double* label_in,
+                      const BatchDev& contexts, const BatchDev& candidates, int64_t B, BatchDev& dst, hipStream_t st);
+// chunks of the row_ptr scan over B rows (the size of chunk_tot / chunk_off)
+int64_t pair_scan_chunks(int64_t B);
+// fm_batch_sample_pairs' device side before the gather: the B = n_pos (1 + n_neg) pairs (each positive,
+// then its drawn negatives; device lists, excl_ptr null for none), their labels and lengths, row_ptr
+// [B + 1] by the three-phase scan and total[0] = row_ptr[B]
+void launch_pair_sample(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, const int64_t* excl_ptr,
+                        const int32_t* excl_rows, double pos_label, double neg_label, uint64_t seed, const BatchDev& contexts,
+                        const BatchDev& candidates, int32_t* pair_ctx, int32_t* pair_cand, double* label, uint32_t* len,
+                        int64_t* row_ptr, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total, hipStream_t st);
+
 // fm_batch_create_splits: each split's own row_ptr (rebased to its first entry) into split_rp
 // [B + n_splits] and every entry's sample index made relative to its split's first row
 // (split_rows [n_splits + 1], device)

@@ -341,6 +341,61 @@ class FMContext:
         b = into if into is not None else DeviceBatch(self, None)
         return b.select_rows(data, rows)
 
+    def batch_from_pairs(self, contexts: DeviceBatch, candidates: DeviceBatch, pair_ctx, pair_cand, labels,
+                         into: DeviceBatch | None = None) -> DeviceBatch:
+        """The mini-batch whose row i is row pair_ctx[i] of `contexts` followed by row pair_cand[i] of
+        `candidates` (both resident batches of this context), labelled labels[i], built on the device
+        (fm_batch_from_pairs); `into` is refilled in place instead of creating a batch."""
+        pc = np.ascontiguousarray(pair_ctx, dtype=np.int32)
+        pd = np.ascontiguousarray(pair_cand, dtype=np.int32)
+        y = np.ascontiguousarray(labels, dtype=np.float64)
+        if not (pc.ndim == pd.ndim == y.ndim == 1 and len(pc) == len(pd) == len(y)):
+            raise ValueError("pair_ctx, pair_cand and labels must be flat and of one length")
+        b = into if into is not None else DeviceBatch(self, None)
+        h = b.handle if b.handle else C.c_void_p()
+        N.check(self._lib.fm_batch_from_pairs(self.handle, contexts.handle, candidates.handle, N.ptr(pc, C.c_int32),
+                                              N.ptr(pd, C.c_int32), N.ptr(y, C.c_double), len(pc), C.byref(h)),
+                "fm_batch_from_pairs")
+        return self._pair_batch(b, h, contexts, candidates)
+
+    def batch_sample_pairs(self, contexts: DeviceBatch, candidates: DeviceBatch, pos_ctx, pos_cand, n_neg: int, *,
+                           exclude=None, pos_label: float = 1.0, neg_label: float = 0.0, seed: int = 0,
+                           into: DeviceBatch | None = None, want_sampled: bool = False):
+        """The implicit-feedback mini-batch of the positives (pos_ctx[i], pos_cand[i]), each followed by
+        n_neg negatives drawn on the device uniformly over the candidate rows its context's ``exclude``
+        list does not hold (fm_batch_sample_pairs; the lists as rank(exclude=) takes them).  Returns the
+        batch, or (batch, sampled [n_pos, n_neg] int32 candidate rows) with want_sampled."""
+        ex = (None, None) if exclude is None else normalize_row_lists(exclude, contexts.n_rows)
+        return self._sample_pairs(contexts, candidates, pos_ctx, pos_cand, n_neg, ex, pos_label, neg_label, seed, into,
+                                  want_sampled)
+
+    def _sample_pairs(self, contexts, candidates, pos_ctx, pos_cand, n_neg, ex, pos_label, neg_label, seed, into,
+                      want_sampled):
+        """batch_sample_pairs with the exclude lists already normalised: ex = (ptr, rows) or (None, None)
+        (a loop normalises its lists once)."""
+        pc = np.ascontiguousarray(pos_ctx, dtype=np.int32)
+        pd = np.ascontiguousarray(pos_cand, dtype=np.int32)
+        if not (pc.ndim == pd.ndim == 1 and len(pc) == len(pd)):
+            raise ValueError("pos_ctx and pos_cand must be flat and of one length")
+        n_neg = int(n_neg)
+        sampled = np.zeros(max(len(pc) * max(n_neg, 0), 1), dtype=np.int32) if want_sampled else None
+        b = into if into is not None else DeviceBatch(self, None)
+        h = b.handle if b.handle else C.c_void_p()
+        N.check(self._lib.fm_batch_sample_pairs(
+            self.handle, contexts.handle, candidates.handle, N.ptr(pc, C.c_int32), N.ptr(pd, C.c_int32), len(pc), n_neg,
+            None if ex[0] is None else N.ptr(ex[0], C.c_int64), None if ex[1] is None else N.ptr(ex[1], C.c_int32),
+            float(pos_label), float(neg_label), int(seed) & (2**64 - 1), C.byref(h),
+            N.ptr(sampled, C.c_int32) if want_sampled else None), "fm_batch_sample_pairs")
+        self._pair_batch(b, h, contexts, candidates)
+        return (b, sampled[: len(pc) * n_neg].reshape(len(pc), n_neg)) if want_sampled else b
+
+    def _pair_batch(self, b: DeviceBatch, h, contexts: DeviceBatch, candidates: DeviceBatch) -> DeviceBatch:
+        b.handle = h
+        b.n_rows = int(self._lib.fm_batch_rows(h))
+        b.nnz = int(self._lib.fm_batch_nnz(h))
+        b._data = (contexts, candidates)  # the sources stay alive while this batch's gather may be queued
+        return b
+
     @property
     def fuse_active(self) -> bool:
         """Whether prepared batches of this context take the fused step (fm_fuse_active)."""

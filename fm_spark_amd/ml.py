@@ -367,6 +367,8 @@ class FactorizationMachinesSGD:
         "parallel": None, "nGpus": 1, "devices": None, "transport": "auto", "wire": "fp32",
         # not in the reference: a held-out frame evaluated on the device during fit, (frame, every)
         "validationData": None,
+        # not in the reference: negatives drawn per positive by fitInteractions
+        "negativesPerPositive": 4,
     }
 
     def __init__(self, uid: str | None = None):
@@ -425,6 +427,13 @@ class FactorizationMachinesSGD:
             raise ValueError("every must be an integer >= 1")
         return self._set("validationData", (dataset, int(every)))
 
+    def setNegativesPerPositive(self, n: int):
+        """fitInteractions draws n negatives for every positive of a mini-batch (0 .. 1024; default 4)."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= 1024:
+            raise ValueError("negativesPerPositive must be an integer in [0, 1024]")
+        return self._set("negativesPerPositive", int(n))
+
+    def getNegativesPerPositive(self): return self._params["negativesPerPositive"]
     def getDimFactorization(self): return self._params["dimFactorization"]
     def getMaxIter(self): return self._params["maxIter"]
     def getMiniBatchFraction(self): return self._params["miniBatchFraction"]
@@ -544,6 +553,88 @@ class FactorizationMachinesSGD:
         if val_run is not None:
             model.validationHistory = val_run.history
             val_run.close()
+        return model
+
+
+    def fitInteractions(self, contexts: DataFrame, candidates: DataFrame, interactions: DataFrame, exclude=None,
+                        initial_tables=None) -> FactorizationMachinesModel:
+        """Fit on implicit feedback: `interactions` holds the integer columns ``context`` (row of
+        `contexts`) and ``candidate`` (row of `candidates`) -- rankPositions' names -- one row per
+        positive; both frames carry featuresCol, as recommend's.  A training row is a context row's
+        entries followed by a candidate row's, the row recommend and rankPositions score; positives are
+        labelled 1.0 and each gets negativesPerPositive negatives labelled 0.0, drawn on the device
+        uniformly over the candidate rows not on its context's ``exclude`` list (default: the context's
+        interacted rows).  Both frames go to the device once and every mini-batch is assembled there
+        (fm_batch_sample_pairs): with n interactions, m = max(1, round(miniBatchFraction * n)) and perm =
+        default_rng(seed).permutation(n), iteration t = 1 .. maxIter takes the positives
+        perm[((t - 1) * m + arange(m)) % n] in that order with the draw seed splitmix64(seed) ^ t, into
+        one of two batches in turn, sorted on the side stream while the previous iteration steps; the
+        steps only enqueue and the loss lines are written after the loop, as the pipelined fit's.
+        ``initial_tables`` = (ids, w, V) replaces the seeded draw over every id of either frame.  A
+        multi-GPU estimator (setParallel) and a set validationData raise ValueError: not built yet."""
+        p = self._params
+        if p["parallel"] is not None:
+            raise ValueError("fitInteractions runs on one GPU: a multi-GPU estimator (setParallel) is not supported yet")
+        if p["validationData"] is not None:
+            raise ValueError("fitInteractions does not evaluate validationData yet")
+        fcol = p["featuresCol"]
+        _check_schema(contexts, fcol, None)
+        _check_schema(candidates, fcol, None)
+        pairs = []
+        for name in ("context", "candidate"):
+            if name not in interactions.columns:
+                raise ValueError(f"Column {name} does not exist.")
+            vals = interactions[name]
+            if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in vals):
+                raise ValueError(f"Column {name} must hold integers")
+            pairs.append(np.asarray(vals, dtype=np.int64))
+        pos_ctx, pos_cand = pairs
+        n_ctx, n_cand, n = contexts.count(), candidates.count(), len(pos_ctx)
+        if n and not (0 <= pos_ctx.min() and pos_ctx.max() < n_ctx and 0 <= pos_cand.min() and pos_cand.max() < n_cand):
+            raise ValueError("interactions name a row outside contexts / candidates")
+        if exclude is None:
+            exclude = [np.unique(pos_cand[pos_ctx == u]) for u in range(n_ctx)]
+        ex = normalize_row_lists(exclude, n_ctx)
+        rows = [_explode(df[fcol]) for df in (contexts, candidates)]
+        k = p["dimFactorization"]
+        top = max([int(col.max()) + 1 for _, col, _ in rows if len(col)], default=1)
+        ctx = FMContext(p["numFeatures"] or top, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0)
+        bu, bc = (ctx.batch(N.CSRHost(rp, col, val, np.zeros(len(rp) - 1))) for rp, col, val in rows)
+        if initial_tables is not None:
+            ctx.load_tables(*initial_tables)
+        else:
+            ctx.init_from_batch(bu)  # createInitialModel's draw (:224-241) for every id of either frame
+            ctx.init_from_batch(bc)
+        from .data import splitmix64
+
+        n_iter, n_neg = p["maxIter"], p["negativesPerPositive"]
+        m = max(1, int(round(p["miniBatchFraction"] * n)))
+        perm = np.random.default_rng(p["seed"]).permutation(n)
+        seed0 = int(splitmix64(np.uint64(p["seed"] & (2**64 - 1))))
+        bufs = [None, None]
+
+        def sample(t):
+            take = perm[((t - 1) * m + np.arange(m)) % n]
+            bufs[t % 2] = ctx._sample_pairs(bu, bc, pos_ctx[take], pos_cand[take], n_neg, ex, 1.0, 0.0, seed0 ^ t,
+                                            bufs[t % 2], False)
+            bufs[t % 2].prepare()
+
+        e0 = ctx.epoch
+        work = list(range(n_iter)) if n else []
+        if work:
+            sample(1)
+        for t in range(1, len(work) + 1):
+            ctx.step_batch(bufs[t % 2], t, p["stepSize"], p["regParam"], sync=False)
+            if t < len(work):
+                sample(t + 1)  # drawn, gathered and sorted while step t runs (the batch step t - 1 read)
+        ctx.sync()
+        _log_losses(ctx, e0, work, n_iter, n_iter)
+        for b in (*bufs, bu, bc):
+            if b is not None:
+                b.close()
+        model = FactorizationMachinesModel(self.uid, k, 0.0, ctx=ctx)
+        model.setMinLabel(p["minLabel"]).setMaxLabel(p["maxLabel"])
+        model.parent = self
         return model
 
 

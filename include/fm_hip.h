@@ -175,7 +175,9 @@ int fm_sync(fm_ctx* ctx);
  * sets and n_top at the call, and kept; nor are the device copies of the lists of
  * fm_rank_candidates_select / fm_rank_batch_select, sized by U and the lists' total length; nor the
  * scratch of fm_rank_positions / fm_rank_positions_batch: the same row summaries, the device copies of
- * its target and exclude lists and its results, 12 bytes per target. */
+ * its target and exclude lists and its results, 12 bytes per target; nor the scratch of
+ * fm_batch_sample_pairs: the device copies of its lists, the drawn pairs with their labels, lengths and
+ * row_ptr (28 bytes per result row) and the scan's per-chunk sums, sized by the largest call. */
 int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz);
 
 /* ---- tables (C9: Strength / FactorizedInteraction, Model.scala:275-289) ------------ */
@@ -237,6 +239,61 @@ int fm_batch_prepare(fm_ctx* ctx, fm_batch* batch);
  * as fm_batch_create splits a host CSR; each rank gathers its share from its own copy of the
  * dataset (made on its device from the dataset's parts at the first selection). */
 int fm_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows, int64_t n, fm_batch** out);
+/* The mini-batch of n (context row, candidate row, label) triples of two device-resident datasets,
+ * built on the device: row i of the result holds the entries of row pair_ctx[i] of contexts, in their
+ * order, followed by the entries of row pair_cand[i] of candidates, with label[i] -- the row the
+ * ranking calls score (fm_rank_candidates), so a recommender trains on the rows it ranks.  Pairs come
+ * in any order and may repeat; either row may be empty; the two rows' ids are not checked to be
+ * disjoint (an id in both counts as two entries, the ranking calls' rule).  The result is the batch
+ * fm_batch_create makes of the host CSR of those concatenated rows -- the same device arrays bit for
+ * bit -- so every step, prediction and evaluation on it is that batch's.  contexts, candidates:
+ * batches of this context that fm_batch_from_rows accepts as data (their row_ptr is kept on the host;
+ * the result's row_ptr is computed there, on the pool of host threads); they may be the same batch.
+ * *out as fm_batch_from_rows': NULL creates a batch, otherwise *out (a batch of this context, neither
+ * source) is refilled in place, a split view detached first.  An index outside its dataset is
+ * FM_ERR_ARG ("pair_ctx ... out of [0, rows of contexts)", "pair_cand ... out of [0, rows of
+ * candidates)"); n < 2^31 and fewer than 2^31 result entries.  The lists are copied (pinned staging);
+ * the gather runs on the context's copy stream behind every queued step, preparation and sharded
+ * iteration that reads *out, and the host returns once it is enqueued, with no host wait but that for
+ * *out's own staging.  n = 0 gives an empty batch (its step is FM_NOTHING_TO_DO).  max_id is the
+ * larger of the sources'.  The table, the epoch and the histories are untouched.  A multi-GPU context
+ * refuses (FM_ERR_ARG: its batches are cut over its ranks). */
+int fm_batch_from_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates,
+                        const int32_t* pair_ctx, const int32_t* pair_cand, const double* label,
+                        int64_t n, fm_batch** out);
+/* The implicit-feedback mini-batch of n_pos positives with n_neg negatives each, drawn on the device:
+ * n_pos * (1 + n_neg) rows, row i * (1 + n_neg) the pair (pos_ctx[i], pos_cand[i]) with pos_label, row
+ * i * (1 + n_neg) + 1 + j the pair (pos_ctx[i], c_ij) with neg_label, built as fm_batch_from_pairs
+ * builds them.  c_ij is drawn uniformly over the candidate rows context u = pos_ctx[i] has not seen:
+ * all of [0, C) except its exclude list excl_rows[excl_ptr[u] .. excl_ptr[u + 1]) -- the lists of
+ * fm_rank_positions, under the rules of fm_rank_candidates_select's (strictly ascending, in [0, C);
+ * messages behind "exclude list: "); excl_ptr == NULL excludes nothing.  The draw is counter-based and
+ * part of the contract:
+ *   h = splitmix64(seed ^ splitmix64(((uint64)i << 20) | j))
+ *   r = ((h >> 32) * E) >> 32            E = C - (length of u's list), 64-bit arithmetic
+ *   c_ij = r + #{ t : excl[t] - t <= r }  the r-th eligible row in ascending order
+ * so the negatives depend on (seed, i, j), the context's list and C alone -- not on n_pos, the other
+ * positives or the launch.  Draws are independent: one positive's negatives may repeat, and a
+ * positive whose candidate row is not on its context's list may be drawn as its own negative (put
+ * what a context has seen on its list).  0 <= n_neg <= 1024; every context in pos_ctx needs E >= 1
+ * (FM_ERR_ARG, "... no eligible candidate row"); all of this is checked on the host before anything is
+ * enqueued, and a refused call changes nothing on the device and leaves *out as it was.  n_neg == 0:
+ * fm_batch_from_pairs' batch of the positives with a constant label, bit for bit.  sampled (may be
+ * NULL): n_pos * n_neg candidate rows, c_ij at [i * n_neg + j].
+ * One host wait: the drawn rows' lengths are known on the device alone and the step needs the entry
+ * count on the host, so the call reads that total back (8 bytes) and synchronises the copy stream
+ * (not the main or the side stream, as fm_shard_route synchronises the side stream alone).  The draw,
+ * the lengths, their scan and the read-back run in scratch of the context before *out is waited for
+ * or resized; only then is the gather enqueued behind the queued reads of *out -- so a loop that
+ * refills two batches in turn never waits for the step in flight.  2^31 or more result entries: FM_ERR_ARG after the
+ * read-back, *out untouched.  The lists' device copies, the drawn pairs and the scan's scratch belong
+ * to the context and grow to the largest call.  Otherwise as fm_batch_from_pairs (sources, *out,
+ * multi-GPU refusal, table untouched). */
+int fm_batch_sample_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates,
+                          const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
+                          const int64_t* excl_ptr, const int32_t* excl_rows,
+                          double pos_label, double neg_label, uint64_t seed,
+                          fm_batch** out, int32_t* sampled);
 /* A training dataset laid out split after split, made resident once: the rows of csr are the
  * randomSplit splits of the cached dfData concatenated in iteration order (FactorizationMachinesSGD
  * .scala:93, 111-112), split s = rows [split_rows[s], split_rows[s + 1]) (split_rows [n_splits + 1],
