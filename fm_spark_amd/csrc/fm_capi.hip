@@ -1091,80 +1091,63 @@ int fm_eval_history(fm_ctx* ctx, fm_eval_out* out, int64_t cap, int64_t* n) {
   });
 }
 
-// fm_rank_candidates / fm_rank_batch on one whole table: the two row sets' summaries, then the score
-// and merge passes over the contexts in tiles whose split lists fit the budget (fm_rank.hip).
-// sel: the per-context lists of the _select calls (checked by rank_select_check); FM_RANK_SELECT_ALL
-// takes the unrestricted score kernel.
-static int rank_impl(fm_ctx* ctx, const BatchDev& bu, const BatchDev& bc, int32_t n_top, double lo, double hi,
-                     int32_t* top_index, double* top_score, const RankSelect& sel = RankSelect{}) {
-  const int64_t U = bu.n_rows, Cn = bc.n_rows;
-  const int kp = ctx->kp;
-  RankWork& w = ctx->rank;
-  const size_t srow = sizeof(double) * (size_t)(kp + 2);
-  w.sum_u.ensure_slack(srow * U);
-  w.sum_c.ensure_slack(srow * Cn);
-  w.cnt_u.ensure_slack(sizeof(uint32_t) * U);
-  w.cnt_c.ensure_slack(sizeof(uint32_t) * Cn);
-  w.bias_u.ensure_slack(sizeof(double) * U);
-  w.bias_c.ensure_slack(sizeof(double) * Cn);
-  // FM_RANK_SELECT_ONLY cuts each context's list, not the candidates: the longest list sets the splits
-  const int splits = rank_splits(sel.mode == FM_RANK_SELECT_ONLY ? sel.longest : Cn, U);
-  const int64_t tile = std::min<int64_t>(U, rank_ctx_tile(splits, n_top));
-  w.lkey.ensure_slack(sizeof(uint64_t) * (size_t)(tile * splits * n_top));
-  w.lidx.ensure_slack(sizeof(uint32_t) * (size_t)(tile * splits * n_top));
-  w.out_idx.ensure_slack(sizeof(int32_t) * (size_t)(U * n_top));
-  w.out_score.ensure_slack(sizeof(double) * (size_t)(U * n_top));
-  hipStream_t st = ctx->stream;
-  if (sel.mode != FM_RANK_SELECT_ALL) {
-    const size_t n_sel = (size_t)sel.ptr[U];
-    w.sel_ptr.ensure_slack(sizeof(int64_t) * (size_t)(U + 1));
-    w.sel_rows.ensure_slack(sizeof(int32_t) * n_sel);
-    FM_HIP_CHECK(hipMemcpyAsync(w.sel_ptr.p, sel.ptr, sizeof(int64_t) * (size_t)(U + 1), hipMemcpyHostToDevice, st));
-    if (n_sel) FM_HIP_CHECK(hipMemcpyAsync(w.sel_rows.p, sel.rows, sizeof(int32_t) * n_sel, hipMemcpyHostToDevice, st));
-  }
-  const TableView T = ctx->view();
-  const double cumE = ctx->cum_host.back(), w0 = ctx->cfg.w0;
-  hipEvent_t e0 = ctx->prof_begin(st);
-  launch_summary(T, bu, cumE, w.sum_u.as<double>(), w.cnt_u.as<uint32_t>(), st);
-  launch_summary(T, bc, cumE, w.sum_c.as<double>(), w.cnt_c.as<uint32_t>(), st);
-  launch_rank_bias(w.sum_u.as<double>(), U, kp, w.bias_u.as<double>(), st);
-  launch_rank_bias(w.sum_c.as<double>(), Cn, kp, w.bias_c.as<double>(), st);
-  ctx->prof_end("rank_summary", e0, st);
-  for (int64_t u0 = 0; u0 < U; u0 += tile) {
-    const int64_t Ut = std::min<int64_t>(tile, U - u0);
-    e0 = ctx->prof_begin(st);
-    if (sel.mode == FM_RANK_SELECT_ALL)
-      launch_rank_score(w.sum_u.as<double>() + u0 * kp, w.bias_u.as<double>() + u0, w.cnt_u.as<uint32_t>() + u0, Ut,
-                        w.sum_c.as<double>(), w.bias_c.as<double>(), w.cnt_c.as<uint32_t>(), Cn, kp, splits, n_top, w0,
-                        w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), st);
-    else  // the tile's offsets: sel_ptr + u0 (they index the whole call's sel_rows)
-      launch_rank_score_select(sel.mode, w.sum_u.as<double>() + u0 * kp, w.bias_u.as<double>() + u0,
-                               w.cnt_u.as<uint32_t>() + u0, Ut, w.sum_c.as<double>(), w.bias_c.as<double>(),
-                               w.cnt_c.as<uint32_t>(), Cn, w.sel_ptr.as<int64_t>() + u0, w.sel_rows.as<int32_t>(), kp, splits,
-                               n_top, w0, w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), st);
-    ctx->prof_end("rank_score", e0, st);
-    e0 = ctx->prof_begin(st);
-    launch_rank_merge(w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), Ut, splits, n_top, w.cnt_u.as<uint32_t>() + u0,
-                      w.cnt_c.as<uint32_t>(), w0, lo, hi, w.out_idx.as<int32_t>() + u0 * n_top,
-                      w.out_score.as<double>() + u0 * n_top, st);
-    ctx->prof_end("rank_merge", e0, st);
-  }
-  FM_HIP_CHECK(hipMemcpyAsync(top_index, w.out_idx.p, sizeof(int32_t) * (size_t)(U * n_top), hipMemcpyDeviceToHost, st));
-  FM_HIP_CHECK(hipMemcpyAsync(top_score, w.out_score.p, sizeof(double) * (size_t)(U * n_top), hipMemcpyDeviceToHost, st));
-  FM_HIP_CHECK(hipStreamSynchronize(st));
-  return FM_OK;
+// ---- ranking (fm_rank_candidates / fm_rank_batch, their _select forms, fm_rank_positions[_batch]; fm_rank.hip) ----
+// a replicated group's replicas are identical: member 0 answers, with the group locked (as fm_loss_grad).
+// repeat(member 0): the same call on it.  (A template inside this file's extern "C" block takes C++ linkage by name.)
+extern "C++" template <class F>
+static int rank_on_member0(fm_ctx* ctx, F&& repeat) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(ctx->cfg.parallel == FM_PARALLEL_REPLICATED,
+               "fm_rank needs the whole table on one device (a replicated or single-table context): a row-sharded "
+               "table is not ranked yet");
+    return repeat(group_member0(ctx));
+  });
 }
 
-// the argument rules both entry points share, for U contexts and Cn candidates; false: nothing to do
-static bool rank_check(const fm_ctx* ctx, int64_t U, int64_t Cn, int32_t n_top, const int32_t* top_index,
-                       const double* top_score) {
+// The two row sets of a call, as host rows or as batches of the context.  rank_rows_check: what is refused
+// whatever else the call asks (call / host_call: the batch form's name and its host-row form's, for the
+// message), and the sets' sizes.  rank_rows_ready, behind the call's own checks: both sets on the device.
+struct RankRows {
+  const BatchDev& u;
+  const BatchDev& c;
+};
+static std::pair<int64_t, int64_t> rank_rows_check(const fm_ctx*, const fm_csr* contexts, const fm_csr* candidates, const char*,
+                                                   const char*) {
+  FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
+  return {contexts->n_rows, candidates->n_rows};
+}
+static std::pair<int64_t, int64_t> rank_rows_check(const fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates,
+                                                   const char* call, const char* host_call) {
+  FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
+  FM_REQUIRE(contexts->owner == ctx && candidates->owner == ctx, "batch belongs to another context");
+  FM_REQUIRE(!ctx->group && !contexts->grp && !candidates->grp,
+             std::string(call) + " needs both row sets whole on one device: a multi-GPU context's batches are cut over its "
+                                 "ranks (" + host_call + " takes host rows)");
+  FM_REQUIRE(contexts->split_rows.empty() && candidates->split_rows.empty(),
+             "a dataset made by fm_batch_create_splits is ranked through its split views");
+  return {contexts->dev.n_rows, candidates->dev.n_rows};
+}
+static RankRows rank_rows_ready(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates) {
+  fm_batch* bu = host_batch(ctx);
+  if (!ctx->host_batch2) ctx->host_batch2.reset(new fm_batch());
+  fm_batch* bc = ctx->host_batch2.get();
+  upload_batch(ctx, contexts, bu, false);
+  upload_batch(ctx, candidates, bc, false);
+  return {bu->dev, bc->dev};
+}
+static RankRows rank_rows_ready(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates) {
+  wait_built(contexts, ctx->stream);
+  wait_built(candidates, ctx->stream);
+  return {contexts->dev, candidates->dev};
+}
+
+// the argument rules every ranking call shares, for U contexts and Cn candidates; false: nothing to do
+static bool rank_common_check(const fm_ctx* ctx, int64_t U, int64_t Cn) {
   FM_REQUIRE(ctx->cfg.shard_count == 1,
              "fm_rank needs the whole table on one device (shard_count == 1): a row-sharded table is not ranked yet");
   if (U == 0) return false;
   FM_REQUIRE(Cn >= 1, "fm_rank needs at least one candidate row");
   FM_REQUIRE(Cn < (int64_t(1) << 31), "fm_rank takes fewer than 2^31 candidate rows");
-  FM_REQUIRE(n_top >= 1 && n_top <= FM_RANK_MAX_TOP && n_top <= Cn, "n_top must be in [1, min(candidate rows, FM_RANK_MAX_TOP)]");
-  FM_REQUIRE(top_index != nullptr && top_score != nullptr, "null argument");
   return true;
 }
 
@@ -1217,148 +1200,21 @@ static int64_t rank_list_check(const std::string& what, const std::string& pname
   return longest;
 }
 
-// The list rules of the _select calls for U contexts and Cn candidates (rank_list_check); fills sel
-// (the longest list with it).
-static void rank_select_check(int32_t select, const int64_t* sel_ptr, const int32_t* sel_rows, int64_t U, int64_t Cn,
-                              RankSelect& sel) {
-  FM_REQUIRE(select == FM_RANK_SELECT_ALL || select == FM_RANK_SELECT_ONLY || select == FM_RANK_SELECT_EXCEPT,
-             "select must be FM_RANK_SELECT_ALL, _ONLY or _EXCEPT, got " + std::to_string(select));
-  sel = RankSelect{};
-  if (select == FM_RANK_SELECT_ALL) return;
-  FM_REQUIRE(sel_ptr != nullptr, "null sel_ptr with FM_RANK_SELECT_ONLY / _EXCEPT");
-  sel.longest = rank_list_check("", "sel_ptr", "sel_rows", sel_ptr, sel_rows, U, Cn);
-  sel.mode = select;
-  sel.ptr = sel_ptr;
-  sel.rows = sel_rows;
+// a checked list pair -> its device copy (offsets [U + 1], rows)
+static void upload_lists(DevBuf& ptr, DevBuf& rows, const int64_t* host_ptr, const int32_t* host_rows, int64_t U,
+                         hipStream_t st) {
+  const size_t n = (size_t)host_ptr[U];
+  ptr.ensure_slack(sizeof(int64_t) * (size_t)(U + 1));
+  rows.ensure_slack(sizeof(int32_t) * n);
+  FM_HIP_CHECK(hipMemcpyAsync(ptr.p, host_ptr, sizeof(int64_t) * (size_t)(U + 1), hipMemcpyHostToDevice, st));
+  if (n) FM_HIP_CHECK(hipMemcpyAsync(rows.p, host_rows, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
 }
 
-int fm_rank_candidates_select(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, int32_t select,
-                              const int64_t* sel_ptr, const int32_t* sel_rows, int32_t n_top, double lo, double hi,
-                              int32_t* top_index, double* top_score) {
-  if (ctx && ctx->group) {
-    // a replicated group's replicas are identical: member 0 answers, with the group locked (as fm_loss_grad)
-    return guarded(ctx, [&]() -> int {
-      FM_REQUIRE(ctx->cfg.parallel == FM_PARALLEL_REPLICATED,
-                 "fm_rank needs the whole table on one device (a replicated or single-table context): a row-sharded "
-                 "table is not ranked yet");
-      return fm_rank_candidates_select(group_member0(ctx), contexts, candidates, select, sel_ptr, sel_rows, n_top, lo, hi,
-                                       top_index, top_score);
-    });
-  }
-  return guarded(ctx, [&]() -> int {
-    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
-    if (!rank_check(ctx, contexts->n_rows, candidates->n_rows, n_top, top_index, top_score)) return FM_OK;
-    RankSelect sel;
-    rank_select_check(select, sel_ptr, sel_rows, contexts->n_rows, candidates->n_rows, sel);
-    fm_batch* bu = host_batch(ctx);
-    if (!ctx->host_batch2) ctx->host_batch2.reset(new fm_batch());
-    fm_batch* bc = ctx->host_batch2.get();
-    upload_batch(ctx, contexts, bu, false);
-    upload_batch(ctx, candidates, bc, false);
-    return rank_impl(ctx, bu->dev, bc->dev, n_top, lo, hi, top_index, top_score, sel);
-  });
-}
-
-int fm_rank_batch_select(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t select, const int64_t* sel_ptr,
-                         const int32_t* sel_rows, int32_t n_top, double lo, double hi, int32_t* top_index,
-                         double* top_score) {
-  return guarded(ctx, [&]() -> int {
-    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
-    FM_REQUIRE(contexts->owner == ctx && candidates->owner == ctx, "batch belongs to another context");
-    FM_REQUIRE(!ctx->group && !contexts->grp && !candidates->grp,
-               "fm_rank_batch needs both row sets whole on one device: a multi-GPU context's batches are cut over its "
-               "ranks (fm_rank_candidates takes host rows)");
-    FM_REQUIRE(contexts->split_rows.empty() && candidates->split_rows.empty(),
-               "a dataset made by fm_batch_create_splits is ranked through its split views");
-    if (!rank_check(ctx, contexts->dev.n_rows, candidates->dev.n_rows, n_top, top_index, top_score)) return FM_OK;
-    RankSelect sel;
-    rank_select_check(select, sel_ptr, sel_rows, contexts->dev.n_rows, candidates->dev.n_rows, sel);
-    wait_built(contexts, ctx->stream);
-    wait_built(candidates, ctx->stream);
-    return rank_impl(ctx, contexts->dev, candidates->dev, n_top, lo, hi, top_index, top_score, sel);
-  });
-}
-
-int fm_rank_candidates(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, int32_t n_top, double lo, double hi,
-                       int32_t* top_index, double* top_score) {
-  if (ctx && ctx->group) {
-    // a replicated group's replicas are identical: member 0 answers, with the group locked (as fm_loss_grad)
-    return guarded(ctx, [&]() -> int {
-      FM_REQUIRE(ctx->cfg.parallel == FM_PARALLEL_REPLICATED,
-                 "fm_rank needs the whole table on one device (a replicated or single-table context): a row-sharded "
-                 "table is not ranked yet");
-      return fm_rank_candidates(group_member0(ctx), contexts, candidates, n_top, lo, hi, top_index, top_score);
-    });
-  }
-  return guarded(ctx, [&]() -> int {
-    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
-    if (!rank_check(ctx, contexts->n_rows, candidates->n_rows, n_top, top_index, top_score)) return FM_OK;
-    fm_batch* bu = host_batch(ctx);
-    if (!ctx->host_batch2) ctx->host_batch2.reset(new fm_batch());
-    fm_batch* bc = ctx->host_batch2.get();
-    upload_batch(ctx, contexts, bu, false);
-    upload_batch(ctx, candidates, bc, false);
-    return rank_impl(ctx, bu->dev, bc->dev, n_top, lo, hi, top_index, top_score);
-  });
-}
-
-int fm_rank_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t n_top, double lo, double hi,
-                  int32_t* top_index, double* top_score) {
-  return guarded(ctx, [&]() -> int {
-    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
-    FM_REQUIRE(contexts->owner == ctx && candidates->owner == ctx, "batch belongs to another context");
-    FM_REQUIRE(!ctx->group && !contexts->grp && !candidates->grp,
-               "fm_rank_batch needs both row sets whole on one device: a multi-GPU context's batches are cut over its "
-               "ranks (fm_rank_candidates takes host rows)");
-    FM_REQUIRE(contexts->split_rows.empty() && candidates->split_rows.empty(),
-               "a dataset made by fm_batch_create_splits is ranked through its split views");
-    if (!rank_check(ctx, contexts->dev.n_rows, candidates->dev.n_rows, n_top, top_index, top_score)) return FM_OK;
-    wait_built(contexts, ctx->stream);
-    wait_built(candidates, ctx->stream);
-    return rank_impl(ctx, contexts->dev, candidates->dev, n_top, lo, hi, top_index, top_score);
-  });
-}
-
-// fm_rank_positions / fm_rank_positions_batch: the lists of a call, checked (rank_positions_check)
-struct RankTargets {
-  const int64_t* tgt_ptr = nullptr;
-  const int32_t* tgt_rows = nullptr;
-  const int64_t* ex_ptr = nullptr;  // null: nothing excluded
-  const int32_t* ex_rows = nullptr;
-  int64_t longest = 0;  // the longest target list
-};
-
-// the argument rules both entry points share, as rank_check's; false: nothing to do
-static bool rank_positions_check(const fm_ctx* ctx, int64_t U, int64_t Cn, const int64_t* tgt_ptr, const int32_t* tgt_rows,
-                                 const int64_t* excl_ptr, const int32_t* excl_rows, const int32_t* position,
-                                 const double* score, RankTargets& t) {
-  FM_REQUIRE(ctx->cfg.shard_count == 1,
-             "fm_rank needs the whole table on one device (shard_count == 1): a row-sharded table is not ranked yet");
-  if (U == 0) return false;
-  FM_REQUIRE(Cn >= 1, "fm_rank needs at least one candidate row");
-  FM_REQUIRE(Cn < (int64_t(1) << 31), "fm_rank takes fewer than 2^31 candidate rows");
-  FM_REQUIRE(position != nullptr && score != nullptr, "null argument");
-  FM_REQUIRE(tgt_ptr != nullptr, "null tgt_ptr: fm_rank_positions needs the target lists");
-  t = RankTargets{};
-  t.longest = rank_list_check("target list: ", "tgt_ptr", "tgt_rows", tgt_ptr, tgt_rows, U, Cn);
-  if (excl_ptr) {
-    rank_list_check("exclude list: ", "excl_ptr", "excl_rows", excl_ptr, excl_rows, U, Cn);
-    t.ex_ptr = excl_ptr;
-    t.ex_rows = excl_rows;
-  }
-  t.tgt_ptr = tgt_ptr;
-  t.tgt_rows = tgt_rows;
-  return tgt_ptr[U] != 0;
-}
-
-// On one whole table: the two row sets' summaries as rank_impl takes them, then the counting pass over
-// the contexts, a launch per rank_position_ctx_tile() of them (fm_rank.hip).  No scratch but the lists'
-// copies and the results: the splits add their counts onto the zeroed positions.
-static int rank_positions_impl(fm_ctx* ctx, const BatchDev& bu, const BatchDev& bc, const RankTargets& t, double lo, double hi,
-                               int32_t* position, double* score) {
+// The stage every ranking call opens with: both row sets' summaries and biases into the context's scratch
+// (one profile entry), as the views the score and position launchers take.
+static std::pair<RankSide, RankSide> rank_summaries(fm_ctx* ctx, const BatchDev& bu, const BatchDev& bc) {
   const int64_t U = bu.n_rows, Cn = bc.n_rows;
   const int kp = ctx->kp;
-  const size_t n_tgt = (size_t)t.tgt_ptr[U];
   RankWork& w = ctx->rank;
   const size_t srow = sizeof(double) * (size_t)(kp + 2);
   w.sum_u.ensure_slack(srow * U);
@@ -1367,40 +1223,133 @@ static int rank_positions_impl(fm_ctx* ctx, const BatchDev& bu, const BatchDev& 
   w.cnt_c.ensure_slack(sizeof(uint32_t) * Cn);
   w.bias_u.ensure_slack(sizeof(double) * U);
   w.bias_c.ensure_slack(sizeof(double) * Cn);
-  w.tgt_ptr.ensure_slack(sizeof(int64_t) * (size_t)(U + 1));
-  w.tgt_rows.ensure_slack(sizeof(int32_t) * n_tgt);
-  w.position.ensure_slack(sizeof(int32_t) * n_tgt);
-  w.pos_score.ensure_slack(sizeof(double) * n_tgt);
-  hipStream_t st = ctx->stream;
-  FM_HIP_CHECK(hipMemcpyAsync(w.tgt_ptr.p, t.tgt_ptr, sizeof(int64_t) * (size_t)(U + 1), hipMemcpyHostToDevice, st));
-  FM_HIP_CHECK(hipMemcpyAsync(w.tgt_rows.p, t.tgt_rows, sizeof(int32_t) * n_tgt, hipMemcpyHostToDevice, st));
-  if (t.ex_ptr) {
-    const size_t n_ex = (size_t)t.ex_ptr[U];
-    w.sel_ptr.ensure_slack(sizeof(int64_t) * (size_t)(U + 1));
-    w.sel_rows.ensure_slack(sizeof(int32_t) * n_ex);
-    FM_HIP_CHECK(hipMemcpyAsync(w.sel_ptr.p, t.ex_ptr, sizeof(int64_t) * (size_t)(U + 1), hipMemcpyHostToDevice, st));
-    if (n_ex) FM_HIP_CHECK(hipMemcpyAsync(w.sel_rows.p, t.ex_rows, sizeof(int32_t) * n_ex, hipMemcpyHostToDevice, st));
-  }
-  FM_HIP_CHECK(hipMemsetAsync(w.position.p, 0, sizeof(int32_t) * n_tgt, st));
   const TableView T = ctx->view();
-  const double cumE = ctx->cum_host.back(), w0 = ctx->cfg.w0;
+  const double cumE = ctx->cum_host.back();
+  hipStream_t st = ctx->stream;
   hipEvent_t e0 = ctx->prof_begin(st);
   launch_summary(T, bu, cumE, w.sum_u.as<double>(), w.cnt_u.as<uint32_t>(), st);
   launch_summary(T, bc, cumE, w.sum_c.as<double>(), w.cnt_c.as<uint32_t>(), st);
   launch_rank_bias(w.sum_u.as<double>(), U, kp, w.bias_u.as<double>(), st);
   launch_rank_bias(w.sum_c.as<double>(), Cn, kp, w.bias_c.as<double>(), st);
   ctx->prof_end("rank_summary", e0, st);
+  return {RankSide{w.sum_u.as<double>(), w.bias_u.as<double>(), w.cnt_u.as<uint32_t>(), U},
+          RankSide{w.sum_c.as<double>(), w.bias_c.as<double>(), w.cnt_c.as<uint32_t>(), Cn}};
+}
+
+// Top-N on one whole table: the lists' copy and the summaries, then the score and merge passes over the
+// contexts in tiles whose split lists fit the budget (fm_rank.hip).  select / sel: the mode and lists of the
+// _select calls (checked by rank_call); FM_RANK_SELECT_ALL reads no list.
+static int rank_impl(fm_ctx* ctx, const RankRows& rows, int32_t n_top, double lo, double hi, int32_t* top_index,
+                     double* top_score, int32_t select, const RankList& sel) {
+  const int64_t U = rows.u.n_rows, Cn = rows.c.n_rows;
+  const int kp = ctx->kp;
+  const double w0 = ctx->cfg.w0;
+  RankWork& w = ctx->rank;
+  hipStream_t st = ctx->stream;
+  // FM_RANK_SELECT_ONLY cuts each context's list, not the candidates: the longest list sets the splits
+  const int splits = rank_splits(select == FM_RANK_SELECT_ONLY ? sel.longest : Cn, U);
+  const int64_t tile = std::min<int64_t>(U, rank_ctx_tile(splits, n_top));
+  w.lkey.ensure_slack(sizeof(uint64_t) * (size_t)(tile * splits * n_top));
+  w.lidx.ensure_slack(sizeof(uint32_t) * (size_t)(tile * splits * n_top));
+  w.out_idx.ensure_slack(sizeof(int32_t) * (size_t)(U * n_top));
+  w.out_score.ensure_slack(sizeof(double) * (size_t)(U * n_top));
+  if (sel.ptr) upload_lists(w.sel_ptr, w.sel_rows, sel.ptr, sel.rows, U, st);
+  const auto [su, sc] = rank_summaries(ctx, rows.u, rows.c);
+  for (int64_t u0 = 0; u0 < U; u0 += tile) {
+    const int64_t Ut = std::min<int64_t>(tile, U - u0);
+    hipEvent_t e0 = ctx->prof_begin(st);
+    // the tile's offsets: sel_ptr + u0 (they index the whole call's sel_rows)
+    launch_rank_score(select, su.tile(u0, Ut, kp), sc, sel.ptr ? w.sel_ptr.as<int64_t>() + u0 : nullptr,
+                      w.sel_rows.as<int32_t>(), kp, splits, n_top, w0, w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), st);
+    ctx->prof_end("rank_score", e0, st);
+    e0 = ctx->prof_begin(st);
+    launch_rank_merge(w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), Ut, splits, n_top, su.cnt + u0, sc.cnt, w0, lo, hi,
+                      w.out_idx.as<int32_t>() + u0 * n_top, w.out_score.as<double>() + u0 * n_top, st);
+    ctx->prof_end("rank_merge", e0, st);
+  }
+  FM_HIP_CHECK(hipMemcpyAsync(top_index, w.out_idx.p, sizeof(int32_t) * (size_t)(U * n_top), hipMemcpyDeviceToHost, st));
+  FM_HIP_CHECK(hipMemcpyAsync(top_score, w.out_score.p, sizeof(double) * (size_t)(U * n_top), hipMemcpyDeviceToHost, st));
+  FM_HIP_CHECK(hipStreamSynchronize(st));
+  return FM_OK;
+}
+
+// The four top-N entry points over either kind of row set: the shared rules, the top-N rules, the list
+// rules of the _select forms (rank_list_check; FM_RANK_SELECT_ALL takes no list), then the work.
+extern "C++" template <class Rows>
+static int rank_call(fm_ctx* ctx, const Rows* contexts, const Rows* candidates, const char* call, const char* host_call,
+                     int32_t select, const int64_t* sel_ptr, const int32_t* sel_rows, int32_t n_top, double lo, double hi,
+                     int32_t* top_index, double* top_score) {
+  return guarded(ctx, [&]() -> int {
+    const auto [U, Cn] = rank_rows_check(ctx, contexts, candidates, call, host_call);
+    if (!rank_common_check(ctx, U, Cn)) return FM_OK;
+    FM_REQUIRE(n_top >= 1 && n_top <= FM_RANK_MAX_TOP && n_top <= Cn, "n_top must be in [1, min(candidate rows, FM_RANK_MAX_TOP)]");
+    FM_REQUIRE(top_index != nullptr && top_score != nullptr, "null argument");
+    FM_REQUIRE(select == FM_RANK_SELECT_ALL || select == FM_RANK_SELECT_ONLY || select == FM_RANK_SELECT_EXCEPT,
+               "select must be FM_RANK_SELECT_ALL, _ONLY or _EXCEPT, got " + std::to_string(select));
+    RankList sel;
+    if (select != FM_RANK_SELECT_ALL) {
+      FM_REQUIRE(sel_ptr != nullptr, "null sel_ptr with FM_RANK_SELECT_ONLY / _EXCEPT");
+      sel = {sel_ptr, sel_rows, rank_list_check("", "sel_ptr", "sel_rows", sel_ptr, sel_rows, U, Cn)};
+    }
+    return rank_impl(ctx, rank_rows_ready(ctx, contexts, candidates), n_top, lo, hi, top_index, top_score, select, sel);
+  });
+}
+
+int fm_rank_candidates_select(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, int32_t select,
+                              const int64_t* sel_ptr, const int32_t* sel_rows, int32_t n_top, double lo, double hi,
+                              int32_t* top_index, double* top_score) {
+  if (ctx && ctx->group)
+    return rank_on_member0(ctx, [&](fm_ctx* m) {
+      return fm_rank_candidates_select(m, contexts, candidates, select, sel_ptr, sel_rows, n_top, lo, hi, top_index, top_score);
+    });
+  return rank_call(ctx, contexts, candidates, "", "", select, sel_ptr, sel_rows, n_top, lo, hi, top_index, top_score);
+}
+
+int fm_rank_batch_select(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t select, const int64_t* sel_ptr,
+                         const int32_t* sel_rows, int32_t n_top, double lo, double hi, int32_t* top_index,
+                         double* top_score) {
+  return rank_call<fm_batch>(ctx, contexts, candidates, "fm_rank_batch", "fm_rank_candidates", select, sel_ptr, sel_rows, n_top,
+                             lo, hi, top_index, top_score);
+}
+
+int fm_rank_candidates(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, int32_t n_top, double lo, double hi,
+                       int32_t* top_index, double* top_score) {
+  return fm_rank_candidates_select(ctx, contexts, candidates, FM_RANK_SELECT_ALL, nullptr, nullptr, n_top, lo, hi, top_index,
+                                   top_score);
+}
+
+int fm_rank_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t n_top, double lo, double hi,
+                  int32_t* top_index, double* top_score) {
+  return fm_rank_batch_select(ctx, contexts, candidates, FM_RANK_SELECT_ALL, nullptr, nullptr, n_top, lo, hi, top_index,
+                              top_score);
+}
+
+// Exact positions on one whole table: the lists' copies and the summaries as rank_impl's, then the counting
+// pass over the contexts, a launch per rank_position_ctx_tile() of them (fm_rank.hip).  No scratch but the
+// lists' copies and the results: the splits add their counts onto the zeroed positions.  ex.ptr null:
+// nothing excluded.
+static int rank_positions_impl(fm_ctx* ctx, const RankRows& rows, const RankList& tgt, const RankList& ex, double lo, double hi,
+                               int32_t* position, double* score) {
+  const int64_t U = rows.u.n_rows, Cn = rows.c.n_rows;
+  const int kp = ctx->kp;
+  const size_t n_tgt = (size_t)tgt.ptr[U];
+  RankWork& w = ctx->rank;
+  hipStream_t st = ctx->stream;
+  w.position.ensure_slack(sizeof(int32_t) * n_tgt);
+  w.pos_score.ensure_slack(sizeof(double) * n_tgt);
+  upload_lists(w.tgt_ptr, w.tgt_rows, tgt.ptr, tgt.rows, U, st);
+  if (ex.ptr) upload_lists(w.sel_ptr, w.sel_rows, ex.ptr, ex.rows, U, st);
+  FM_HIP_CHECK(hipMemsetAsync(w.position.p, 0, sizeof(int32_t) * n_tgt, st));
+  const auto [su, sc] = rank_summaries(ctx, rows.u, rows.c);
   const int splits = rank_splits(Cn, U);
   const int64_t tile = rank_position_ctx_tile();
   for (int64_t u0 = 0; u0 < U; u0 += tile) {
     const int64_t Ut = std::min<int64_t>(tile, U - u0);
-    e0 = ctx->prof_begin(st);
+    hipEvent_t e0 = ctx->prof_begin(st);
     // the tile's offsets: tgt_ptr + u0, sel_ptr + u0 (they index the whole call's rows and results)
-    launch_rank_position(w.sum_u.as<double>() + u0 * kp, w.bias_u.as<double>() + u0, w.cnt_u.as<uint32_t>() + u0, Ut,
-                         w.sum_c.as<double>(), w.bias_c.as<double>(), w.cnt_c.as<uint32_t>(), Cn, w.tgt_ptr.as<int64_t>() + u0,
-                         w.tgt_rows.as<int32_t>(), t.longest, t.ex_ptr ? w.sel_ptr.as<int64_t>() + u0 : nullptr,
-                         w.sel_rows.as<int32_t>(), kp, splits, w0, lo, hi, w.position.as<int32_t>(),
-                         w.pos_score.as<double>(), st);
+    launch_rank_position(su.tile(u0, Ut, kp), sc, w.tgt_ptr.as<int64_t>() + u0, w.tgt_rows.as<int32_t>(), tgt.longest,
+                         ex.ptr ? w.sel_ptr.as<int64_t>() + u0 : nullptr, w.sel_rows.as<int32_t>(), kp, splits, ctx->cfg.w0, lo,
+                         hi, w.position.as<int32_t>(), w.pos_score.as<double>(), st);
     ctx->prof_end("rank_position", e0, st);
   }
   FM_HIP_CHECK(hipMemcpyAsync(position, w.position.p, sizeof(int32_t) * n_tgt, hipMemcpyDeviceToHost, st));
@@ -1409,53 +1358,39 @@ static int rank_positions_impl(fm_ctx* ctx, const BatchDev& bu, const BatchDev& 
   return FM_OK;
 }
 
+// the two positions entry points over either kind of row set, as rank_call
+extern "C++" template <class Rows>
+static int rank_positions_call(fm_ctx* ctx, const Rows* contexts, const Rows* candidates, const char* call,
+                               const char* host_call, const int64_t* tgt_ptr, const int32_t* tgt_rows, const int64_t* excl_ptr,
+                               const int32_t* excl_rows, double lo, double hi, int32_t* position, double* score) {
+  return guarded(ctx, [&]() -> int {
+    const auto [U, Cn] = rank_rows_check(ctx, contexts, candidates, call, host_call);
+    if (!rank_common_check(ctx, U, Cn)) return FM_OK;
+    FM_REQUIRE(position != nullptr && score != nullptr, "null argument");
+    FM_REQUIRE(tgt_ptr != nullptr, "null tgt_ptr: fm_rank_positions needs the target lists");
+    const RankList tgt = {tgt_ptr, tgt_rows, rank_list_check("target list: ", "tgt_ptr", "tgt_rows", tgt_ptr, tgt_rows, U, Cn)};
+    RankList ex;
+    if (excl_ptr) ex = {excl_ptr, excl_rows, rank_list_check("exclude list: ", "excl_ptr", "excl_rows", excl_ptr, excl_rows, U, Cn)};
+    if (tgt_ptr[U] == 0) return FM_OK;
+    return rank_positions_impl(ctx, rank_rows_ready(ctx, contexts, candidates), tgt, ex, lo, hi, position, score);
+  });
+}
+
 int fm_rank_positions(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, const int64_t* tgt_ptr,
                       const int32_t* tgt_rows, const int64_t* excl_ptr, const int32_t* excl_rows, double lo, double hi,
                       int32_t* position, double* score) {
-  if (ctx && ctx->group) {
-    // a replicated group's replicas are identical: member 0 answers, with the group locked (as fm_loss_grad)
-    return guarded(ctx, [&]() -> int {
-      FM_REQUIRE(ctx->cfg.parallel == FM_PARALLEL_REPLICATED,
-                 "fm_rank needs the whole table on one device (a replicated or single-table context): a row-sharded "
-                 "table is not ranked yet");
-      return fm_rank_positions(group_member0(ctx), contexts, candidates, tgt_ptr, tgt_rows, excl_ptr, excl_rows, lo, hi,
-                               position, score);
+  if (ctx && ctx->group)
+    return rank_on_member0(ctx, [&](fm_ctx* m) {
+      return fm_rank_positions(m, contexts, candidates, tgt_ptr, tgt_rows, excl_ptr, excl_rows, lo, hi, position, score);
     });
-  }
-  return guarded(ctx, [&]() -> int {
-    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
-    RankTargets t;
-    if (!rank_positions_check(ctx, contexts->n_rows, candidates->n_rows, tgt_ptr, tgt_rows, excl_ptr, excl_rows, position,
-                              score, t))
-      return FM_OK;
-    fm_batch* bu = host_batch(ctx);
-    if (!ctx->host_batch2) ctx->host_batch2.reset(new fm_batch());
-    fm_batch* bc = ctx->host_batch2.get();
-    upload_batch(ctx, contexts, bu, false);
-    upload_batch(ctx, candidates, bc, false);
-    return rank_positions_impl(ctx, bu->dev, bc->dev, t, lo, hi, position, score);
-  });
+  return rank_positions_call(ctx, contexts, candidates, "", "", tgt_ptr, tgt_rows, excl_ptr, excl_rows, lo, hi, position, score);
 }
 
 int fm_rank_positions_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, const int64_t* tgt_ptr,
                             const int32_t* tgt_rows, const int64_t* excl_ptr, const int32_t* excl_rows, double lo, double hi,
                             int32_t* position, double* score) {
-  return guarded(ctx, [&]() -> int {
-    FM_REQUIRE(contexts != nullptr && candidates != nullptr, "null argument");
-    FM_REQUIRE(contexts->owner == ctx && candidates->owner == ctx, "batch belongs to another context");
-    FM_REQUIRE(!ctx->group && !contexts->grp && !candidates->grp,
-               "fm_rank_positions_batch needs both row sets whole on one device: a multi-GPU context's batches are cut "
-               "over its ranks (fm_rank_positions takes host rows)");
-    FM_REQUIRE(contexts->split_rows.empty() && candidates->split_rows.empty(),
-               "a dataset made by fm_batch_create_splits is ranked through its split views");
-    RankTargets t;
-    if (!rank_positions_check(ctx, contexts->dev.n_rows, candidates->dev.n_rows, tgt_ptr, tgt_rows, excl_ptr, excl_rows,
-                              position, score, t))
-      return FM_OK;
-    wait_built(contexts, ctx->stream);
-    wait_built(candidates, ctx->stream);
-    return rank_positions_impl(ctx, contexts->dev, candidates->dev, t, lo, hi, position, score);
-  });
+  return rank_positions_call<fm_batch>(ctx, contexts, candidates, "fm_rank_positions_batch", "fm_rank_positions", tgt_ptr,
+                                       tgt_rows, excl_ptr, excl_rows, lo, hi, position, score);
 }
 
 // ---- pair batches (fm_batch_from_pairs / fm_batch_sample_pairs; fm_pairs.hip) ----

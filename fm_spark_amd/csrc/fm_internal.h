@@ -385,12 +385,21 @@ struct RankWork {
   DevBuf tgt_ptr, tgt_rows;   // fm_rank_positions: the target lists, laid out as sel_ptr / sel_rows
   DevBuf position, pos_score;  // ... and its results, int32 / double per target
 };
-// a call's per-context row lists (host arrays, validated): mode FM_RANK_SELECT_*, ptr[U + 1], rows[ptr[U]]
-struct RankSelect {
-  int32_t mode = FM_RANK_SELECT_ALL;
+// a call's per-context row lists (host arrays, validated): ptr[U + 1], rows[ptr[U]]; ptr null: no list
+struct RankList {
   const int64_t* ptr = nullptr;
   const int32_t* rows = nullptr;
   int64_t longest = 0;  // the longest list of the call
+};
+// one row set's per-row arrays on the device: the summaries (FwdOut::summary's layout), a_r and the
+// learned entries of n rows
+struct RankSide {
+  const double* sum;
+  const double* bias;
+  const uint32_t* cnt;
+  int64_t n;
+  // rows [r0, r0 + nt) of it: a context tile
+  RankSide tile(int64_t r0, int64_t nt, int kp) const { return {sum + r0 * kp, bias + r0, cnt + r0, nt}; }
 };
 // candidate splits of a call of U contexts (whole chunks each; fewer as the contexts alone fill the
 // chip) and the contexts one pass of the score kernel takes (the list budget)
@@ -398,36 +407,30 @@ int rank_splits(int64_t C, int64_t U);
 int64_t rank_ctx_tile(int splits, int n_top);
 // a_r for n rows of a summary buffer
 void launch_rank_bias(const double* summary, int64_t n, int kp, double* bias, hipStream_t st);
-// contexts [0, Ut) of the given arrays against all C candidates: per (context, split) the split's
-// best n_top in order into lkey / lidx [Ut][splits][n_top]
-void launch_rank_score(const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut,
-                       const double* sum_c, const double* bias_c, const uint32_t* cnt_c, int64_t C, int kp, int splits,
-                       int n_top, double w0, uint64_t* lkey, uint32_t* lidx, hipStream_t st);
-// the same under per-context lists (device: sel_ptr[Ut + 1] of this tile, offsets into sel_rows; rows in
-// [0, C), strictly ascending per list).  FM_RANK_SELECT_EXCEPT: a listed row enters as padding, splits as
-// above.  FM_RANK_SELECT_ONLY: the splits (rank_splits of the call's longest list) cut each context's
-// list; a split without a chunk writes n_top padding entries.
-void launch_rank_score_select(int select, const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut,
-                              const double* sum_c, const double* bias_c, const uint32_t* cnt_c, int64_t C,
-                              const int64_t* sel_ptr, const int32_t* sel_rows, int kp, int splits, int n_top, double w0,
-                              uint64_t* lkey, uint32_t* lidx, hipStream_t st);
+// the contexts u (a tile) against all candidates c: per (context, split) the split's best n_top in order
+// into lkey / lidx [u.n][splits][n_top].  select FM_RANK_SELECT_ALL: every candidate, the lists not read.
+// Else under per-context lists (device: sel_ptr[u.n + 1] of this tile, offsets into sel_rows; rows in
+// [0, c.n), strictly ascending per list).  FM_RANK_SELECT_EXCEPT: a listed row enters as padding, the
+// splits cut the candidates as without lists.  FM_RANK_SELECT_ONLY: the splits (rank_splits of the call's
+// longest list) cut each context's list; a split without a chunk writes n_top padding entries.
+void launch_rank_score(int select, const RankSide& u, const RankSide& c, const int64_t* sel_ptr, const int32_t* sel_rows,
+                       int kp, int splits, int n_top, double w0, uint64_t* lkey, uint32_t* lidx, hipStream_t st);
 // the splits' lists merged in split order; the first n_top per context into out_idx / out_score
 // (w0 for a pair without a learned entry, else the key's value clamped to [lo, hi]; row -1 and NaN
 // where a list's entry is padding: fewer eligible rows than n_top)
 void launch_rank_merge(const uint64_t* lkey, const uint32_t* lidx, int64_t Ut, int splits, int n_top,
                        const uint32_t* cnt_u, const uint32_t* cnt_c, double w0, double lo, double hi, int32_t* out_idx,
                        double* out_score, hipStream_t st);
-// fm_rank_positions: contexts [0, Ut) of the given arrays (Ut <= rank_position_ctx_tile()) against all C
-// candidates.  Device lists as launch_rank_score_select takes them: tgt_ptr[Ut + 1] / tgt_rows, the
-// longest of the tile's target lists `longest` >= 1; ex_ptr / ex_rows the exclude lists, ex_ptr null for
+// fm_rank_positions: the contexts u (a tile of at most rank_position_ctx_tile()) against all candidates c.
+// Device lists as launch_rank_score takes them: tgt_ptr[u.n + 1] / tgt_rows, the longest of the tile's
+// target lists `longest` >= 1; ex_ptr / ex_rows the exclude lists, ex_ptr null for
 // none.  Per target e the rows of this launch's splits that rank before it are added onto position[e]
 // (zeroed by the caller; integer atomics) and score[e] is written: k_rank_merge's score of the pair;
 // -1 / NaN for a target on its context's exclude list.
 int64_t rank_position_ctx_tile();
-void launch_rank_position(const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut, const double* sum_c,
-                          const double* bias_c, const uint32_t* cnt_c, int64_t C, const int64_t* tgt_ptr,
-                          const int32_t* tgt_rows, int64_t longest, const int64_t* ex_ptr, const int32_t* ex_rows, int kp,
-                          int splits, double w0, double lo, double hi, int32_t* position, double* score, hipStream_t st);
+void launch_rank_position(const RankSide& u, const RankSide& c, const int64_t* tgt_ptr, const int32_t* tgt_rows,
+                          int64_t longest, const int64_t* ex_ptr, const int32_t* ex_rows, int kp, int splits, double w0,
+                          double lo, double hi, int32_t* position, double* score, hipStream_t st);
 
 // fm_batch_from_rows: dst row s = src row rows[s] (device rows[B]); row_ptr_in[B + 1] (device) is the
 // result's row_ptr, computed by the host from the source's

@@ -86,10 +86,11 @@ __device__ __forceinline__ void bitonic_stage(uint64_t* key, uint32_t* row, int 
   }
   __syncthreads();
 }
-// a chunk in any order -> descending (the caller has synchronised after writing key / row)
-__device__ __forceinline__ void bitonic_sort(uint64_t* key, uint32_t* row) {
-  for (int kk = 2; kk <= kRankChunk; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) bitonic_stage(key, row, j, kk, kRankChunk);
+// n elements in any order (n a power of two <= kRankChunk) -> descending (the caller has synchronised
+// after writing key / row)
+__device__ __forceinline__ void bitonic_sort_n(uint64_t* key, uint32_t* row, int n) {
+  for (int kk = 2; kk <= n; kk <<= 1)
+    for (int j = kk >> 1; j > 0; j >>= 1) bitonic_stage(key, row, j, kk, n);
 }
 // the first W of best[] and of add[], both descending (W a power of two >= n_top) -> the first W of
 // best[] = the best W of the two, descending
@@ -128,7 +129,91 @@ __global__ __launch_bounds__(kBlock) void k_rank_bias(const double* __restrict__
   bias[r] = ql.y + 0.5 * (ss - ql.x);
 }
 
-// block b: context b / splits, split b % splits = the chunks [nch s / splits, nch (s + 1) / splits)
+// ---- what the score kernel and k_rank_position share: a block's context, a pair's key, a context's
+// list of candidate rows (sel_rows / ex_rows: strictly ascending), the score a call returns.
+constexpr int kSelAll = FM_RANK_SELECT_ALL, kSelOnly = FM_RANK_SELECT_ONLY, kSelExcept = FM_RANK_SELECT_EXCEPT;
+constexpr int kMaskWords = kRankChunk / 32;
+
+// A block's context u and its split s of n rows: w0 + a_u, whether u has a learned entry, and the
+// split's chunks [nch s / splits, nch (s + 1) / splits) of kRankChunk rows.  (S_u goes into LDS in the
+// kernel itself, one line: staged from inside a helper, k_rank_position takes 84 SGPRs for its 82.)
+struct RankContext {
+  double base;
+  bool learned;
+  int64_t ch0, ch1;
+};
+__device__ __forceinline__ RankContext load_context(const double* __restrict__ bias_u, const uint32_t* __restrict__ cnt_u,
+                                                    int64_t u, double w0, int64_t n, int s, int splits) {
+  const int64_t nch = (n + kRankChunk - 1) / kRankChunk;
+  return {w0 + bias_u[u], cnt_u[u] != 0, nch * s / splits, nch * (s + 1) / splits};
+}
+
+// The key of the context (su, x) and candidate row c: ((w0 + a_u) + b_c) + dot, the dot product one
+// chain over f = 0 .. kp - 1.  The only place a pair is scored.  kFreeUnroll: the loop's unrolling is
+// the compiler's choice (the bits are the chain's either way).
+template <bool kFreeUnroll = false>
+__device__ __forceinline__ uint64_t score_row(const double* su, const RankContext& x, const double* __restrict__ sum_c,
+                                              const double* __restrict__ bias_c, const uint32_t* __restrict__ cnt_c,
+                                              int64_t c, int kp, double w0) {
+  const double2* Sc = reinterpret_cast<const double2*>(sum_c + c * kp);
+  double dot = 0.0;
+  auto step = [&](int f) {
+    const double2 v = Sc[f];
+    dot = fma(su[2 * f], v.x, dot);
+    dot = fma(su[2 * f + 1], v.y, dot);
+  };
+  if (kFreeUnroll) {
+    // k_rank_score: more loads in flight at its 71 VGPRs (6 waves per SIMD either way)
+    for (int f = 0; f < kp / 2; ++f) step(f);
+  } else {
+    // beside the list code, unrolled further the four rows of a thread hold 83 to 90 VGPRs (5 waves per SIMD)
+#pragma unroll 2
+    for (int f = 0; f < kp / 2; ++f) step(f);
+  }
+  double y = (x.base + bias_c[c]) + dot;
+  if (!x.learned && cnt_c[c] == 0) y = w0;  // no learned entry on either side ranks at w0
+  return key_of(y + 0.0);
+}
+
+// the first entry of rows[lo, hi) that is >= first (hi: none)
+__device__ __forceinline__ int list_lower_bound(const int32_t* __restrict__ rows, int lo, int hi, int64_t first) {
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if (rows[mid] < first) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// The chunk's 1024-bit mask (LDS) of the rows [c0, c0 + kRankChunk) that rows[cur, l1) lists, cur the
+// first entry >= c0: cleared, marked (atomicOr: any order of arrival gives the same mask) and counted.
+// Ascending rows make the chunk's entries one run, its length the mask's population: the return value,
+// the same in every lane, is what cur moves on by.  The last reads of the mask's previous use lie before
+// a barrier; this ends behind one.
+__device__ __forceinline__ int mark_listed(uint32_t* mask, const int32_t* __restrict__ rows, int cur, int l1, int64_t c0) {
+  const int tid = threadIdx.x;
+  if (tid < kMaskWords) mask[tid] = 0;
+  __syncthreads();
+  for (int e = cur + tid; e < l1; e += kBlock) {
+    const int64_t d = (int64_t)rows[e] - c0;
+    if (d >= kRankChunk) break;
+    if (d >= 0) atomicOr(&mask[d >> 5], 1u << (d & 31));
+  }
+  __syncthreads();
+  int marked = __popc(mask[tid & (kMaskWords - 1)]);  // every 32 lanes hold the 32 words: their sum, in each lane
+  for (int d = kMaskWords / 2; d > 0; d >>= 1) marked += __shfl_xor(marked, d);
+  return __builtin_amdgcn_readfirstlane(marked);
+}
+__device__ __forceinline__ bool listed(const uint32_t* mask, int i) { return (mask[i >> 5] >> (i & 31)) & 1u; }
+
+// The score a call returns for a pair of key `key`: globalBias unclamped for a pair without a learned
+// entry (Model.scala:86), else the key's value clamped.
+__device__ __forceinline__ double final_score(uint64_t key, bool learned_u, uint32_t cnt_c_of_row, double w0, double lo,
+                                              double hi) {
+  return learned_u || cnt_c_of_row != 0 ? fmin(fmax(value_of(key), lo), hi) : w0;
+}
+
+// The score kernel without lists.  Block b: context b / splits, split b % splits = the chunks
+// [nch s / splits, nch (s + 1) / splits) of the candidates.  It stays a kernel of its own: as a third
+// mode of the template below its pass measured 0.7 to 2 % slower at k = 16.
 __global__ __launch_bounds__(kBlock) void k_rank_score(const double* __restrict__ sum_u, const double* __restrict__ bias_u,
                                                        const uint32_t* __restrict__ cnt_u, const double* __restrict__ sum_c,
                                                        const double* __restrict__ bias_c, const uint32_t* __restrict__ cnt_c,
@@ -140,16 +225,17 @@ __global__ __launch_bounds__(kBlock) void k_rank_score(const double* __restrict_
   const int tid = threadIdx.x;
   const int64_t u = blockIdx.x / splits;
   const int s = blockIdx.x % splits;
+  // load_context's values in the order this kernel has always formed them: through the helper the
+  // prologue compiles to other code, and this kernel's code is held to what was measured
   const int64_t nch = (C + kRankChunk - 1) / kRankChunk;
   const int64_t ch0 = nch * s / splits, ch1 = nch * (s + 1) / splits;
   for (int f = tid; f < kp; f += kBlock) su[f] = sum_u[u * kp + f];
   const int W = list_width(n_top);
-  const double base = w0 + bias_u[u];
-  const bool learned_u = cnt_u[u] != 0;
+  const RankContext x = {w0 + bias_u[u], cnt_u[u] != 0, ch0, ch1};
   __syncthreads();
-  for (int64_t ch = ch0; ch < ch1; ++ch) {
-    uint64_t* key = ch == ch0 ? bkey : ckey;  // the split's first chunk is its running list
-    uint32_t* row = ch == ch0 ? brow : crow;
+  for (int64_t ch = x.ch0; ch < x.ch1; ++ch) {
+    uint64_t* key = ch == x.ch0 ? bkey : ckey;  // the split's first chunk is its running list
+    uint32_t* row = ch == x.ch0 ? brow : crow;
 #pragma unroll
     for (int j = 0; j < kRankPer; ++j) {
       const int i = tid + j * kBlock;
@@ -157,24 +243,15 @@ __global__ __launch_bounds__(kBlock) void k_rank_score(const double* __restrict_
       uint64_t k = kWorstKey;
       uint32_t r = kNoRow;
       if (c < C) {
-        const double2* Sc = reinterpret_cast<const double2*>(sum_c + c * kp);
-        double dot = 0.0;
-        for (int f = 0; f < kp / 2; ++f) {
-          const double2 v = Sc[f];
-          dot = fma(su[2 * f], v.x, dot);
-          dot = fma(su[2 * f + 1], v.y, dot);
-        }
-        double y = (base + bias_c[c]) + dot;
-        if (!learned_u && cnt_c[c] == 0) y = w0;  // no learned entry on either side ranks at w0
-        k = key_of(y + 0.0);
+        k = score_row<true>(su, x, sum_c, bias_c, cnt_c, c, kp, w0);
         r = (uint32_t)c;
       }
       key[i] = k;
       row[i] = r;
     }
     __syncthreads();
-    bitonic_sort(key, row);
-    if (ch != ch0) fold_sorted(bkey, brow, ckey, crow, W);
+    bitonic_sort_n(key, row, kRankChunk);
+    if (ch != x.ch0) fold_sorted(bkey, brow, ckey, crow, W);
   }
   const int64_t o = ((int64_t)u * splits + s) * n_top;
   for (int i = tid; i < n_top; i += kBlock) {
@@ -183,37 +260,12 @@ __global__ __launch_bounds__(kBlock) void k_rank_score(const double* __restrict_
   }
 }
 
-// ---- per-context row lists (fm_rank_*_select).  k_rank_score above is left as it was; the kernel
-// below scores with the same expression in the same order (score_row), so a pair has the same bits
-// in both, and hands the same sort, fold and merge the same (key, row) entries.
-constexpr int kSelOnly = FM_RANK_SELECT_ONLY, kSelExcept = FM_RANK_SELECT_EXCEPT;
-constexpr int kMaskWords = kRankChunk / 32;
-
-// the key of context (su, base, learned_u) and candidate row c: k_rank_score's, operation for operation
-__device__ __forceinline__ uint64_t score_row(const double* su, double base, bool learned_u, const double* __restrict__ sum_c,
-                                              const double* __restrict__ bias_c, const uint32_t* __restrict__ cnt_c,
-                                              int64_t c, int kp, double w0) {
-  const double2* Sc = reinterpret_cast<const double2*>(sum_c + c * kp);
-  double dot = 0.0;
-  // one chain either way; unrolled further, the four rows of a thread hold 83 to 90 VGPRs (5 waves per SIMD)
-#pragma unroll 2
-  for (int f = 0; f < kp / 2; ++f) {
-    const double2 v = Sc[f];
-    dot = fma(su[2 * f], v.x, dot);
-    dot = fma(su[2 * f + 1], v.y, dot);
-  }
-  double y = (base + bias_c[c]) + dot;
-  if (!learned_u && cnt_c[c] == 0) y = w0;  // no learned entry on either side ranks at w0
-  return key_of(y + 0.0);
-}
-
-// Block b: context b / splits, split b % splits.  The list of context u is sel_rows[sel_ptr[u] ..
-// sel_ptr[u + 1]), candidate rows in [0, C), strictly ascending (the host has checked all of it).
-//   kSelExcept  the splits cut the candidate chunks as k_rank_score's do.  The list's cursor starts at
-//               the first entry >= the split's first row (binary search) and moves on by the entries
-//               each chunk marks in its 1024-bit LDS mask (atomicOr: any order of arrival gives the
-//               same mask; ascending rows make the chunk's entries one run, its length the mask's
-//               population).  A marked row enters the chunk as the padding does.
+// The score kernel under per-context lists: k_rank_score's blocks, keys (score_row), sort and fold.  The
+// list of context u is sel_rows[sel_ptr[u] .. sel_ptr[u + 1]), candidate rows in [0, C), strictly
+// ascending (the host has checked all of it).
+//   kSelExcept  the splits cut the candidates as k_rank_score's do.  The list's cursor starts at the first
+//               entry >= the split's first row and moves on by the entries each chunk marks in its mask
+//               (mark_listed).  A marked row enters the chunk as the padding does.
 //   kSelOnly    the splits cut the chunks of the context's *list*, kRankChunk entries each; a thread
 //               gathers the summaries of its listed rows and carries the candidate row as the
 //               tie-break.  The split count comes from the call's longest list, so a shorter list
@@ -234,10 +286,9 @@ __global__ __launch_bounds__(kBlock) void k_rank_score_sel(const double* __restr
   const int s = blockIdx.x % splits;
   const int l0 = (int)sel_ptr[u], l1 = (int)sel_ptr[u + 1];  // sel_ptr[U] < 2^31
   const int64_t n = kMode == kSelOnly ? l1 - l0 : C;  // what the splits cut: the list, or the candidates
-  const int64_t nch = (n + kRankChunk - 1) / kRankChunk;
-  const int64_t ch0 = nch * s / splits, ch1 = nch * (s + 1) / splits;
+  const RankContext x = load_context(bias_u, cnt_u, u, w0, n, s, splits);
   const int64_t o = ((int64_t)u * splits + s) * n_top;
-  if (ch0 == ch1) {  // kSelOnly: no chunk of a shorter list falls into this split
+  if (x.ch0 == x.ch1) {  // kSelOnly: no chunk of a shorter list falls into this split
     for (int i = tid; i < n_top; i += kBlock) {
       lkey[o + i] = kWorstKey;
       lidx[o + i] = kNoRow;
@@ -246,71 +297,43 @@ __global__ __launch_bounds__(kBlock) void k_rank_score_sel(const double* __restr
   }
   for (int f = tid; f < kp; f += kBlock) su[f] = sum_u[u * kp + f];
   const int W = list_width(n_top);
-  const double base = w0 + bias_u[u];
-  const bool learned_u = cnt_u[u] != 0;
   int cur = l0;  // kSelExcept: the first list entry at or after the chunk's first row
-  if (kMode == kSelExcept) {
-    int hi = l1;
-    const int64_t first = ch0 * kRankChunk;
-    while (cur < hi) {
-      const int mid = cur + (hi - cur) / 2;
-      if (sel_rows[mid] < first) cur = mid + 1; else hi = mid;
-    }
-  }
+  if (kMode == kSelExcept) cur = list_lower_bound(sel_rows, l0, l1, x.ch0 * kRankChunk);
   __syncthreads();
-  for (int64_t ch = ch0; ch < ch1; ++ch) {
-    uint64_t* key = ch == ch0 ? bkey : ckey;  // the split's first chunk is its running list
-    uint32_t* row = ch == ch0 ? brow : crow;
+  for (int64_t ch = x.ch0; ch < x.ch1; ++ch) {
+    uint64_t* key = ch == x.ch0 ? bkey : ckey;  // the split's first chunk is its running list
+    uint32_t* row = ch == x.ch0 ? brow : crow;
     const int64_t c0 = ch * kRankChunk;
-    if (kMode == kSelExcept) {
-      // the last reads of the mask lie before the barriers of the chunk's sort
-      if (tid < kMaskWords) mask[tid] = 0;
-      __syncthreads();
-      for (int e = cur + tid; e < l1; e += kBlock) {
-        const int64_t d = (int64_t)sel_rows[e] - c0;
-        if (d >= kRankChunk) break;
-        if (d >= 0) atomicOr(&mask[d >> 5], 1u << (d & 31));
-      }
-      __syncthreads();
-      int marked = __popc(mask[tid & (kMaskWords - 1)]);  // every 32 lanes hold the 32 words: their sum, in each lane
-      for (int d = kMaskWords / 2; d > 0; d >>= 1) marked += __shfl_xor(marked, d);
-      cur += __builtin_amdgcn_readfirstlane(marked);
-    }
+    if (kMode == kSelExcept) cur += mark_listed(mask, sel_rows, cur, l1, c0);
 #pragma unroll
     for (int j = 0; j < kRankPer; ++j) {
       const int i = tid + j * kBlock;
       uint64_t k = kWorstKey;
       uint32_t r = kNoRow;
-      if (kMode == kSelOnly) {
-        if (c0 + i < n) {
-          r = (uint32_t)sel_rows[l0 + c0 + i];
-          k = score_row(su, base, learned_u, sum_c, bias_c, cnt_c, r, kp, w0);
-        }
-      } else {
-        const int64_t c = c0 + i;
-        if (c < C) {
-          k = score_row(su, base, learned_u, sum_c, bias_c, cnt_c, c, kp, w0);
-          r = (uint32_t)c;
-        }
+      const int64_t c = c0 + i;
+      if (c < n) {
+        const int64_t cr = kMode == kSelOnly ? sel_rows[l0 + c] : c;  // the candidate row
+        k = score_row(su, x, sum_c, bias_c, cnt_c, cr, kp, w0);
+        r = (uint32_t)cr;
       }
       key[i] = k;
       row[i] = r;
     }
     if (kMode == kSelExcept) {
-      // a listed row was scored like the rest (the scoring loop stays k_rank_score's); its owner
-      // now enters it as padding
+      // a listed row was scored like the rest (the scoring loop stays k_rank_score's); its owner now
+      // enters it as padding
 #pragma unroll
       for (int j = 0; j < kRankPer; ++j) {
         const int i = tid + j * kBlock;
-        if ((mask[i >> 5] >> (i & 31)) & 1u) {
+        if (listed(mask, i)) {
           key[i] = kWorstKey;
           row[i] = kNoRow;
         }
       }
     }
     __syncthreads();
-    bitonic_sort(key, row);
-    if (ch != ch0) fold_sorted(bkey, brow, ckey, crow, W);
+    bitonic_sort_n(key, row, kRankChunk);
+    if (ch != x.ch0) fold_sorted(bkey, brow, ckey, crow, W);
   }
   for (int i = tid; i < n_top; i += kBlock) {
     lkey[o + i] = bkey[i];
@@ -341,11 +364,10 @@ __global__ __launch_bounds__(kBlock) void k_rank_merge(const uint64_t* __restric
   const bool learned_u = cnt_u[u] != 0;
   for (int i = tid; i < n_top; i += kBlock) {
     const uint32_t c = brow[i];
-    double y = w0;  // a pair without a learned entry: globalBias, unclamped (Model.scala:86)
-    if (c == kNoRow) y = __longlong_as_double(0x7FF8000000000000ll);  // fewer eligible rows than n_top (the _select calls): NaN
-    else if (learned_u || cnt_c[c] != 0) y = fmin(fmax(value_of(bkey[i]), lo), hi);
+    // padding: fewer eligible rows than n_top (the _select calls), row -1 and NaN
     out_idx[u * n_top + i] = (int32_t)c;
-    out_score[u * n_top + i] = y;
+    out_score[u * n_top + i] = c == kNoRow ? __longlong_as_double(0x7FF8000000000000ll)
+                                           : final_score(bkey[i], learned_u, cnt_c[c], w0, lo, hi);
   }
 }
 
@@ -371,11 +393,6 @@ __global__ __launch_bounds__(kBlock) void k_rank_merge(const uint64_t* __restric
 //             no count from anyone.
 constexpr int kPosCtxTile = 65535;  // contexts of one launch: the grid's y extent
 
-__device__ __forceinline__ void bitonic_sort_n(uint64_t* key, uint32_t* row, int n) {
-  for (int kk = 2; kk <= n; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) bitonic_stage(key, row, j, kk, n);
-}
-
 __global__ __launch_bounds__(kBlock) void k_rank_position(
     const double* __restrict__ sum_u, const double* __restrict__ bias_u, const uint32_t* __restrict__ cnt_u,
     const double* __restrict__ sum_c, const double* __restrict__ bias_c, const uint32_t* __restrict__ cnt_c, int64_t C,
@@ -399,63 +416,40 @@ __global__ __launch_bounds__(kBlock) void k_rank_position(
   while (n < m) n <<= 1;
   const bool ex = ex_ptr != nullptr;
   const int l0 = ex ? (int)ex_ptr[u] : 0, l1 = ex ? (int)ex_ptr[u + 1] : 0;  // ex_ptr[U] < 2^31
-  const int64_t nch = (C + kRankChunk - 1) / kRankChunk;
-  const int64_t ch0 = nch * s / splits, ch1 = nch * (s + 1) / splits;
+  const RankContext x = load_context(bias_u, cnt_u, u, w0, C, s, splits);
   for (int f = tid; f < kp; f += kBlock) su[f] = sum_u[u * kp + f];
-  const double base = w0 + bias_u[u];
-  const bool learned_u = cnt_u[u] != 0;
   __syncthreads();
   for (int i = tid; i < kRankChunk; i += kBlock) {
     uint64_t k = kWorstKey;
-    uint32_t x = kNoRow;
+    uint32_t xi = kNoRow;
     if (i < m) {
       const uint32_t r = (uint32_t)tgt_rows[t0 + i];
       lrow[i] = r;
-      k = score_row(su, base, learned_u, sum_c, bias_c, cnt_c, r, kp, w0);
-      x = (uint32_t)i;
+      k = score_row(su, x, sum_c, bias_c, cnt_c, r, kp, w0);
+      xi = (uint32_t)i;
     }
     tkey[i] = k;
-    tidx[i] = x;
+    tidx[i] = xi;
     hist[i] = 0;
   }
   __syncthreads();
   bitonic_sort_n(tkey, tidx, n);
 
   int cur = l0;  // the first exclude entry at or after the chunk's first row
-  if (ex) {
-    int top = l1;
-    const int64_t first = ch0 * kRankChunk;
-    while (cur < top) {
-      const int mid = cur + (top - cur) / 2;
-      if (ex_rows[mid] < first) cur = mid + 1; else top = mid;
-    }
-  }
+  if (ex) cur = list_lower_bound(ex_rows, l0, l1, x.ch0 * kRankChunk);
   uint32_t all = 0;  // rows of this thread that rank before every target of the tile
-  for (int64_t ch = ch0; ch < ch1; ++ch) {
+  for (int64_t ch = x.ch0; ch < x.ch1; ++ch) {
     const int64_t c0 = ch * kRankChunk;
-    const uint32_t* mk = mask[(ch - ch0) & 1];
-    if (ex) {
-      uint32_t* mw = mask[(ch - ch0) & 1];
-      if (tid < kMaskWords) mw[tid] = 0;
-      __syncthreads();
-      for (int e = cur + tid; e < l1; e += kBlock) {
-        const int64_t d = (int64_t)ex_rows[e] - c0;
-        if (d >= kRankChunk) break;
-        if (d >= 0) atomicOr(&mw[d >> 5], 1u << (d & 31));
-      }
-      __syncthreads();
-      int marked = __popc(mk[tid & (kMaskWords - 1)]);  // every 32 lanes hold the 32 words: their sum, in each lane
-      for (int d = kMaskWords / 2; d > 0; d >>= 1) marked += __shfl_xor(marked, d);
-      cur += __builtin_amdgcn_readfirstlane(marked);
-    }
+    uint32_t* mk = mask[(ch - x.ch0) & 1];
+    if (ex) cur += mark_listed(mk, ex_rows, cur, l1, c0);
     uint64_t key[kRankPer];
     bool live[kRankPer];
 #pragma unroll
     for (int j = 0; j < kRankPer; ++j) {
       const int i = tid + j * kBlock;
       const int64_t c = c0 + i;
-      live[j] = c < C && !(ex && ((mk[i >> 5] >> (i & 31)) & 1u));
-      key[j] = live[j] ? score_row(su, base, learned_u, sum_c, bias_c, cnt_c, c, kp, w0) : kWorstKey;
+      live[j] = c < C && !(ex && listed(mk, i));
+      key[j] = live[j] ? score_row(su, x, sum_c, bias_c, cnt_c, c, kp, w0) : kWorstKey;
     }
 #pragma unroll
     for (int j = 0; j < kRankPer; ++j) {
@@ -482,14 +476,14 @@ __global__ __launch_bounds__(kBlock) void k_rank_position(
     run += hist[tid * kRankPer + j];
     h[j] = run;
   }
-  uint32_t x = run;
+  uint32_t scan = run;
   for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if ((tid & 63) >= d) x += y;
+    const uint32_t y = __shfl_up(scan, d);
+    if ((tid & 63) >= d) scan += y;
   }
-  if ((tid & 63) == 63) wsum[tid >> 6] = x;
+  if ((tid & 63) == 63) wsum[tid >> 6] = scan;
   __syncthreads();
-  uint32_t off = x - run;
+  uint32_t off = scan - run;
   for (int wv = 0; wv < (tid >> 6); ++wv) off += wsum[wv];
 #pragma unroll
   for (int j = 0; j < kRankPer; ++j) {
@@ -499,11 +493,7 @@ __global__ __launch_bounds__(kBlock) void k_rank_position(
     const uint32_t r = lrow[x_t];
     bool out = false;  // the target is on the context's own exclude list
     if (ex) {
-      int a = l0, b = l1;
-      while (a < b) {
-        const int mid = a + (b - a) / 2;
-        if ((uint32_t)ex_rows[mid] < r) a = mid + 1; else b = mid;
-      }
+      const int a = list_lower_bound(ex_rows, l0, l1, r);
       out = a < l1 && (uint32_t)ex_rows[a] == r;
     }
     const int64_t e = t0 + x_t;
@@ -516,11 +506,7 @@ __global__ __launch_bounds__(kBlock) void k_rank_position(
     }
     const uint32_t count = off + h[j];
     if (count) atomicAdd(&position[e], (int32_t)count);
-    if (s == 0) {
-      double y = w0;  // a pair without a learned entry: globalBias, unclamped (k_rank_merge's rule)
-      if (learned_u || cnt_c[r] != 0) y = fmin(fmax(value_of(tkey[i]), lo), hi);
-      score[e] = y;
-    }
+    if (s == 0) score[e] = final_score(tkey[i], x.learned, cnt_c[r], w0, lo, hi);
   }
 }
 
@@ -528,18 +514,18 @@ __global__ __launch_bounds__(kBlock) void k_rank_position(
 
 int64_t rank_position_ctx_tile() { return kPosCtxTile; }
 
-void launch_rank_position(const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut, const double* sum_c,
-                          const double* bias_c, const uint32_t* cnt_c, int64_t C, const int64_t* tgt_ptr,
-                          const int32_t* tgt_rows, int64_t longest, const int64_t* ex_ptr, const int32_t* ex_rows, int kp,
-                          int splits, double w0, double lo, double hi, int32_t* position, double* score, hipStream_t st) {
+void launch_rank_position(const RankSide& u, const RankSide& c, const int64_t* tgt_ptr, const int32_t* tgt_rows,
+                          int64_t longest, const int64_t* ex_ptr, const int32_t* ex_rows, int kp, int splits, double w0,
+                          double lo, double hi, int32_t* position, double* score, hipStream_t st) {
   FM_REQUIRE(kp <= 256, "dimFactorization > 256 is not supported");
-  FM_REQUIRE(Ut >= 1 && Ut <= kPosCtxTile && C >= 1 && C < (int64_t(1) << 31) && longest >= 1 && longest <= C,
+  FM_REQUIRE(u.n >= 1 && u.n <= kPosCtxTile && c.n >= 1 && c.n < (int64_t(1) << 31) && longest >= 1 && longest <= c.n,
              "rank positions: bad shape");
-  FM_REQUIRE(splits >= 1 && splits <= kRankMaxSplits && splits <= (C + kRankChunk - 1) / kRankChunk,
+  FM_REQUIRE(splits >= 1 && splits <= kRankMaxSplits && splits <= (c.n + kRankChunk - 1) / kRankChunk,
              "rank positions: every split needs a chunk");
   const int64_t tiles = (longest + kRankChunk - 1) / kRankChunk;  // < 2^21, times splits <= 64: below 2^31
-  hipLaunchKernelGGL(k_rank_position, dim3((unsigned)(tiles * splits), (unsigned)Ut), dim3(kBlock), 0, st, sum_u, bias_u, cnt_u,
-                     sum_c, bias_c, cnt_c, C, tgt_ptr, tgt_rows, ex_ptr, ex_rows, kp, splits, w0, lo, hi, position, score);
+  hipLaunchKernelGGL(k_rank_position, dim3((unsigned)(tiles * splits), (unsigned)u.n), dim3(kBlock), 0, st, u.sum, u.bias,
+                     u.cnt, c.sum, c.bias, c.cnt, c.n, tgt_ptr, tgt_rows, ex_ptr, ex_rows, kp, splits, w0, lo, hi, position,
+                     score);
   FM_HIP_CHECK(hipGetLastError());
 }
 
@@ -562,35 +548,21 @@ void launch_rank_bias(const double* summary, int64_t n, int kp, double* bias, hi
   FM_HIP_CHECK(hipGetLastError());
 }
 
-void launch_rank_score(const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut, const double* sum_c,
-                       const double* bias_c, const uint32_t* cnt_c, int64_t C, int kp, int splits, int n_top, double w0,
-                       uint64_t* lkey, uint32_t* lidx, hipStream_t st) {
+void launch_rank_score(int select, const RankSide& u, const RankSide& c, const int64_t* sel_ptr, const int32_t* sel_rows,
+                       int kp, int splits, int n_top, double w0, uint64_t* lkey, uint32_t* lidx, hipStream_t st) {
   FM_REQUIRE(kp <= 256, "dimFactorization > 256 is not supported");
-  FM_REQUIRE(Ut >= 1 && C >= 1 && n_top >= 1 && n_top <= kRankChunk && n_top <= C, "rank: bad shape");
-  FM_REQUIRE(splits >= 1 && splits <= (C + kRankChunk - 1) / kRankChunk, "rank: every split needs a chunk");
-  FM_REQUIRE(Ut * splits < (int64_t(1) << 31), "rank: context tile too large");
-  hipLaunchKernelGGL(k_rank_score, dim3((unsigned)(Ut * splits)), dim3(kBlock), 0, st, sum_u, bias_u, cnt_u, sum_c, bias_c,
-                     cnt_c, C, kp, splits, n_top, w0, lkey, lidx);
-  FM_HIP_CHECK(hipGetLastError());
-}
-
-void launch_rank_score_select(int select, const double* sum_u, const double* bias_u, const uint32_t* cnt_u, int64_t Ut,
-                              const double* sum_c, const double* bias_c, const uint32_t* cnt_c, int64_t C,
-                              const int64_t* sel_ptr, const int32_t* sel_rows, int kp, int splits, int n_top, double w0,
-                              uint64_t* lkey, uint32_t* lidx, hipStream_t st) {
-  FM_REQUIRE(kp <= 256, "dimFactorization > 256 is not supported");
-  FM_REQUIRE(select == kSelOnly || select == kSelExcept, "rank: bad select");
-  FM_REQUIRE(Ut >= 1 && C >= 1 && n_top >= 1 && n_top <= kRankChunk && n_top <= C, "rank: bad shape");
+  FM_REQUIRE(select == kSelAll || select == kSelOnly || select == kSelExcept, "rank: bad select");
+  FM_REQUIRE(u.n >= 1 && c.n >= 1 && n_top >= 1 && n_top <= kRankChunk && n_top <= c.n, "rank: bad shape");
   FM_REQUIRE(splits >= 1 && splits <= kRankMaxSplits, "rank: bad split count");
-  FM_REQUIRE(select == kSelOnly || splits <= (C + kRankChunk - 1) / kRankChunk, "rank: every split needs a chunk");
-  FM_REQUIRE(Ut * splits < (int64_t(1) << 31), "rank: context tile too large");
-  const dim3 grid((unsigned)(Ut * splits)), block(kBlock);
-  if (select == kSelOnly)
-    hipLaunchKernelGGL(k_rank_score_sel<kSelOnly>, grid, block, 0, st, sum_u, bias_u, cnt_u, sum_c, bias_c, cnt_c, C, sel_ptr,
-                       sel_rows, kp, splits, n_top, w0, lkey, lidx);
+  FM_REQUIRE(select == kSelOnly || splits <= (c.n + kRankChunk - 1) / kRankChunk, "rank: every split needs a chunk");
+  FM_REQUIRE(u.n * splits < (int64_t(1) << 31), "rank: context tile too large");
+  const dim3 grid((unsigned)(u.n * splits)), block(kBlock);
+  if (select == kSelAll)
+    hipLaunchKernelGGL(k_rank_score, grid, block, 0, st, u.sum, u.bias, u.cnt, c.sum, c.bias, c.cnt, c.n, kp, splits, n_top, w0,
+                       lkey, lidx);
   else
-    hipLaunchKernelGGL(k_rank_score_sel<kSelExcept>, grid, block, 0, st, sum_u, bias_u, cnt_u, sum_c, bias_c, cnt_c, C, sel_ptr,
-                       sel_rows, kp, splits, n_top, w0, lkey, lidx);
+    hipLaunchKernelGGL(select == kSelOnly ? k_rank_score_sel<kSelOnly> : k_rank_score_sel<kSelExcept>, grid, block, 0, st, u.sum,
+                       u.bias, u.cnt, c.sum, c.bias, c.cnt, c.n, sel_ptr, sel_rows, kp, splits, n_top, w0, lkey, lidx);
   FM_HIP_CHECK(hipGetLastError());
 }
 

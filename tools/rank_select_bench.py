@@ -14,7 +14,9 @@ Python layer's normalisation (np.unique per list) is timed separately.  The libr
 per pass is read in a later pass of the same process, route by route.  `only` is compared with
 `per_ctx` bit for bit, `except` with the unrestricted call's first 1024 filtered on the host.
 Prints one JSON object (and writes it to --out).
-  python tools/rank_select_bench.py [--out FILE] [--calls N] [--reps N] [--unrestricted-only]
+  python tools/rank_select_bench.py [--out FILE] [--calls N] [--reps N] [--unrestricted-only] [--k K]
+--k: another factor count on the same rows (default c5's 16); at k = 128 a pair's dot product is eight
+times as long.
 --unrestricted-only: the `all` route alone; runs on a tree without the select calls (the parent commit),
 for the check that the unrestricted call's time did not move."""
 import argparse
@@ -36,9 +38,11 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--calls", type=int, default=50)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--unrestricted-only", action="store_true")
+ap.add_argument("--k", type=int, default=None)
 args = ap.parse_args()
 
 F, k, _, _, _ = bench.CONFIGS["c5"]
+k = args.k or k
 U, ZU, Cn, ZC, N_TOP = 64, 26, 16384, 13, 100
 N_EXCEPT, N_ONLY = 200, 512
 INF = float("inf")
