@@ -135,6 +135,18 @@ SIGNATURES = {
     "fm_rank_positions": (C.c_int, [_P, C.POINTER(fm_csr), C.POINTER(fm_csr), _I64P, _I32P, _I64P, _I32P, C.c_double,
                                     C.c_double, _I32P, _DP]),
     "fm_rank_positions_batch": (C.c_int, [_P, _P, _P, _I64P, _I32P, _I64P, _I32P, C.c_double, C.c_double, _I32P, _DP]),
+    "fm_lists_create": (C.c_int, [_P, C.c_int64, C.c_int64, _I64P, _I32P, C.POINTER(_P)]),
+    "fm_lists_from_pairs": (C.c_int, [_P, C.c_int64, C.c_int64, _I32P, _I32P, C.c_int64, C.POINTER(_P)]),
+    "fm_lists_destroy": (None, [_P]),
+    "fm_lists_contexts": (C.c_int64, [_P]),
+    "fm_lists_candidates": (C.c_int64, [_P]),
+    "fm_lists_total": (C.c_int64, [_P]),
+    "fm_lists_longest": (C.c_int64, [_P]),
+    "fm_lists_export": (C.c_int, [_P, _P, _I64P, _I32P, C.c_int64]),
+    "fm_rank_batch_select_lists": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, C.c_double, C.c_double, _I32P, _DP]),
+    "fm_rank_positions_batch_lists": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, C.c_double, _I32P, _DP]),
+    "fm_batch_sample_pairs_lists": (C.c_int, [_P, _P, _P, _I32P, _I32P, C.c_int64, C.c_int32, _P, C.c_double, C.c_double,
+                                              C.c_uint64, C.POINTER(_P), _I32P]),
     "fm_init_from_batch": (C.c_int, [_P, _P, _I64P]),
     "fm_loss_grad": (C.c_int, [_P, C.POINTER(fm_csr), _DP, _DP, _DP, _DP]),
     "fm_calc_loss_grad": (C.c_int, [_P, C.POINTER(fm_csr), C.c_double, C.c_uint64, _DP, _DP, _DP, _DP]),

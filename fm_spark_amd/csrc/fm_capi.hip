@@ -1210,6 +1210,30 @@ static void upload_lists(DevBuf& ptr, DevBuf& rows, const int64_t* host_ptr, con
   if (n) FM_HIP_CHECK(hipMemcpyAsync(rows.p, host_rows, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
 }
 
+// where a call's lists are on the device: an fm_lists' own buffers as they stand, or the host arrays' copy
+// in the context's scratch (ptr / rows), enqueued here; {null, null} without lists
+struct DevLists {
+  const int64_t* ptr = nullptr;
+  const int32_t* rows = nullptr;
+};
+static DevLists device_lists(DevBuf& ptr, DevBuf& rows, const RankList& l, int64_t U, hipStream_t st) {
+  if (l.dev_ptr) return {l.dev_ptr, l.dev_rows};
+  if (!l.ptr) return {};
+  upload_lists(ptr, rows, l.ptr, l.rows, U, st);
+  return {ptr.as<int64_t>(), rows.as<int32_t>()};
+}
+
+// An fm_lists as a call's lists, for U contexts and Cn candidates: of this context and of these sizes (what:
+// the argument's name).  Its rules were checked when it was made; nothing of it is read here but its sizes.
+static RankList resident_list(const fm_ctx* ctx, const fm_lists* l, int64_t U, int64_t Cn, const char* what) {
+  FM_REQUIRE(l->owner == ctx, std::string(what) + ": the lists belong to another context");
+  FM_REQUIRE(l->U == U, std::string(what) + ": lists of " + std::to_string(l->U) + " contexts for contexts of " +
+                            std::to_string(U) + " rows");
+  FM_REQUIRE(l->C == Cn, std::string(what) + ": lists over " + std::to_string(l->C) + " candidate rows for candidates of " +
+                             std::to_string(Cn) + " rows");
+  return {l->host_ptr.data(), nullptr, l->longest, l->ptr.as<int64_t>(), l->rows.as<int32_t>()};
+}
+
 // The stage every ranking call opens with: both row sets' summaries and biases into the context's scratch
 // (one profile entry), as the views the score and position launchers take.
 static std::pair<RankSide, RankSide> rank_summaries(fm_ctx* ctx, const BatchDev& bu, const BatchDev& bc) {
@@ -1253,14 +1277,14 @@ static int rank_impl(fm_ctx* ctx, const RankRows& rows, int32_t n_top, double lo
   w.lidx.ensure_slack(sizeof(uint32_t) * (size_t)(tile * splits * n_top));
   w.out_idx.ensure_slack(sizeof(int32_t) * (size_t)(U * n_top));
   w.out_score.ensure_slack(sizeof(double) * (size_t)(U * n_top));
-  if (sel.ptr) upload_lists(w.sel_ptr, w.sel_rows, sel.ptr, sel.rows, U, st);
+  const DevLists dsel = device_lists(w.sel_ptr, w.sel_rows, sel, U, st);
   const auto [su, sc] = rank_summaries(ctx, rows.u, rows.c);
   for (int64_t u0 = 0; u0 < U; u0 += tile) {
     const int64_t Ut = std::min<int64_t>(tile, U - u0);
     hipEvent_t e0 = ctx->prof_begin(st);
     // the tile's offsets: sel_ptr + u0 (they index the whole call's sel_rows)
-    launch_rank_score(select, su.tile(u0, Ut, kp), sc, sel.ptr ? w.sel_ptr.as<int64_t>() + u0 : nullptr,
-                      w.sel_rows.as<int32_t>(), kp, splits, n_top, w0, w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), st);
+    launch_rank_score(select, su.tile(u0, Ut, kp), sc, dsel.ptr ? dsel.ptr + u0 : nullptr, dsel.rows, kp, splits, n_top, w0,
+                      w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), st);
     ctx->prof_end("rank_score", e0, st);
     e0 = ctx->prof_begin(st);
     launch_rank_merge(w.lkey.as<uint64_t>(), w.lidx.as<uint32_t>(), Ut, splits, n_top, su.cnt + u0, sc.cnt, w0, lo, hi,
@@ -1273,12 +1297,13 @@ static int rank_impl(fm_ctx* ctx, const RankRows& rows, int32_t n_top, double lo
   return FM_OK;
 }
 
-// The four top-N entry points over either kind of row set: the shared rules, the top-N rules, the list
-// rules of the _select forms (rank_list_check; FM_RANK_SELECT_ALL takes no list), then the work.
+// The top-N entry points over either kind of row set: the shared rules, the top-N rules, the list
+// rules of the _select forms (rank_list_check; FM_RANK_SELECT_ALL takes no list) or -- resident -- the
+// fm_lists' fit (resident_list: checked when it was made), then the work.
 extern "C++" template <class Rows>
 static int rank_call(fm_ctx* ctx, const Rows* contexts, const Rows* candidates, const char* call, const char* host_call,
                      int32_t select, const int64_t* sel_ptr, const int32_t* sel_rows, int32_t n_top, double lo, double hi,
-                     int32_t* top_index, double* top_score) {
+                     int32_t* top_index, double* top_score, bool resident = false, const fm_lists* rsel = nullptr) {
   return guarded(ctx, [&]() -> int {
     const auto [U, Cn] = rank_rows_check(ctx, contexts, candidates, call, host_call);
     if (!rank_common_check(ctx, U, Cn)) return FM_OK;
@@ -1287,7 +1312,10 @@ static int rank_call(fm_ctx* ctx, const Rows* contexts, const Rows* candidates, 
     FM_REQUIRE(select == FM_RANK_SELECT_ALL || select == FM_RANK_SELECT_ONLY || select == FM_RANK_SELECT_EXCEPT,
                "select must be FM_RANK_SELECT_ALL, _ONLY or _EXCEPT, got " + std::to_string(select));
     RankList sel;
-    if (select != FM_RANK_SELECT_ALL) {
+    if (select != FM_RANK_SELECT_ALL && resident) {
+      FM_REQUIRE(rsel != nullptr, "null sel with FM_RANK_SELECT_ONLY / _EXCEPT");
+      sel = resident_list(ctx, rsel, U, Cn, "sel");
+    } else if (select != FM_RANK_SELECT_ALL) {
       FM_REQUIRE(sel_ptr != nullptr, "null sel_ptr with FM_RANK_SELECT_ONLY / _EXCEPT");
       sel = {sel_ptr, sel_rows, rank_list_check("", "sel_ptr", "sel_rows", sel_ptr, sel_rows, U, Cn)};
     }
@@ -1310,6 +1338,12 @@ int fm_rank_batch_select(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, 
                          double* top_score) {
   return rank_call<fm_batch>(ctx, contexts, candidates, "fm_rank_batch", "fm_rank_candidates", select, sel_ptr, sel_rows, n_top,
                              lo, hi, top_index, top_score);
+}
+
+int fm_rank_batch_select_lists(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t select, const fm_lists* sel,
+                               int32_t n_top, double lo, double hi, int32_t* top_index, double* top_score) {
+  return rank_call<fm_batch>(ctx, contexts, candidates, "fm_rank_batch", "fm_rank_candidates", select, nullptr, nullptr, n_top,
+                             lo, hi, top_index, top_score, true, sel);
 }
 
 int fm_rank_candidates(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candidates, int32_t n_top, double lo, double hi,
@@ -1337,8 +1371,8 @@ static int rank_positions_impl(fm_ctx* ctx, const RankRows& rows, const RankList
   hipStream_t st = ctx->stream;
   w.position.ensure_slack(sizeof(int32_t) * n_tgt);
   w.pos_score.ensure_slack(sizeof(double) * n_tgt);
-  upload_lists(w.tgt_ptr, w.tgt_rows, tgt.ptr, tgt.rows, U, st);
-  if (ex.ptr) upload_lists(w.sel_ptr, w.sel_rows, ex.ptr, ex.rows, U, st);
+  const DevLists dtgt = device_lists(w.tgt_ptr, w.tgt_rows, tgt, U, st);
+  const DevLists dex = device_lists(w.sel_ptr, w.sel_rows, ex, U, st);
   FM_HIP_CHECK(hipMemsetAsync(w.position.p, 0, sizeof(int32_t) * n_tgt, st));
   const auto [su, sc] = rank_summaries(ctx, rows.u, rows.c);
   const int splits = rank_splits(Cn, U);
@@ -1347,9 +1381,8 @@ static int rank_positions_impl(fm_ctx* ctx, const RankRows& rows, const RankList
     const int64_t Ut = std::min<int64_t>(tile, U - u0);
     hipEvent_t e0 = ctx->prof_begin(st);
     // the tile's offsets: tgt_ptr + u0, sel_ptr + u0 (they index the whole call's rows and results)
-    launch_rank_position(su.tile(u0, Ut, kp), sc, w.tgt_ptr.as<int64_t>() + u0, w.tgt_rows.as<int32_t>(), tgt.longest,
-                         ex.ptr ? w.sel_ptr.as<int64_t>() + u0 : nullptr, w.sel_rows.as<int32_t>(), kp, splits, ctx->cfg.w0, lo,
-                         hi, w.position.as<int32_t>(), w.pos_score.as<double>(), st);
+    launch_rank_position(su.tile(u0, Ut, kp), sc, dtgt.ptr + u0, dtgt.rows, tgt.longest, dex.ptr ? dex.ptr + u0 : nullptr,
+                         dex.rows, kp, splits, ctx->cfg.w0, lo, hi, w.position.as<int32_t>(), w.pos_score.as<double>(), st);
     ctx->prof_end("rank_position", e0, st);
   }
   FM_HIP_CHECK(hipMemcpyAsync(position, w.position.p, sizeof(int32_t) * n_tgt, hipMemcpyDeviceToHost, st));
@@ -1362,16 +1395,23 @@ static int rank_positions_impl(fm_ctx* ctx, const RankRows& rows, const RankList
 extern "C++" template <class Rows>
 static int rank_positions_call(fm_ctx* ctx, const Rows* contexts, const Rows* candidates, const char* call,
                                const char* host_call, const int64_t* tgt_ptr, const int32_t* tgt_rows, const int64_t* excl_ptr,
-                               const int32_t* excl_rows, double lo, double hi, int32_t* position, double* score) {
+                               const int32_t* excl_rows, double lo, double hi, int32_t* position, double* score,
+                               bool resident = false, const fm_lists* rtgt = nullptr, const fm_lists* rex = nullptr) {
   return guarded(ctx, [&]() -> int {
     const auto [U, Cn] = rank_rows_check(ctx, contexts, candidates, call, host_call);
     if (!rank_common_check(ctx, U, Cn)) return FM_OK;
     FM_REQUIRE(position != nullptr && score != nullptr, "null argument");
-    FM_REQUIRE(tgt_ptr != nullptr, "null tgt_ptr: fm_rank_positions needs the target lists");
-    const RankList tgt = {tgt_ptr, tgt_rows, rank_list_check("target list: ", "tgt_ptr", "tgt_rows", tgt_ptr, tgt_rows, U, Cn)};
-    RankList ex;
-    if (excl_ptr) ex = {excl_ptr, excl_rows, rank_list_check("exclude list: ", "excl_ptr", "excl_rows", excl_ptr, excl_rows, U, Cn)};
-    if (tgt_ptr[U] == 0) return FM_OK;
+    RankList tgt, ex;
+    if (resident) {
+      FM_REQUIRE(rtgt != nullptr, "null tgt: fm_rank_positions needs the target lists");
+      tgt = resident_list(ctx, rtgt, U, Cn, "tgt");
+      if (rex) ex = resident_list(ctx, rex, U, Cn, "excl");
+    } else {
+      FM_REQUIRE(tgt_ptr != nullptr, "null tgt_ptr: fm_rank_positions needs the target lists");
+      tgt = {tgt_ptr, tgt_rows, rank_list_check("target list: ", "tgt_ptr", "tgt_rows", tgt_ptr, tgt_rows, U, Cn)};
+      if (excl_ptr) ex = {excl_ptr, excl_rows, rank_list_check("exclude list: ", "excl_ptr", "excl_rows", excl_ptr, excl_rows, U, Cn)};
+    }
+    if (tgt.ptr[U] == 0) return FM_OK;
     return rank_positions_impl(ctx, rank_rows_ready(ctx, contexts, candidates), tgt, ex, lo, hi, position, score);
   });
 }
@@ -1391,6 +1431,141 @@ int fm_rank_positions_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidate
                             int32_t* position, double* score) {
   return rank_positions_call<fm_batch>(ctx, contexts, candidates, "fm_rank_positions_batch", "fm_rank_positions", tgt_ptr,
                                        tgt_rows, excl_ptr, excl_rows, lo, hi, position, score);
+}
+
+int fm_rank_positions_batch_lists(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, const fm_lists* tgt,
+                                  const fm_lists* excl, double lo, double hi, int32_t* position, double* score) {
+  return rank_positions_call<fm_batch>(ctx, contexts, candidates, "fm_rank_positions_batch", "fm_rank_positions", nullptr,
+                                       nullptr, nullptr, nullptr, lo, hi, position, score, true, tgt, excl);
+}
+
+// ---- resident row lists (fm_lists_*; fm_lists.hip) ----
+// what both constructors ask of the context and the sizes
+static void lists_args_check(const fm_ctx* ctx, int64_t U, int64_t C, fm_lists** out, const char* call) {
+  FM_REQUIRE(out != nullptr, "null out");
+  FM_REQUIRE(!ctx->group, std::string(call) + " needs a context of one device: a multi-GPU context's batches are cut over its "
+                                              "ranks, and the calls that read resident lists refuse it");
+  FM_REQUIRE(U >= 0 && U < (int64_t(1) << 31) && C >= 0 && C < (int64_t(1) << 31),
+             "row lists: U and C must be in [0, 2^31), got U = " + std::to_string(U) + ", C = " + std::to_string(C));
+}
+
+static std::unique_ptr<fm_lists> new_lists(fm_ctx* ctx, int64_t U, int64_t C) {
+  std::unique_ptr<fm_lists> l(new fm_lists());
+  l->owner = ctx;
+  l->device = ctx->cfg.device;
+  l->U = U;
+  l->C = C;
+  return l;
+}
+
+int fm_lists_create(fm_ctx* ctx, int64_t U, int64_t C, const int64_t* ptr, const int32_t* rows, fm_lists** out) {
+  return guarded(ctx, [&]() -> int {
+    lists_args_check(ctx, U, C, out, "fm_lists_create");
+    FM_REQUIRE(ptr != nullptr, "row lists: null ptr");
+    const int64_t longest = rank_list_check("row lists: ", "ptr", "rows", ptr, rows, U, C);
+    std::unique_ptr<fm_lists> l = new_lists(ctx, U, C);
+    l->longest = longest;
+    l->host_ptr.assign(ptr, ptr + U + 1);
+    const size_t n = (size_t)ptr[U];
+    l->ptr.ensure(sizeof(int64_t) * (size_t)(U + 1));
+    l->rows.ensure(sizeof(int32_t) * n);
+    FM_HIP_CHECK(hipMemcpy(l->ptr.p, ptr, sizeof(int64_t) * (size_t)(U + 1), hipMemcpyHostToDevice));
+    if (n) FM_HIP_CHECK(hipMemcpy(l->rows.p, rows, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    *out = l.release();
+    return FM_OK;
+  });
+}
+
+int fm_lists_from_pairs(fm_ctx* ctx, int64_t U, int64_t C, const int32_t* pair_ctx, const int32_t* pair_cand, int64_t n,
+                        fm_lists** out) {
+  return guarded(ctx, [&]() -> int {
+    lists_args_check(ctx, U, C, out, "fm_lists_from_pairs");
+    FM_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "n out of range");
+    FM_REQUIRE(n == 0 || (pair_ctx != nullptr && pair_cand != nullptr), "null pair lists");
+    std::atomic<int> bad{0};
+    parallel_chunks(n, int64_t(1) << 18, [&](int64_t lo, int64_t hi) {
+      int b = 0;
+      for (int64_t i = lo; i < hi; ++i) {
+        const int64_t u = pair_ctx[i], c = pair_cand[i];
+        b |= (u < 0 || u >= U ? 1 : 0) | (c < 0 || c >= C ? 2 : 0);
+      }
+      if (b) bad.fetch_or(b);
+    });
+    FM_REQUIRE(!(bad.load() & 1), "pair_ctx index out of [0, U = " + std::to_string(U) + ")");
+    FM_REQUIRE(!(bad.load() & 2), "pair_cand index out of [0, C = " + std::to_string(C) + ")");
+    std::unique_ptr<fm_lists> l = new_lists(ctx, U, C);
+    l->ptr.ensure(sizeof(int64_t) * (size_t)(U + 1));
+    l->host_ptr.assign((size_t)U + 1, 0);
+    hipStream_t st = ctx->stream;
+    {
+      // The call's own scratch, freed where this block ends: the pairs' upload, a sort workspace per sort (a
+      // sort's output lies in its workspace, and the context's may be sorting a prepared batch on the side
+      // stream), the head flags, their scan.
+      DevBuf dctx, dcand, flag, off, ctot, coff, total;
+      SortWork by_cand, by_ctx;
+      const uint32_t *sctx = nullptr, *scand = nullptr;
+      if (n > 0) {
+        dctx.ensure(sizeof(int32_t) * (size_t)n);
+        dcand.ensure(sizeof(int32_t) * (size_t)n);
+        FM_HIP_CHECK(hipMemcpy(dctx.p, pair_ctx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+        FM_HIP_CHECK(hipMemcpy(dcand.p, pair_cand, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+      }
+      // (profile "lists_build": the sorts through the compaction, the read-back of the offsets between them included)
+      hipEvent_t e0 = ctx->prof_begin(st);
+      if (n > 0) {
+        // by candidate, then (stable) by context: sorted by (context, candidate)
+        const uint32_t *k1 = nullptr, *v1 = nullptr;
+        radix_sort_pairs(by_cand, dcand.as<uint32_t>(), dctx.as<uint32_t>(), n, bits_for(C - 1), st, &k1, &v1);
+        radix_sort_pairs(by_ctx, v1, k1, n, bits_for(U - 1), st, &sctx, &scand);
+      }
+      const size_t nchunks = (size_t)std::max<int64_t>(pair_scan_chunks(n), 1);
+      flag.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(n, 1));
+      off.ensure(sizeof(int64_t) * ((size_t)n + 1));
+      ctot.ensure(sizeof(int64_t) * nchunks);
+      coff.ensure(sizeof(int64_t) * nchunks);
+      total.ensure(sizeof(int64_t));
+      launch_lists_offsets(sctx, scand, n, U, flag.as<uint32_t>(), off.as<int64_t>(), ctot.as<int64_t>(), coff.as<int64_t>(),
+                           total.as<int64_t>(), l->ptr.as<int64_t>(), st);
+      // the one read-back: the offsets (the host copy, the longest list, and ptr[U], which sizes rows)
+      FM_HIP_CHECK(hipMemcpyAsync(l->host_ptr.data(), l->ptr.p, sizeof(int64_t) * (size_t)(U + 1), hipMemcpyDeviceToHost, st));
+      FM_HIP_CHECK(hipStreamSynchronize(st));
+      const int64_t rows_n = l->host_ptr[U];
+      FM_REQUIRE(rows_n >= 0 && rows_n <= n, "fm_lists_from_pairs: the offsets read back are out of range");
+      l->rows.ensure(sizeof(int32_t) * (size_t)rows_n);
+      launch_lists_compact(scand, flag.as<uint32_t>(), off.as<int64_t>(), n, l->rows.as<int32_t>(), st);
+      ctx->prof_end("lists_build", e0, st);
+      FM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    for (int64_t u = 0; u < U; ++u) l->longest = std::max(l->longest, l->host_ptr[u + 1] - l->host_ptr[u]);
+    *out = l.release();
+    return FM_OK;
+  });
+}
+
+void fm_lists_destroy(fm_lists* l) {
+  if (!l) return;
+  try {
+    delete l;
+  } catch (...) {
+  }
+}
+
+int64_t fm_lists_contexts(const fm_lists* l) { return l ? l->U : -1; }
+int64_t fm_lists_candidates(const fm_lists* l) { return l ? l->C : -1; }
+int64_t fm_lists_total(const fm_lists* l) { return l ? l->total() : -1; }
+int64_t fm_lists_longest(const fm_lists* l) { return l ? l->longest : -1; }
+
+int fm_lists_export(fm_ctx* ctx, const fm_lists* l, int64_t* ptr, int32_t* rows, int64_t cap_rows) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(l != nullptr && l->owner == ctx, "the lists belong to another context");
+    const int64_t n = l->total();
+    if (ptr) FM_HIP_CHECK(hipMemcpy(ptr, l->ptr.p, sizeof(int64_t) * (size_t)(l->U + 1), hipMemcpyDeviceToHost));
+    if (rows) {
+      FM_REQUIRE(cap_rows >= n, "cap_rows " + std::to_string(cap_rows) + " is less than the lists' " + std::to_string(n) + " rows");
+      if (n) FM_HIP_CHECK(hipMemcpy(rows, l->rows.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return FM_OK;
+  });
 }
 
 // ---- pair batches (fm_batch_from_pairs / fm_batch_sample_pairs; fm_pairs.hip) ----
@@ -1523,10 +1698,13 @@ int fm_batch_from_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* c
   });
 }
 
-int fm_batch_sample_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, const int32_t* pos_ctx,
-                          const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, const int64_t* excl_ptr,
-                          const int32_t* excl_rows, double pos_label, double neg_label, uint64_t seed, fm_batch** out,
-                          int32_t* sampled) {
+// Both forms of the sampled call: the exclude lists as host arrays (excl_ptr / excl_rows: checked, staged and
+// uploaded with the positives) or -- resident -- as an fm_lists (rex; null: none), whose device buffers the
+// draw reads where they are: only the positives are staged, and the E >= 1 rule reads the object's host offsets.
+static int sample_pairs_call(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, const int32_t* pos_ctx,
+                             const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, const int64_t* excl_ptr,
+                             const int32_t* excl_rows, bool resident, const fm_lists* rex, double pos_label, double neg_label,
+                             uint64_t seed, fm_batch** out, int32_t* sampled) {
   return guarded(ctx, [&]() -> int {
     pair_args_check(ctx, contexts, candidates, out, pos_ctx, pos_cand, n_pos, "fm_batch_sample_pairs");
     FM_REQUIRE(n_neg >= 0 && n_neg <= 1024, "n_neg must be in [0, 1024], got " + std::to_string(n_neg));
@@ -1539,13 +1717,16 @@ int fm_batch_sample_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch*
       return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     };
     auto t0 = std::chrono::steady_clock::now();
-    if (excl_ptr) rank_list_check("exclude list: ", "excl_ptr", "excl_rows", excl_ptr, excl_rows, U, Cn);
+    RankList ex;
+    if (resident && rex) ex = resident_list(ctx, rex, U, Cn, "excl");
+    else if (excl_ptr) ex = {excl_ptr, excl_rows, rank_list_check("exclude list: ", "excl_ptr", "excl_rows", excl_ptr, excl_rows, U, Cn)};
+    if (ex.dev_ptr) excl_ptr = nullptr;  // (resident: from here on the host arrays are the positives alone)
     ctx->prof_host("pair_lists_check", host_ms(t0));
     for (int64_t i = 0; i < n_pos; ++i) {
       const int64_t u = pos_ctx[i], c = pos_cand[i];
       FM_REQUIRE(u >= 0 && u < U, "pos_ctx index out of [0, rows of contexts)");
       FM_REQUIRE(c >= 0 && c < Cn, "pos_cand index out of [0, rows of candidates)");
-      const int64_t L = excl_ptr ? excl_ptr[u + 1] - excl_ptr[u] : 0;
+      const int64_t L = ex.ptr ? ex.ptr[u + 1] - ex.ptr[u] : 0;
       FM_REQUIRE(Cn - L >= 1, "context " + std::to_string(u) + " (positive " + std::to_string(i) +
                                   ") has no eligible candidate row: its exclude list holds every row");
     }
@@ -1594,8 +1775,9 @@ int fm_batch_sample_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch*
     e0 = ctx->prof_begin(gs);
     const char* dl = w.lists.as<char>();  // the staging from o_ptr on
     launch_pair_sample(reinterpret_cast<const int32_t*>(dl + (o_pc - o_ptr)), reinterpret_cast<const int32_t*>(dl + (o_pd - o_ptr)),
-                       n_pos, n_neg, excl_ptr ? reinterpret_cast<const int64_t*>(dl) : nullptr,
-                       reinterpret_cast<const int32_t*>(dl + (o_ex - o_ptr)), pos_label, neg_label, seed, contexts->dev,
+                       n_pos, n_neg, ex.dev_ptr ? ex.dev_ptr : excl_ptr ? reinterpret_cast<const int64_t*>(dl) : nullptr,
+                       ex.dev_ptr ? ex.dev_rows : reinterpret_cast<const int32_t*>(dl + (o_ex - o_ptr)), pos_label, neg_label, seed,
+                       contexts->dev,
                        candidates->dev,
                        w.pair_ctx.as<int32_t>(), w.pair_cand.as<int32_t>(), w.label.as<double>(), w.len.as<uint32_t>(),
                        w.row_ptr.as<int64_t>(), w.chunk_tot.as<int64_t>(), w.chunk_off.as<int64_t>(), w.total.as<int64_t>(),
@@ -1626,6 +1808,21 @@ int fm_batch_sample_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch*
     res.commit();
     return FM_OK;
   });
+}
+
+int fm_batch_sample_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, const int32_t* pos_ctx,
+                          const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, const int64_t* excl_ptr,
+                          const int32_t* excl_rows, double pos_label, double neg_label, uint64_t seed, fm_batch** out,
+                          int32_t* sampled) {
+  return sample_pairs_call(ctx, contexts, candidates, pos_ctx, pos_cand, n_pos, n_neg, excl_ptr, excl_rows, false, nullptr,
+                           pos_label, neg_label, seed, out, sampled);
+}
+
+int fm_batch_sample_pairs_lists(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, const int32_t* pos_ctx,
+                                const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, const fm_lists* excl, double pos_label,
+                                double neg_label, uint64_t seed, fm_batch** out, int32_t* sampled) {
+  return sample_pairs_call(ctx, contexts, candidates, pos_ctx, pos_cand, n_pos, n_neg, nullptr, nullptr, true, excl, pos_label,
+                           neg_label, seed, out, sampled);
 }
 
 int fm_init_from_batch(fm_ctx* ctx, fm_batch* b, int64_t* n_present) {

@@ -170,6 +170,24 @@ struct fm_batch {
   }
 };
 
+// Per-context candidate-row lists resident on the device (fm_lists_create / fm_lists_from_pairs): U lists over
+// C candidate rows, each strictly ascending and in [0, C).  Read-only after construction.
+struct fm_lists {
+  fm_ctx* owner = nullptr;
+  int device = 0;
+  int64_t U = 0, C = 0;
+  int64_t longest = 0;            // the longest list
+  DevBuf ptr, rows;               // int64 [U + 1] offsets, int32 [ptr[U]] candidate rows
+  std::vector<int64_t> host_ptr;  // the offsets again: sizes and the per-context lengths without a device read
+  int64_t total() const { return host_ptr.empty() ? 0 : host_ptr.back(); }
+  ~fm_lists() {
+    // (each DevBuf frees itself; released here only for the order: on the lists' device)
+    (void)hipSetDevice(device);
+    rows.release();
+    ptr.release();
+  }
+};
+
 struct fm_ctx {
   std::mutex mu;
   fm_config cfg{};

@@ -385,11 +385,15 @@ struct RankWork {
   DevBuf tgt_ptr, tgt_rows;   // fm_rank_positions: the target lists, laid out as sel_ptr / sel_rows
   DevBuf position, pos_score;  // ... and its results, int32 / double per target
 };
-// a call's per-context row lists (host arrays, validated): ptr[U + 1], rows[ptr[U]]; ptr null: no list
+// a call's per-context row lists (validated): ptr[U + 1], rows[ptr[U]] on the host; ptr null: no list.
+// dev_ptr set: the lists of an fm_lists, resident already -- ptr is the object's host copy of the offsets,
+// rows stays null, and the call neither stages nor uploads anything of them.
 struct RankList {
   const int64_t* ptr = nullptr;
   const int32_t* rows = nullptr;
   int64_t longest = 0;  // the longest list of the call
+  const int64_t* dev_ptr = nullptr;
+  const int32_t* dev_rows = nullptr;
 };
 // one row set's per-row arrays on the device: the summaries (FwdOut::summary's layout), a_r and the
 // learned entries of n rows
@@ -441,6 +445,7 @@ void launch_select_rows(const BatchDev& src, const int64_t* rows, const int64_t*
 // stream alone (fm_pairs.hip's header).
 struct PairWork {
   DevBuf lists;                // the call's lists: int64 excl_ptr [U + 1], then int32 pos_ctx, pos_cand [n_pos], excl_rows
+                               // (fm_batch_sample_pairs_lists: the positives alone, the exclude lists are the fm_lists')
   DevBuf pair_ctx, pair_cand;  // int32 [B]: every output row's pair
   DevBuf label;                // double [B]
   DevBuf len;                  // uint32 [B]: every output row's entries
@@ -454,6 +459,12 @@ void launch_pair_rows(const int32_t* pair_ctx, const int32_t* pair_cand, const i
                       const BatchDev& contexts, const BatchDev& candidates, int64_t B, BatchDev& dst, hipStream_t st);
 // chunks of the row_ptr scan over B rows (the size of chunk_tot / chunk_off)
 int64_t pair_scan_chunks(int64_t B);
+// the exclusive scan of len[B] (uint32) into off[B + 1] (int64; off[B] = the sum, also left in total[0]) by
+// the three phases k_pair_chunk_sum / k_pair_scan_chunks / k_pair_scan_rows; chunk_tot / chunk_off hold
+// pair_scan_chunks(B) int64 each.  B = 0: off[0] = total[0] = 0.  fm_batch_sample_pairs' row_ptr and
+// fm_lists_from_pairs' offsets (fm_lists.hip) are both this scan.
+void launch_len_scan(const uint32_t* len, int64_t B, int64_t* off, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total,
+                     hipStream_t st);
 // fm_batch_sample_pairs' device side before the gather: the B = n_pos (1 + n_neg) pairs (each positive,
 // then its drawn negatives; device lists, excl_ptr null for none), their labels and lengths, row_ptr
 // [B + 1] by the three-phase scan and total[0] = row_ptr[B]
@@ -461,6 +472,18 @@ void launch_pair_sample(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t
                         const int32_t* excl_rows, double pos_label, double neg_label, uint64_t seed, const BatchDev& contexts,
                         const BatchDev& candidates, int32_t* pair_ctx, int32_t* pair_cand, double* label, uint32_t* len,
                         int64_t* row_ptr, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total, hipStream_t st);
+
+// ---------------------------------------------------------------- resident row lists (fm_lists.hip)
+// fm_lists_from_pairs' device side, in two halves around the one read-back (ptr: it sizes rows).  Both take
+// the n pairs sorted by (context, candidate) -- sctx / scand, device, as two stable radix sorts leave them.
+// launch_lists_offsets: flag[i] = 1 where sorted pair i opens a (context, candidate) run, off[n + 1] = the
+// flags' exclusive scan (launch_len_scan; total[0] = the distinct pairs), ptr[v] = off[the first sorted pair
+// with context >= v] for v in [0, U].  launch_lists_compact: a flagged pair i writes rows[off[i]] = scand[i].
+// Integer work, one writer per slot, no atomics: equal inputs give equal bytes.
+void launch_lists_offsets(const uint32_t* sctx, const uint32_t* scand, int64_t n, int64_t U, uint32_t* flag, int64_t* off,
+                          int64_t* chunk_tot, int64_t* chunk_off, int64_t* total, int64_t* ptr, hipStream_t st);
+void launch_lists_compact(const uint32_t* scand, const uint32_t* flag, const int64_t* off, int64_t n, int32_t* rows,
+                          hipStream_t st);
 
 // fm_batch_create_splits: each split's own row_ptr (rebased to its first entry) into split_rp
 // [B + n_splits] and every entry's sample index made relative to its split's first row

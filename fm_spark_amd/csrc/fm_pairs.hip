@@ -6,7 +6,8 @@
 //   k_pair_chunk_sum / k_pair_scan_chunks / k_pair_scan_rows
 //                  the exclusive scan of those lengths into the result's row_ptr, in the three phases
 //                  of fm_update.hip's split: chunk totals, a one-block scan of the totals (in rounds),
-//                  each chunk's local scan plus its offset
+//                  each chunk's local scan plus its offset (launch_len_scan: also the scan of
+//                  fm_lists_from_pairs' head flags, fm_lists.hip)
 // Integer work and copies only, no atomics: equal inputs give equal bits.
 //
 // The sampled call's scratch (PairWork, fm_internal.h: the lists' device copies, the drawn pairs, the
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(kBlock) void k_pair_sample(const int32_t* __restric
 constexpr int kPairChunk = kBlock;    // rows per scan chunk
 constexpr int kPairScanNT = 256;      // threads of the one-block scan of the chunk totals
 constexpr int kPairScanPer = 4;       // chunk totals per thread and round
-static_assert(kPairChunk == 256, "the scan's chunk edges tests/test_gpu_pairs.py places its row counts at");
+static_assert(kPairChunk == 256, "the scan's chunk edges tests/test_gpu_pairs.py and tests/test_gpu_row_lists.py place their counts at");
 static_assert(kPairChunk == kBlock, "k_pair_chunk_sum / k_pair_scan_rows give every row of a chunk one thread of a block");
 static_assert(kPairChunk % 64 == 0 && kPairScanNT % 64 == 0, "whole waves: the block scans combine per-wave sums");
 static_assert(kPairScanNT <= 1024 && kPairScanPer >= 1, "one block scans a round");
@@ -216,12 +217,23 @@ void launch_pair_sample(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t
   hipLaunchKernelGGL(k_pair_sample, dim3(grid_for(B, kBlock)), dim3(kBlock), 0, st, pos_ctx, pos_cand, B, n_neg, excl_ptr,
                      excl_rows, candidates.n_rows, pos_label, neg_label, seed, contexts.row_ptr.as<int64_t>(),
                      candidates.row_ptr.as<int64_t>(), pair_ctx, pair_cand, label, len);
+  launch_len_scan(len, B, row_ptr, chunk_tot, chunk_off, total, st);
+}
+
+void launch_len_scan(const uint32_t* len, int64_t B, int64_t* off, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total,
+                     hipStream_t st) {
+  if (B <= 0) {
+    FM_HIP_CHECK(hipMemsetAsync(off, 0, sizeof(int64_t), st));
+    FM_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(int64_t), st));
+    return;
+  }
   const int64_t nchunks = pair_scan_chunks(B);
   const unsigned blocks = grid_for(nchunks * kBlock, kBlock);
   hipLaunchKernelGGL(k_pair_chunk_sum, dim3(blocks), dim3(kBlock), 0, st, len, B, nchunks, chunk_tot);
-  hipLaunchKernelGGL(k_pair_scan_chunks, dim3(1), dim3(kPairScanNT), 0, st, chunk_tot, nchunks, chunk_off, row_ptr + B, total);
-  hipLaunchKernelGGL(k_pair_scan_rows, dim3(blocks), dim3(kBlock), 0, st, len, B, nchunks, chunk_off, row_ptr);
+  hipLaunchKernelGGL(k_pair_scan_chunks, dim3(1), dim3(kPairScanNT), 0, st, chunk_tot, nchunks, chunk_off, off + B, total);
+  hipLaunchKernelGGL(k_pair_scan_rows, dim3(blocks), dim3(kBlock), 0, st, len, B, nchunks, chunk_off, off);
   FM_HIP_CHECK(hipGetLastError());
 }
+
 
 }  // namespace fmhip

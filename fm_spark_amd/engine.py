@@ -118,6 +118,40 @@ class DeviceBatch:
             pass
 
 
+class RowLists:
+    """Per-context candidate-row lists resident in HBM (fm_lists_create / fm_lists_from_pairs): built once,
+    then passed wherever a call of the same context takes ``only`` / ``exclude`` / ``targets`` lists over
+    resident batches, which then checks, stages and uploads nothing of them."""
+
+    def __init__(self, ctx: "FMContext", handle):
+        self._lib = N.load()
+        self.ctx = ctx
+        self.handle = handle
+        self.n_contexts = int(self._lib.fm_lists_contexts(handle))
+        self.n_candidates = int(self._lib.fm_lists_candidates(handle))
+        self.total = int(self._lib.fm_lists_total(handle))
+        self.longest = int(self._lib.fm_lists_longest(handle))
+
+    def export(self):
+        """(ptr int64 [n_contexts + 1], rows int32 [total]) read back from the device (fm_lists_export)."""
+        ptr = np.zeros(self.n_contexts + 1, dtype=np.int64)
+        rows = np.zeros(max(self.total, 1), dtype=np.int32)
+        N.check(self._lib.fm_lists_export(self.ctx.handle, self.handle, N.ptr(ptr, C.c_int64), N.ptr(rows, C.c_int32),
+                                          len(rows)), "fm_lists_export")
+        return ptr, rows[: self.total]
+
+    def close(self):
+        if self.handle:
+            self._lib.fm_lists_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def comm_unique_id() -> bytes:
     """RCCL unique id (128 bytes) that process 0 of a multi-process job hands to the others
     (fm_comm_unique_id)."""
@@ -341,6 +375,38 @@ class FMContext:
         b = into if into is not None else DeviceBatch(self, None)
         return b.select_rows(data, rows)
 
+    def row_lists(self, lists, n_candidates: int) -> RowLists:
+        """``lists`` (what normalize_row_lists accepts: one integer sequence per context, or a CSR pair; or
+        an already normalised (ptr, rows)) over n_candidates candidate rows, made resident (fm_lists_create)."""
+        if isinstance(lists, RowLists):
+            raise ValueError("lists is a RowLists already")
+        if (isinstance(lists, tuple) and len(lists) == 2 and all(isinstance(a, np.ndarray) and a.ndim == 1 for a in lists)
+                and lists[0].dtype.kind in "iu" and len(lists[0]) >= 1):
+            n_ctx = len(lists[0]) - 1
+        else:
+            n_ctx = len(lists)
+        return self._row_lists(normalize_row_lists(lists, n_ctx), n_candidates)
+
+    def _row_lists(self, normalised, n_candidates: int) -> RowLists:
+        """row_lists with the lists already normalised: (ptr, rows) as normalize_row_lists returns them."""
+        ptr, rows = normalised
+        h = C.c_void_p()
+        N.check(self._lib.fm_lists_create(self.handle, len(ptr) - 1, int(n_candidates), N.ptr(ptr, C.c_int64),
+                                          N.ptr(rows, C.c_int32), C.byref(h)), "fm_lists_create")
+        return RowLists(self, h)
+
+    def row_lists_from_pairs(self, pair_ctx, pair_cand, n_contexts: int, n_candidates: int) -> RowLists:
+        """The lists the pairs spell out, built on the device (fm_lists_from_pairs): context u's list is the
+        distinct pair_cand[i] with pair_ctx[i] == u, ascending; pairs in any order, repeats allowed."""
+        pc = np.ascontiguousarray(pair_ctx, dtype=np.int32)
+        pd = np.ascontiguousarray(pair_cand, dtype=np.int32)
+        if not (pc.ndim == pd.ndim == 1 and len(pc) == len(pd)):
+            raise ValueError("pair_ctx and pair_cand must be flat and of one length")
+        h = C.c_void_p()
+        N.check(self._lib.fm_lists_from_pairs(self.handle, int(n_contexts), int(n_candidates), N.ptr(pc, C.c_int32),
+                                              N.ptr(pd, C.c_int32), len(pc), C.byref(h)), "fm_lists_from_pairs")
+        return RowLists(self, h)
+
     def batch_from_pairs(self, contexts: DeviceBatch, candidates: DeviceBatch, pair_ctx, pair_cand, labels,
                          into: DeviceBatch | None = None) -> DeviceBatch:
         """The mini-batch whose row i is row pair_ctx[i] of `contexts` followed by row pair_cand[i] of
@@ -365,14 +431,19 @@ class FMContext:
         n_neg negatives drawn on the device uniformly over the candidate rows its context's ``exclude``
         list does not hold (fm_batch_sample_pairs; the lists as rank(exclude=) takes them).  Returns the
         batch, or (batch, sampled [n_pos, n_neg] int32 candidate rows) with want_sampled."""
-        ex = (None, None) if exclude is None else normalize_row_lists(exclude, contexts.n_rows)
+        if exclude is None:
+            ex = (None, None)
+        elif isinstance(exclude, RowLists):
+            ex = exclude
+        else:
+            ex = normalize_row_lists(exclude, contexts.n_rows)
         return self._sample_pairs(contexts, candidates, pos_ctx, pos_cand, n_neg, ex, pos_label, neg_label, seed, into,
                                   want_sampled)
 
     def _sample_pairs(self, contexts, candidates, pos_ctx, pos_cand, n_neg, ex, pos_label, neg_label, seed, into,
                       want_sampled):
-        """batch_sample_pairs with the exclude lists already normalised: ex = (ptr, rows) or (None, None)
-        (a loop normalises its lists once)."""
+        """batch_sample_pairs with the exclude lists already normalised: ex = (ptr, rows), (None, None) or a
+        RowLists (fm_batch_sample_pairs_lists) -- a loop normalises its lists once, or makes them resident."""
         pc = np.ascontiguousarray(pos_ctx, dtype=np.int32)
         pd = np.ascontiguousarray(pos_cand, dtype=np.int32)
         if not (pc.ndim == pd.ndim == 1 and len(pc) == len(pd)):
@@ -381,11 +452,15 @@ class FMContext:
         sampled = np.zeros(max(len(pc) * max(n_neg, 0), 1), dtype=np.int32) if want_sampled else None
         b = into if into is not None else DeviceBatch(self, None)
         h = b.handle if b.handle else C.c_void_p()
-        N.check(self._lib.fm_batch_sample_pairs(
-            self.handle, contexts.handle, candidates.handle, N.ptr(pc, C.c_int32), N.ptr(pd, C.c_int32), len(pc), n_neg,
-            None if ex[0] is None else N.ptr(ex[0], C.c_int64), None if ex[1] is None else N.ptr(ex[1], C.c_int32),
-            float(pos_label), float(neg_label), int(seed) & (2**64 - 1), C.byref(h),
-            N.ptr(sampled, C.c_int32) if want_sampled else None), "fm_batch_sample_pairs")
+        head = (self.handle, contexts.handle, candidates.handle, N.ptr(pc, C.c_int32), N.ptr(pd, C.c_int32), len(pc), n_neg)
+        tail = (float(pos_label), float(neg_label), int(seed) & (2**64 - 1), C.byref(h),
+                N.ptr(sampled, C.c_int32) if want_sampled else None)
+        if isinstance(ex, RowLists):
+            N.check(self._lib.fm_batch_sample_pairs_lists(*head, ex.handle, *tail), "fm_batch_sample_pairs_lists")
+        else:
+            N.check(self._lib.fm_batch_sample_pairs(
+                *head, None if ex[0] is None else N.ptr(ex[0], C.c_int64),
+                None if ex[1] is None else N.ptr(ex[1], C.c_int32), *tail), "fm_batch_sample_pairs")
         self._pair_batch(b, h, contexts, candidates)
         return (b, sampled[: len(pc) * n_neg].reshape(len(pc), n_neg)) if want_sampled else b
 
@@ -503,13 +578,19 @@ class FMContext:
 
     def rank_batch(self, contexts: DeviceBatch, candidates: DeviceBatch, n_top: int, min_label: float,
                    max_label: float, *, only=None, exclude=None):
-        """rank over device-resident batches of this context (fm_rank_batch / fm_rank_batch_select)."""
+        """rank over device-resident batches of this context (fm_rank_batch / fm_rank_batch_select); only /
+        exclude may be a RowLists of this context (fm_rank_batch_select_lists)."""
         return self._rank(self._lib.fm_rank_batch, self._lib.fm_rank_batch_select, "fm_rank_batch", contexts.handle,
-                          candidates.handle, contexts.n_rows, n_top, min_label, max_label, only, exclude)
+                          candidates.handle, contexts.n_rows, n_top, min_label, max_label, only, exclude,
+                          self._lib.fm_rank_batch_select_lists)
 
-    def _rank(self, fn, fn_select, what, contexts, candidates, n_ctx, n_top, min_label, max_label, only, exclude):
+    def _rank(self, fn, fn_select, what, contexts, candidates, n_ctx, n_top, min_label, max_label, only, exclude,
+              fn_lists=None):
         if only is not None and exclude is not None:
             raise ValueError("give only= or exclude=, not both")
+        given = exclude if only is None else only
+        if isinstance(given, RowLists) and fn_lists is None:
+            raise ValueError("a RowLists goes with resident batches (rank_batch); rank takes host lists")
         n_top = int(n_top)
         n = max(n_ctx * max(n_top, 0), 1)
         idx = np.zeros(n, dtype=np.int32)
@@ -517,8 +598,11 @@ class FMContext:
         out = (n_top, float(min_label), float(max_label), N.ptr(idx, C.c_int32), N.ptr(score, C.c_double))
         if only is None and exclude is None:
             N.check(fn(self.handle, contexts, candidates, *out), what)
+        elif isinstance(given, RowLists):
+            mode = N.FM_RANK_SELECT_EXCEPT if only is None else N.FM_RANK_SELECT_ONLY
+            N.check(fn_lists(self.handle, contexts, candidates, mode, given.handle, *out), what + "_select_lists")
         else:
-            ptr, rows = normalize_row_lists(exclude if only is None else only, n_ctx)
+            ptr, rows = normalize_row_lists(given, n_ctx)
             mode = N.FM_RANK_SELECT_EXCEPT if only is None else N.FM_RANK_SELECT_ONLY
             N.check(fn_select(self.handle, contexts, candidates, mode, N.ptr(ptr, C.c_int64), N.ptr(rows, C.c_int32), *out),
                     what + "_select")
@@ -541,11 +625,42 @@ class FMContext:
 
     def rank_positions_batch(self, contexts: DeviceBatch, candidates: DeviceBatch, targets, min_label: float,
                              max_label: float, *, exclude=None):
-        """rank_positions over device-resident batches of this context (fm_rank_positions_batch)."""
-        return self._rank_positions(self._lib.fm_rank_positions_batch, "fm_rank_positions_batch", contexts.handle,
-                                    candidates.handle, contexts.n_rows, targets, min_label, max_label, exclude)
+        """rank_positions over device-resident batches of this context (fm_rank_positions_batch).  targets /
+        exclude may be RowLists of this context (fm_rank_positions_batch_lists): resident targets come back
+        as their exported (ptr, rows); where only one of the two is resident the other is made resident for
+        the call."""
+        if not isinstance(targets, RowLists) and not isinstance(exclude, RowLists):
+            return self._rank_positions(self._lib.fm_rank_positions_batch, "fm_rank_positions_batch", contexts.handle,
+                                        candidates.handle, contexts.n_rows, targets, min_label, max_label, exclude)
+        if targets is None:
+            raise ValueError("targets: one list of candidate rows per context")
+        made = []
+        try:
+            tgt, ex = targets, exclude
+            if not isinstance(tgt, RowLists):
+                ptr, rows = normalize_row_lists(tgt, contexts.n_rows)
+                tgt = self._row_lists((ptr, rows), candidates.n_rows)
+                made.append(tgt)
+            else:
+                ptr, rows = tgt.export()
+            if ex is not None and not isinstance(ex, RowLists):
+                ex = self._row_lists(normalize_row_lists(ex, contexts.n_rows), candidates.n_rows)
+                made.append(ex)
+            n = max(len(rows), 1)
+            position = np.zeros(n, dtype=np.int32)
+            score = np.zeros(n)
+            N.check(self._lib.fm_rank_positions_batch_lists(
+                self.handle, contexts.handle, candidates.handle, tgt.handle, None if ex is None else ex.handle,
+                float(min_label), float(max_label), N.ptr(position, C.c_int32), N.ptr(score, C.c_double)),
+                "fm_rank_positions_batch_lists")
+            return ptr, rows, position[: len(rows)], score[: len(rows)]
+        finally:
+            for l in made:
+                l.close()
 
     def _rank_positions(self, fn, what, contexts, candidates, n_ctx, targets, min_label, max_label, exclude):
+        if isinstance(targets, RowLists) or isinstance(exclude, RowLists):
+            raise ValueError("a RowLists goes with resident batches (rank_positions_batch); rank_positions takes host lists")
         if targets is None:
             raise ValueError("targets: one list of candidate rows per context")
         ptr, rows = normalize_row_lists(targets, n_ctx)

@@ -564,8 +564,9 @@ class FactorizationMachinesSGD:
         entries followed by a candidate row's, the row recommend and rankPositions score; positives are
         labelled 1.0 and each gets negativesPerPositive negatives labelled 0.0, drawn on the device
         uniformly over the candidate rows not on its context's ``exclude`` list (default: the context's
-        interacted rows).  Both frames go to the device once and every mini-batch is assembled there
-        (fm_batch_sample_pairs): with n interactions, m = max(1, round(miniBatchFraction * n)) and perm =
+        interacted rows, built on the device from the interactions: fm_lists_from_pairs).  Both frames and
+        the lists go to the device once and every mini-batch is assembled there
+        (fm_batch_sample_pairs_lists): with n interactions, m = max(1, round(miniBatchFraction * n)) and perm =
         default_rng(seed).permutation(n), iteration t = 1 .. maxIter takes the positives
         perm[((t - 1) * m + arange(m)) % n] in that order with the draw seed splitmix64(seed) ^ t, into
         one of two batches in turn, sorted on the side stream while the previous iteration steps; the
@@ -592,14 +593,19 @@ class FactorizationMachinesSGD:
         n_ctx, n_cand, n = contexts.count(), candidates.count(), len(pos_ctx)
         if n and not (0 <= pos_ctx.min() and pos_ctx.max() < n_ctx and 0 <= pos_cand.min() and pos_cand.max() < n_cand):
             raise ValueError("interactions name a row outside contexts / candidates")
-        if exclude is None:
-            exclude = [np.unique(pos_cand[pos_ctx == u]) for u in range(n_ctx)]
-        ex = normalize_row_lists(exclude, n_ctx)
+        if exclude is not None:
+            exclude = normalize_row_lists(exclude, n_ctx)
         rows = [_explode(df[fcol]) for df in (contexts, candidates)]
         k = p["dimFactorization"]
         top = max([int(col.max()) + 1 for _, col, _ in rows if len(col)], default=1)
         ctx = FMContext(p["numFeatures"] or top, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0)
         bu, bc = (ctx.batch(N.CSRHost(rp, col, val, np.zeros(len(rp) - 1))) for rp, col, val in rows)
+        # the exclude lists, resident for the whole loop: the given ones (normalised above, once), else what
+        # the interactions say each context has seen, built on the device from the pairs themselves
+        if exclude is not None:
+            ex = ctx._row_lists(exclude, n_cand)
+        else:
+            ex = ctx.row_lists_from_pairs(pos_ctx, pos_cand, n_ctx, n_cand)
         if initial_tables is not None:
             ctx.load_tables(*initial_tables)
         else:
@@ -629,7 +635,7 @@ class FactorizationMachinesSGD:
                 sample(t + 1)  # drawn, gathered and sorted while step t runs (the batch step t - 1 read)
         ctx.sync()
         _log_losses(ctx, e0, work, n_iter, n_iter)
-        for b in (*bufs, bu, bc):
+        for b in (*bufs, bu, bc, ex):
             if b is not None:
                 b.close()
         model = FactorizationMachinesModel(self.uid, k, 0.0, ctx=ctx)

@@ -55,6 +55,7 @@ extern "C" {
 
 typedef struct fm_ctx fm_ctx;
 typedef struct fm_batch fm_batch;
+typedef struct fm_lists fm_lists;
 
 /* Model hyper-parameters fixed at creation.
  * num_features : feature ids are int32 in [0, num_features) (README.md:7 "<= Int.MaxValue").
@@ -177,7 +178,10 @@ int fm_sync(fm_ctx* ctx);
  * scratch of fm_rank_positions / fm_rank_positions_batch: the same row summaries, the device copies of
  * its target and exclude lists and its results, 12 bytes per target; nor the scratch of
  * fm_batch_sample_pairs: the device copies of its lists, the drawn pairs with their labels, lengths and
- * row_ptr (28 bytes per result row) and the scan's per-chunk sums, sized by the largest call. */
+ * row_ptr (28 bytes per result row) and the scan's per-chunk sums, sized by the largest call.  The
+ * _lists forms of these calls (fm_rank_batch_select_lists, fm_rank_positions_batch_lists,
+ * fm_batch_sample_pairs_lists) keep no list copies in the context's scratch: they read the fm_lists'
+ * own buffers, and the rest of their scratch is the host-list forms'. */
 int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz);
 
 /* ---- tables (C9: Strength / FactorizedInteraction, Model.scala:275-289) ------------ */
@@ -523,6 +527,67 @@ int fm_rank_positions(fm_ctx* ctx, const fm_csr* contexts, const fm_csr* candida
 int fm_rank_positions_batch(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, const int64_t* tgt_ptr,
                             const int32_t* tgt_rows, const int64_t* excl_ptr, const int32_t* excl_rows,
                             double min_label, double max_label, int32_t* position, double* score);
+/* ---- resident row lists --------------------------------------------------------------------
+ * The per-context candidate-row lists that fm_rank_batch_select (sel), fm_rank_positions_batch (tgt, excl)
+ * and fm_batch_sample_pairs (excl) take, kept on the device: built once, read by every later call.  The
+ * host-list forms check, stage and upload their lists at every call (a training loop hands over every
+ * context's exclude list at every mini-batch); the _lists forms below take an fm_lists instead and do no
+ * host check, staging or upload of list rows.
+ * An fm_lists holds U lists over C candidate rows: device int64 ptr[U + 1] and int32 rows[ptr[U]], each list
+ * strictly ascending and in [0, C), with a host copy of ptr and the longest list's length.  It belongs to
+ * the context that made it, is read-only afterwards, and counts in fm_device_bytes_live /
+ * fm_device_allocs_live with its two buffers.  0 <= U, C < 2^31.  A multi-GPU context refuses both
+ * constructors (FM_ERR_ARG), as it refuses the batch forms of the calls that read the lists.
+ *   fm_lists_create : from host arrays under fm_rank_candidates_select's list rules, checked in one pass
+ *           with the same messages behind "row lists: " and the argument names ptr / rows.  Synchronous; a
+ *           refused call allocates nothing that stays and leaves *out as it was.
+ *   fm_lists_from_pairs : from n (context, candidate) pairs, on the device: context u's list is the distinct
+ *           pair_cand[i] with pair_ctx[i] == u, ascending -- what a training loop's interactions say each
+ *           context has seen.  Pairs come in any order and may repeat; a context without a pair gets an
+ *           empty list; n = 0 gives U empty lists; n < 2^31.  An index outside [0, U) / [0, C) is FM_ERR_ARG
+ *           ("pair_ctx index out of [0, U = ...)", "pair_cand index out of [0, C = ...)"), checked on the pool
+ *           of host threads before anything is enqueued.  Two stable radix sorts (by candidate, then by
+ *           context), head flags of the runs of equal pairs, their scan, one binary search per offset and a
+ *           compaction: integer work, no atomics, so equal inputs -- in any order -- give equal bytes.
+ *           Synchronous, on the main stream behind every queued step; it reads ptr back once (the host copy,
+ *           the longest list, and the size of rows).  Its scratch (the pairs' upload, the sorts' buffers, the
+ *           flags, the scan's arrays) is the call's own and freed before it returns: afterwards the live bytes
+ *           have grown by the object's two buffers and nothing else.
+ *   fm_lists_destroy : frees at once.  Every consumer below has finished reading the lists when it returns:
+ *           the rank calls are synchronous, and fm_batch_sample_pairs_lists waits for its draw on the copy
+ *           stream -- the gather it leaves queued reads the drawn pairs, not the lists.  A later consumer that
+ *           leaves a read of the lists queued must add an event for this call to wait for.  Lists may outlive
+ *           their context; no call takes them after that except this one.
+ *   fm_lists_contexts / _candidates / _total / _longest : U, C, ptr[U] and the longest list (-1 for NULL).
+ *   fm_lists_export : the device arrays back on the host: ptr [U + 1] and rows [fm_lists_total], either may
+ *           be NULL; cap_rows (the capacity of rows) below the total is FM_ERR_ARG.  Synchronous. */
+int fm_lists_create(fm_ctx* ctx, int64_t U, int64_t C, const int64_t* ptr, const int32_t* rows, fm_lists** out);
+int fm_lists_from_pairs(fm_ctx* ctx, int64_t U, int64_t C, const int32_t* pair_ctx, const int32_t* pair_cand,
+                        int64_t n, fm_lists** out);
+void fm_lists_destroy(fm_lists* lists);
+int64_t fm_lists_contexts(const fm_lists* lists);
+int64_t fm_lists_candidates(const fm_lists* lists);
+int64_t fm_lists_total(const fm_lists* lists);
+int64_t fm_lists_longest(const fm_lists* lists);
+int fm_lists_export(fm_ctx* ctx, const fm_lists* lists, int64_t* ptr, int32_t* rows, int64_t cap_rows);
+/* fm_rank_batch_select, fm_rank_positions_batch and fm_batch_sample_pairs with their lists resident: the
+ * same paths, the device pointers taken from the objects instead of from an upload, so the results are
+ * the host-list calls' with the same lists, bit for bit (-1 / NaN slots, excluded targets, sampled and
+ * the batch's device arrays included).  sel may be NULL with FM_RANK_SELECT_ALL only; tgt must not be
+ * NULL; excl == NULL excludes nothing (the host calls' excl_ptr == NULL).  FM_ERR_ARG, each with a message
+ * that names the mismatch: lists of another context, lists whose U or C differ from the batches' row
+ * counts.  The sampled call's E >= 1 rule reads the object's host copy of ptr.  Everything else -- arguments,
+ * order, synchronisation, refusals, U = 0, no target -- as the host-list call. */
+int fm_rank_batch_select_lists(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, int32_t select,
+                               const fm_lists* sel, int32_t n_top, double min_label, double max_label,
+                               int32_t* top_index, double* top_score);
+int fm_rank_positions_batch_lists(fm_ctx* ctx, fm_batch* contexts, fm_batch* candidates, const fm_lists* tgt,
+                                  const fm_lists* excl, double min_label, double max_label, int32_t* position,
+                                  double* score);
+int fm_batch_sample_pairs_lists(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates,
+                                const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
+                                const fm_lists* excl, double pos_label, double neg_label, uint64_t seed,
+                                fm_batch** out, int32_t* sampled);
 /* calcLossGrad (Model.scala:135-234), per active entry e in CSR order:
  * pred[e] = yhat of its row (unclamped), loss[e] = (yhat - y)^2, delta_w[e] = x,
  * delta_v[e*k + f] = vfxiSum_f * x - (v_f * x) * x.  Any output may be NULL.

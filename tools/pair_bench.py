@@ -8,7 +8,11 @@ Shape: c5's table (1M features, k = 16); 65 536 context rows of about 20 entries
       library's profile), and the call through ctx.sync() by the host clock;
   (b) the route it replaces: a NumPy draw + concatenation + fm_batch_create of the same rows, host clock;
   (c) ms per iteration of the pipelined loop (sample, prepare, step; two batches in turn) against the same
-      loop over split views of a resident dataset of the same rows -- the fit's own fastest path.
+      loop over split views of a resident dataset of the same rows -- the fit's own fastest path -- with the
+      exclude lists as host arrays at every call, resident (a RowLists made once), and absent;
+  (d) building those lists on the device from their 13.1M (context, row) pairs (fm_lists_from_pairs), by HIP
+      events (the sorts through the compaction) and through the call by the host clock, beside a vectorised
+      NumPy build (lexsort + unique + bincount) of the same lists.
 
 Runs on the GPU only: without one the context constructor raises.  Writes profiles/pairs/pair_bench.json.
   python tools/pair_bench.py [iters] [reps]"""
@@ -55,9 +59,14 @@ res = {"shape": {"features": F, "k": k, "contexts": U, "candidates": C, "exclude
                  "negatives_per_positive": N_NEG, "rows_per_batch": N_POS * (1 + N_NEG)}, "iters": iters, "reps": reps}
 
 
+resident = ctx._row_lists(ex, C)  # (ex is normalised as built)
+
+
 def sample(j, into, lists=True):
+    """lists: True -- the host arrays at every call; "resident" -- the RowLists; False -- none"""
     pc, pd = pos[j % N_SETS]
-    return ctx._sample_pairs(bu, bc, pc, pd, N_NEG, ex if lists else (None, None), 1.0, 0.0, j, into, False)
+    given = resident if lists == "resident" else ex if lists else (None, None)
+    return ctx._sample_pairs(bu, bc, pc, pd, N_NEG, given, 1.0, 0.0, j, into, False)
 
 
 def host_rows(j):
@@ -172,18 +181,20 @@ pb, vb = [None, None], [None, None]
 loop_pairs(pb)  # warm-up: both loops' buffers grown
 loop_views(vb)
 loop_pairs(pb, lists=False)
-pairs_ms, views_ms, free_ms = [], [], []
+loop_pairs(pb, lists="resident")
+pairs_ms, views_ms, free_ms, resident_ms = [], [], [], []
 for _ in range(reps):  # alternating
     pairs_ms.append(loop_pairs(pb))
+    resident_ms.append(loop_pairs(pb, lists="resident"))
     views_ms.append(loop_views(vb))
     free_ms.append(loop_pairs(pb, lists=False))
 # where the pair loop's host time goes: the sample call alone on an idle device, with the exclude lists (13.1M
 # rows checked, staged and uploaded by every call) and without them (excl_ptr = NULL)
-t_call, t_free = [], []
-for t in range(1, 17):
+t_call, t_free, t_res = [], [], []
+for t in range(1, 25):
     t0 = time.perf_counter()
-    pb[t % 2] = sample(t, pb[t % 2], lists=t % 2 == 0)
-    (t_call if t % 2 == 0 else t_free).append(1e3 * (time.perf_counter() - t0))
+    pb[t % 2] = sample(t, pb[t % 2], lists=(True, False, "resident")[t % 3])
+    (t_call, t_free, t_res)[t % 3].append(1e3 * (time.perf_counter() - t0))
     ctx.sync()
 res["c_pipelined_loop"] = {
     "pairs_ms_per_iter": spread(pairs_ms), "split_views_ms_per_iter": spread(views_ms),
@@ -192,6 +203,53 @@ res["c_pipelined_loop"] = {
     "ratio_without_exclude_lists": float(np.median(free_ms) / np.median(views_ms)),
     "sample_call_host_ms_idle_device": spread(t_call),
     "sample_call_without_exclude_lists_host_ms_idle_device": spread(t_free),
+    # the same loop with the lists resident (fm_batch_sample_pairs_lists): no check, staging or upload per call
+    "pairs_resident_lists_ms_per_iter": spread(resident_ms),
+    "ratio_resident_to_host_lists": float(np.median(resident_ms) / np.median(pairs_ms)),
+    "ratio_resident_to_without_exclude_lists": float(np.median(resident_ms) / np.median(free_ms)),
+    "ratio_resident_to_split_views": float(np.median(resident_ms) / np.median(views_ms)),
+    "sample_call_resident_lists_host_ms_idle_device": spread(t_res),
+}
+
+
+# ---- (d) the lists built on the device from their pairs, beside a vectorised NumPy build
+def numpy_lists(pc, pd, n_ctx):
+    order = np.lexsort((pd, pc))
+    sc, sd = pc[order], pd[order]
+    head = np.ones(len(sc), dtype=bool)
+    head[1:] = (sc[1:] != sc[:-1]) | (sd[1:] != sd[:-1])
+    ptr = np.zeros(n_ctx + 1, dtype=np.int64)
+    np.cumsum(np.bincount(sc[head], minlength=n_ctx), out=ptr[1:])
+    return ptr, sd[head].astype(np.int32)
+
+
+shuffle = rng.permutation(U * N_EXCL)  # the lists' own pairs, in no order
+lp_ctx = np.repeat(np.arange(U, dtype=np.int32), N_EXCL)[shuffle]
+lp_cand = ex[1][shuffle]
+ctx.row_lists_from_pairs(lp_ctx, lp_cand, U, C).close()  # warm-up
+ctx.profile_enable(True)
+ctx.profile_reset()
+build_ms = []
+for _ in range(reps):
+    t0 = time.perf_counter()
+    built = ctx.row_lists_from_pairs(lp_ctx, lp_cand, U, C)
+    build_ms.append(1e3 * (time.perf_counter() - t0))
+    got = built.export()
+    built.close()
+prof = ctx.profile_read()
+ctx.profile_enable(False)
+assert got[0].tobytes() == ex[0].tobytes() and got[1].tobytes() == ex[1].tobytes()  # the lists the loops used
+numpy_ms = []
+for _ in range(2):
+    t0 = time.perf_counter()
+    want = numpy_lists(lp_ctx, lp_cand, U)
+    numpy_ms.append(1e3 * (time.perf_counter() - t0))
+assert want[0].tobytes() == ex[0].tobytes() and want[1].tobytes() == ex[1].tobytes()
+res["d_lists_from_pairs"] = {
+    "pairs": int(U * N_EXCL), "list_rows": int(ex[0][-1]),
+    "device_ms_hip_events": prof["lists_build"][0] / prof["lists_build"][1],
+    "call_ms_host_clock": spread(build_ms),
+    "numpy_lexsort_unique_bincount_ms_host_clock": spread(numpy_ms),
 }
 out = os.path.join(ROOT, "profiles", "pairs")
 os.makedirs(out, exist_ok=True)
