@@ -21,6 +21,7 @@ FM_TRANSPORT_AUTO, FM_TRANSPORT_RCCL, FM_TRANSPORT_COPY = 0, 1, 2
 FM_MAX_LOCAL = 16
 FM_FUSE_DEFAULT, FM_FUSE_ON, FM_FUSE_OFF = 0, 1, -1
 FM_WIRE_FP32, FM_WIRE_FP64 = 0, 1
+FM_LOSS_SQUARED, FM_LOSS_LOGISTIC, FM_LOSS_BPR = 0, 1, 2
 FM_RANK_MAX_TOP = 1024
 FM_RANK_SELECT_ALL, FM_RANK_SELECT_ONLY, FM_RANK_SELECT_EXCEPT = 0, 1, 2
 
@@ -49,6 +50,7 @@ class fm_config(C.Structure):
         ("fuse_single", C.c_int32),
         ("xchg_chunks", C.c_int32),
         ("wire", C.c_int32),
+        ("loss", C.c_int32),
     ]
 
 
@@ -117,6 +119,8 @@ SIGNATURES = {
     "fm_fuse_active": (C.c_int32, [_P]),
     "fm_batch_rows": (C.c_int64, [_P]),
     "fm_batch_nnz": (C.c_int64, [_P]),
+    "fm_batch_set_group": (C.c_int, [_P, _P, C.c_int32]),
+    "fm_batch_group": (C.c_int32, [_P]),
     "fm_step": (C.c_int, [_P, C.POINTER(fm_csr), C.c_int32, C.c_double, C.c_double, C.POINTER(fm_step_out)]),
     "fm_step_batch": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.POINTER(fm_step_out)]),
     "fm_loss_history": (C.c_int, [_P, _DP, C.c_int64, _I64P]),

@@ -236,9 +236,21 @@ static Staged stage_csr(fm_ctx* ctx, const fm_csr* c, bool check_range, Pinned& 
 // cache-resident table re-reads them on-die, and the split and tags would cost more than they save
 // (c2 / c5: 0.245 / 0.273 ms per step fused against 0.184 / 0.208 unfused, profiles/r03_v1).
 bool fuse_rule(const fm_ctx* ctx) {
+  // the fused forward applies the singleton rows with the squared residual, before the objective stage
+  // (fm_objective.hip) has replaced it: another loss never fuses
+  if (ctx->cfg.loss != FM_LOSS_SQUARED) return false;
   if (ctx->cfg.fuse_single == FM_FUSE_OFF || ctx->kp > 16) return false;
   const double table_bytes = (double)ctx->rows * ctx->stride * sizeof(float);
   return ctx->cfg.fuse_single == FM_FUSE_ON || table_bytes > 256.0 * 1024 * 1024;
+}
+
+static const char* loss_name(int32_t loss) {
+  return loss == FM_LOSS_LOGISTIC ? "FM_LOSS_LOGISTIC" : loss == FM_LOSS_BPR ? "FM_LOSS_BPR" : "FM_LOSS_SQUARED";
+}
+
+void require_squared(const fm_ctx* ctx, const char* call) {
+  FM_REQUIRE(ctx->cfg.loss == FM_LOSS_SQUARED, std::string(call) + " runs the squared step only: this context's loss is " +
+                                                   loss_name(ctx->cfg.loss));
 }
 
 static bool fuse_on(const fm_ctx* ctx) { return ctx->cfg.shard_count == 1 && fuse_rule(ctx); }
@@ -348,6 +360,9 @@ int step_impl(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_
   FM_REQUIRE(b->owner == ctx, "batch belongs to another context");
   FM_REQUIRE(ctx->cfg.shard_count == 1, "sharded contexts step through the fm_shard_* entry points");
   FM_REQUIRE(b->split_rows.empty(), "a dataset made by fm_batch_create_splits is stepped through its split views");
+  const int32_t loss = ctx->cfg.loss;
+  FM_REQUIRE(loss != FM_LOSS_BPR || (b->row_group >= 2 && b->dev.n_rows % b->row_group == 0),
+             "an FM_LOSS_BPR step needs a grouped batch: fm_batch_sample_pairs with n_neg >= 1, or fm_batch_set_group");
   if (emit) FM_HIP_CHECK(hipMemsetAsync(emit, 0, sizeof(float) * (size_t)ctx->rows * (ctx->kp + 4), ctx->stream));
   if (b->dev.n_rows == 0) return FM_NOTHING_TO_DO;  // SGD.scala:126-128
   FM_REQUIRE(t >= 1, "iteration index t must be >= 1");
@@ -406,6 +421,14 @@ int step_impl(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_
   e0 = ctx->prof_begin(ctx->stream);
   launch_forward(T, b->dev, ctx->work, p, ctx->stream, &nfwd, nullptr, fused ? &fx : nullptr);
   ctx->prof_end("forward", e0, ctx->stream);
+  if (loss != FM_LOSS_SQUARED) {
+    // the objective stage: {r, yhat} -> {r, r} with the loss's own r, and its loss partials in place of
+    // the forward's (a squared context launches nothing here)
+    FM_REQUIRE(!fused && !emit, "the fused and the replicated step are the squared loss's");
+    e0 = ctx->prof_begin(ctx->stream);
+    nfwd = launch_objective(loss, b->row_group, ctx->kp, b->dev, ctx->work, ctx->stream);
+    ctx->prof_end("objective", e0, ctx->stream);
+  }
   // (the prepared batch's wait moved before the forward, where its sort has long finished, measured
   // 0.170-0.173 against 0.167-0.168 ms at c2 and 0.191-0.192 against 0.187-0.190 at c5, three
   // alternating reps, profiles/r05_h/ab: not taken)
@@ -449,6 +472,17 @@ int64_t fm_device_allocs_live(void) { return g_dev_allocs_live.load(std::memory_
 int fm_create(const fm_config* cfg, fm_ctx** out) {
   return guarded_free([&]() -> int {
     FM_REQUIRE(cfg && out, "null argument");
+    FM_REQUIRE(cfg->loss == FM_LOSS_SQUARED || cfg->loss == FM_LOSS_LOGISTIC || cfg->loss == FM_LOSS_BPR,
+               "loss must be FM_LOSS_SQUARED, FM_LOSS_LOGISTIC or FM_LOSS_BPR");
+    if (cfg->loss != FM_LOSS_SQUARED) {
+      const std::string nm = loss_name(cfg->loss);
+      FM_REQUIRE(cfg->parallel == FM_PARALLEL_NONE,
+                 "loss = " + nm + " needs parallel == FM_PARALLEL_NONE: multi-GPU objectives are not built yet");
+      FM_REQUIRE(cfg->shard_count == 1, "loss = " + nm + " needs shard_count == 1: multi-GPU objectives are not built yet");
+      FM_REQUIRE(cfg->fuse_single != FM_FUSE_ON,
+                 "loss = " + nm + " cannot take fuse_single = FM_FUSE_ON: the fused forward applies singleton rows with the "
+                 "squared residual");
+    }
     FM_REQUIRE(cfg->wire == FM_WIRE_FP32 || cfg->wire == FM_WIRE_FP64, "wire must be FM_WIRE_FP32 or FM_WIRE_FP64");
     FM_REQUIRE(cfg->wire != FM_WIRE_FP64 || cfg->parallel != FM_PARALLEL_REPLICATED,
                "wire = FM_WIRE_FP64 applies to the sharded step only: the replicated gradient all-reduce is fp32");
@@ -803,6 +837,7 @@ int fm_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows, i
     FM_HIP_CHECK(hipEventRecord(b->built, gs));
     b->prepared = false;  // a refilled batch is sorted again by its own fm_batch_prepare
     b->host_rp.clear();   // a selection is not itself a dataset (fm_batch_create's batches are)
+    b->row_group = 0;
     res.commit();
     return FM_OK;
   });
@@ -910,6 +945,7 @@ int fm_batch_split_view(fm_ctx* ctx, const fm_batch* data, int32_t split, fm_bat
     b->max_id = data->max_id;
     b->prepared = false;
     b->host_rp.clear();
+    b->row_group = 0;
     res.commit();
     return FM_OK;
   });
@@ -925,6 +961,20 @@ int32_t fm_fuse_active(fm_ctx* ctx) {
 
 int64_t fm_batch_rows(const fm_batch* b) { return b ? b->dev.n_rows : -1; }
 int64_t fm_batch_nnz(const fm_batch* b) { return b ? b->dev.nnz : -1; }
+int32_t fm_batch_group(const fm_batch* b) { return b ? b->row_group : -1; }
+
+int fm_batch_set_group(fm_ctx* ctx, fm_batch* b, int32_t group) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(b != nullptr && b->owner == ctx, "batch belongs to another context");
+    FM_REQUIRE(!ctx->group && !b->grp, "fm_batch_set_group: a multi-GPU context's batches are cut over its ranks");
+    FM_REQUIRE(b->split_rows.empty(), "fm_batch_set_group: a dataset made by fm_batch_create_splits is not grouped");
+    FM_REQUIRE(group == 0 || (group >= 2 && group <= 1025), "group must be 0 or in [2, 1025], got " + std::to_string(group));
+    FM_REQUIRE(group == 0 || b->dev.n_rows % group == 0,
+               "group " + std::to_string(group) + " does not divide the batch's " + std::to_string(b->dev.n_rows) + " rows");
+    b->row_group = group;
+    return FM_OK;
+  });
+}
 
 int fm_step_batch(fm_ctx* ctx, fm_batch* batch, int32_t t, double step_size, double reg_param,
                   fm_step_out* out) {
@@ -937,6 +987,9 @@ int fm_step_batch(fm_ctx* ctx, fm_batch* batch, int32_t t, double step_size, dou
 int fm_step(fm_ctx* ctx, const fm_csr* csr, int32_t t, double step_size, double reg_param, fm_step_out* out) {
   return guarded(ctx, [&]() -> int {
     FM_REQUIRE(csr != nullptr, "null batch");
+    FM_REQUIRE(ctx->cfg.loss != FM_LOSS_BPR,
+               "an FM_LOSS_BPR step needs a grouped batch: a host batch carries no group (fm_batch_sample_pairs, or "
+               "fm_batch_create + fm_batch_set_group, then fm_step_batch)");
     if (csr->n_rows == 0) {
       if (out) {
         out->loss_sum = 0.0;
@@ -1693,6 +1746,7 @@ int fm_batch_from_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* c
     }
     ctx->prof_end("pair_gather", e0, gs);
     pair_refill_end(b, contexts, candidates, gs);
+    b->row_group = 0;
     res.commit();
     return FM_OK;
   });
@@ -1805,6 +1859,7 @@ static int sample_pairs_call(fm_ctx* ctx, const fm_batch* contexts, const fm_bat
       FM_HIP_CHECK(hipMemcpyAsync(b->dev.row_ptr.p, w.row_ptr.p, sizeof(int64_t), hipMemcpyDeviceToDevice, gs));
     ctx->prof_end("pair_gather", e0, gs);
     pair_refill_end(b, contexts, candidates, gs);
+    b->row_group = n_neg >= 1 ? (int32_t)per : 0;  // a positive and its negatives; none: ungrouped
     res.commit();
     return FM_OK;
   });
@@ -1987,6 +2042,7 @@ int fm_profile_read(fm_ctx* ctx, char* names, int64_t names_cap, double* total_m
 int fm_repl_grad(fm_ctx* ctx, fm_batch* batch, void* grad) {
   return guarded(ctx, [&]() -> int {
     FM_REQUIRE(!ctx->group, "a multi-GPU context runs its replicated step itself (fm_step / fm_step_batch)");
+    require_squared(ctx, "fm_repl_grad");
     FM_REQUIRE(grad != nullptr, "null gradient buffer");
     FM_REQUIRE(!ctx->repl_pending, "fm_repl_apply must follow fm_repl_grad");
     ctx->ensure_hist(ctx->epoch + 1);
@@ -2002,6 +2058,7 @@ int fm_repl_apply(fm_ctx* ctx, const void* grad, int32_t t, double step_size, do
                   int64_t global_rows) {
   return guarded(ctx, [&]() -> int {
     FM_REQUIRE(!ctx->group, "a multi-GPU context runs its replicated step itself (fm_step / fm_step_batch)");
+    require_squared(ctx, "fm_repl_apply");
     FM_REQUIRE(ctx->repl_pending, "fm_repl_grad must run first");
     FM_REQUIRE(global_rows >= 0, "negative global_rows");
     ctx->repl_pending = false;

@@ -100,6 +100,7 @@ struct fm_batch {
   int device = 0;
   BatchDev dev;
   int64_t max_id = -1;
+  int32_t row_group = 0;  // rows per (positive, negatives) group, read by the FM_LOSS_BPR step; 0 = ungrouped
   DevBuf up;  // device image of the host staging (fm_capi.hip Staged::enqueue_copies)
   // feature-major view produced by fm_batch_prepare (consumed once by the next step): the whole
   // sorted view in skeys / sents, or -- split = true, the fused step -- the whole sorted view in
@@ -463,6 +464,9 @@ inline int bits_for(int64_t max_value) {
 // the fused step's rule (fm_config.fuse_single, kp <= 16, tables above 256 MB unless FUSE_ON) for the
 // single table
 bool fuse_rule(const fm_ctx* ctx);
+// the manual multi-GPU phases (fm_shard_*, fm_repl_*) are the squared step's: FM_ERR_ARG on a context
+// with another fm_config.loss
+void require_squared(const fm_ctx* ctx, const char* call);
 // stream st waits until a batch refilled by fm_batch_from_rows has been gathered (copy stream)
 void wait_built(const fm_batch* b, hipStream_t st);
 void upload_batch(fm_ctx* ctx, const fm_csr* c, fm_batch* b, bool check_range);

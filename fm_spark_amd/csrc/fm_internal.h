@@ -191,6 +191,17 @@ struct StepWork {
   SortWork sort;
 };
 
+// where sample s's {r, yhat} lies during a single-table step: yl[s * stride], inside the S record
+// (s_rec_yl) or in StepWork::yl -- the addresses launch_forward writes and launch_segment_update reads
+struct StepYl {
+  float2* yl;
+  int64_t stride;  // in float2 elements
+};
+inline StepYl step_yl(const StepWork& w, int kp) {
+  if (s_rec_yl(kp)) return {reinterpret_cast<float2*>(w.S.as<float>() + kp), (int64_t)s_rec_floats(kp) / 2};
+  return {w.yl.as<float2>(), 1};
+}
+
 struct StepParams {
   int64_t n_rows;
   double eta;        // stepSize / sqrt(t)
@@ -283,6 +294,13 @@ struct SegSource {
 void launch_segment_update(const TableView& T, const BatchDev& b, StepWork& w, const StepParams& p,
                            const uint32_t* skeys, const uint2* sents, int64_t n_fwd_blocks,
                            double* stats_out, hipStream_t st, float* emit = nullptr, const int64_t* n_dev = nullptr);
+// The objective stage (fm_objective.hip), between launch_forward and launch_segment_update of a step
+// whose context's loss is FM_LOSS_LOGISTIC or FM_LOSS_BPR (group: the batch's rows per group, BPR only;
+// it divides b.n_rows): every sample's {r, yhat} becomes {r, r} with the objective's r, computed in fp64
+// from the stored fp32 yhat, and w.loss_part gets the stage's own per-block {loss, loss rows}.  Returns
+// the number of those partials (<= kLossPartBlocks), which launch_segment_update takes in place of the
+// forward's block count.
+int64_t launch_objective(int32_t loss, int32_t group, int kp, const BatchDev& b, StepWork& w, hipStream_t st);
 // the fused step's singleton split of a prepared sorted view, at the step (fm_update.hip; fm_device.h
 // "Singleton rows"): the entries of runs of two or more, in order, into mkeys / ments (capacity N); n_out[0] =
 // their count, n_out[1] = the number of singleton runs (device); each multi run's row in tag_T gets

@@ -680,6 +680,7 @@ extern "C" {
 
 int fm_shard_route(fm_ctx* ctx, fm_batch* b, void* send_slot, void* send_ent, int64_t* counts) {
   return guarded(ctx, [&]() -> int {
+    require_squared(ctx, "fm_shard_route");
     FM_REQUIRE(counts != nullptr, "bad arguments");
     shard_route_launch(ctx, b, send_slot, send_ent, ctx->side);
     const int R = ctx->cfg.shard_count;
@@ -791,6 +792,7 @@ extern "C" {
 int fm_shard_owner_prepare(fm_ctx* ctx, fm_batch* b, const void* recv_slot, const void* recv_ent, int64_t n,
                            const int64_t* src_entries, const int64_t* src_pairs) {
   return guarded(ctx, [&]() -> int {
+    require_squared(ctx, "fm_shard_owner_prepare");
     ShardBatchState& S = shard_state(ctx, b);
     const int R = ctx->cfg.shard_count;
     FM_REQUIRE(n >= 0 && src_entries && src_pairs, "bad arguments");
@@ -856,6 +858,7 @@ int fm_shard_owner_prepare(fm_ctx* ctx, fm_batch* b, const void* recv_slot, cons
 
 int fm_shard_owner_forward(fm_ctx* ctx, fm_batch* b, void* partials_out) {
   return guarded(ctx, [&]() -> int {
+    require_squared(ctx, "fm_shard_owner_forward");
     shard_owner_partials(ctx, b, partials_out, nullptr);
     return FM_OK;
   });
@@ -933,6 +936,7 @@ extern "C" {
 
 int fm_shard_combine(fm_ctx* ctx, fm_batch* b, const void* partials_in, void* s_send) {
   return guarded(ctx, [&]() -> int {
+    require_squared(ctx, "fm_shard_combine");
     ShardBatchState& S = shard_state(ctx, b);
     const ReqPlan q = requester_plan(ctx, b, S);
     FM_REQUIRE(q.Ps == 0 || (partials_in && s_send), "null buffer");
@@ -952,6 +956,7 @@ int fm_shard_combine(fm_ctx* ctx, fm_batch* b, const void* partials_in, void* s_
 int fm_shard_owner_update(fm_ctx* ctx, fm_batch* b, const void* s_recv, int32_t t, double step_size,
                           double reg_param, int64_t global_rows) {
   return guarded(ctx, [&]() -> int {
+    require_squared(ctx, "fm_shard_owner_update");
     ShardBatchState& S = shard_state(ctx, b);
     FM_REQUIRE(global_rows >= 0, "negative global_rows");
     if (global_rows == 0) return FM_NOTHING_TO_DO;  // SGD.scala:126-128 (every rank skips)

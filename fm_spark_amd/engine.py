@@ -102,6 +102,19 @@ class DeviceBatch:
         self._data = data  # the dataset outlives the view (its rows are borrowed)
         return self
 
+    def set_group(self, group: int):
+        """Mark every ``group`` consecutive rows as a positive followed by its negatives, which a "bpr"
+        context's step reads (fm_batch_set_group): 0 = ungrouped, else 2 .. 1025 and a divisor of n_rows.
+        Returns self."""
+        N.check(self._lib.fm_batch_set_group(self.ctx.handle, self.handle, int(group)), "fm_batch_set_group")
+        return self
+
+    @property
+    def group(self) -> int:
+        """Rows per group (fm_batch_group): set by set_group and by batch_sample_pairs (1 + n_neg), reset
+        to 0 by every other refill."""
+        return int(self._lib.fm_batch_group(self.handle)) if self.handle else 0
+
     def prepare(self):
         """Sort this batch by feature on the side stream ahead of its step (fm_batch_prepare)."""
         N.check(self._lib.fm_batch_prepare(self.ctx.handle, self.handle), "fm_batch_prepare")
@@ -201,17 +214,23 @@ class FMContext:
     the multi-GPU step itself (include/fm_hip.h); ``transport`` "auto" | "rccl" | "copy".
     ``fuse`` None (the library's default: on) | True | False: the fused step for prepared batches
     (fm_config.fuse_single); ``xchg_chunks``: 0 = default (fm_config.xchg_chunks); ``wire`` "fp32" |
-    "fp64": the format of the sharded step's partial sums on the wire (fm_config.wire)."""
+    "fp64": the format of the sharded step's partial sums on the wire (fm_config.wire).  ``loss``
+    "squared" | "logistic" | "bpr": the step's objective (fm_config.loss); the last two are single-GPU,
+    never fuse, and "bpr" steps grouped batches only (DeviceBatch.set_group, batch_sample_pairs)."""
 
     _PAR = {None: N.FM_PARALLEL_NONE, "none": N.FM_PARALLEL_NONE, "sharded": N.FM_PARALLEL_SHARDED,
             "replicated": N.FM_PARALLEL_REPLICATED}
     _TR = {"auto": N.FM_TRANSPORT_AUTO, "rccl": N.FM_TRANSPORT_RCCL, "copy": N.FM_TRANSPORT_COPY}
     _WIRE = {"fp32": N.FM_WIRE_FP32, "fp64": N.FM_WIRE_FP64}
+    _LOSS = {"squared": N.FM_LOSS_SQUARED, "logistic": N.FM_LOSS_LOGISTIC, "bpr": N.FM_LOSS_BPR}
 
     def __init__(self, num_features: int, k: int, *, device: int = 0, seed: int = 0, init_sd: float = 0.01,
                  w0: float = 0.0, shard_index: int = 0, shard_count: int = 1, parallel: str | None = None,
                  n_gpus: int = 1, devices=None, transport: str = "auto", n_procs: int = 1, proc_rank: int = 0,
-                 comm_id: bytes | None = None, fuse: bool | None = None, xchg_chunks: int = 0, wire: str = "fp32"):
+                 comm_id: bytes | None = None, fuse: bool | None = None, xchg_chunks: int = 0, wire: str = "fp32",
+                 loss: str = "squared"):
+        if loss not in self._LOSS:
+            raise ValueError('loss must be "squared", "logistic" or "bpr"')
         self._lib = N.load()
         if wire not in self._WIRE:
             raise ValueError('wire must be "fp32" or "fp64"')
@@ -231,6 +250,7 @@ class FMContext:
         cfg.fuse_single = N.FM_FUSE_DEFAULT if fuse is None else (N.FM_FUSE_ON if fuse else N.FM_FUSE_OFF)
         cfg.xchg_chunks = int(xchg_chunks)
         cfg.wire = self._WIRE[wire]
+        cfg.loss = self._LOSS[loss]
         cfg.n_procs = int(n_procs)
         cfg.proc_rank = int(proc_rank)
         if comm_id is not None:
@@ -249,6 +269,7 @@ class FMContext:
         self.shard_index = int(shard_index)
         self.shard_count = int(shard_count)
         self.wire = wire
+        self.loss = loss
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):

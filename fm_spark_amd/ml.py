@@ -116,6 +116,13 @@ def _explode(vectors):
     return row_ptr, np.asarray(cols, dtype=np.int32), np.asarray(vals, dtype=np.float64)
 
 
+def _sigmoid(z):
+    """sigma(z) from exp(-|z|): finite for every finite z."""
+    z = np.asarray(z, dtype=np.float64)
+    e = np.exp(-np.abs(z))
+    return np.where(z >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
 def _check_schema(df: DataFrame, features_col: str, label_col: str | None):
     """validateAndTransformSchema (FactorizationMachines.scala:33-37): features must be
     vectors (VectorUDT), the label a double."""
@@ -165,7 +172,9 @@ class FactorizationMachinesModel:
         self.dimFactorization = int(dimFactorization)
         self.globalBias = float(globalBias)
         self._params = {"sampleIdCol": "sampleId", "featuresCol": "features", "predictionCol": "prediction",
-                        "labelCol": "label", "minLabel": 0.0, "maxLabel": 1.0}  # Model.scala:54-61
+                        "labelCol": "label", "minLabel": 0.0, "maxLabel": 1.0,  # Model.scala:54-61
+                        # not in the reference: the objective the model was fitted with (setLoss)
+                        "loss": "squared", "rawPredictionCol": "rawPrediction"}
         self.parent = None
         # fit with setValidationData: [(iteration, EvalSums)] of the held-out frame during the fit
         self.validationHistory = []
@@ -222,15 +231,27 @@ class FactorizationMachinesModel:
 
     # transform / predict ---------------------------------------------------------------
     def transformSchema(self, schema):
+        if self._params["loss"] == "logistic":
+            return list(schema) + [self._params["rawPredictionCol"], self._params["predictionCol"]]
         return list(schema) + [self._params["predictionCol"]]
 
     def transform(self, dataset: DataFrame) -> DataFrame:
         """Model.scala:69-87 + predict :90-133: inner-join semantics for unknown ids, clamp to
-        [minLabel, maxLabel], rows without a learned feature get globalBias (na.fill)."""
+        [minLabel, maxLabel], rows without a learned feature get globalBias (na.fill).
+
+        A model fitted with loss "logistic" adds two columns instead: ``rawPrediction``, the unclamped
+        score (fm_predict with -inf / +inf; globalBias for a row without a learned feature), and
+        ``prediction`` = sigma(rawPrediction), the probability of label 1.  minLabel / maxLabel are not
+        applied there: they bound a regression's label, not a score.  Models of the other losses
+        transform as the reference's ("bpr" scores order candidates; they are no label estimate)."""
         fcol = self._params["featuresCol"]
         _check_schema(dataset, fcol, None)
         rp, col, val = _explode(dataset[fcol])
         csr = N.CSRHost(rp, col, val, np.zeros(dataset.count()))
+        if self._params["loss"] == "logistic":
+            raw = self._ctx.predict(csr, -np.inf, np.inf)
+            out = dataset.with_column(self._params["rawPredictionCol"], [float(z) for z in raw])
+            return out.with_column(self._params["predictionCol"], [float(q) for q in _sigmoid(raw)])
         pred = self._ctx.predict(csr, self.getMinLabel(), self.getMaxLabel())
         return dataset.with_column(self._params["predictionCol"], [float(p) for p in pred])
 
@@ -369,6 +390,8 @@ class FactorizationMachinesSGD:
         "validationData": None,
         # not in the reference: negatives drawn per positive by fitInteractions
         "negativesPerPositive": 4,
+        # not in the reference (its loss is the squared error, SGD.scala:134-146): the step's objective
+        "loss": "squared",
     }
 
     def __init__(self, uid: str | None = None):
@@ -406,6 +429,8 @@ class FactorizationMachinesSGD:
         summed in fp64 as on one GPU (fm_config.wire); the fitted model transforms with the same wire."""
         if wire not in ("fp32", "fp64"):
             raise ValueError('wire must be "fp32" or "fp64"')
+        if mode not in (None, "none") and self._params["loss"] != "squared":
+            raise ValueError(f'loss "{self._params["loss"]}" trains on one GPU: multi-GPU objectives are not built yet')
         self._set("parallel", mode)
         self._set("wire", wire)
         self._set("nGpus", int(n_gpus))
@@ -423,6 +448,9 @@ class FactorizationMachinesSGD:
         synchronous fit and multi-GPU estimators evaluate synchronously.  None (default): off."""
         if dataset is None:
             return self._set("validationData", None)
+        if self._params["loss"] != "squared":
+            raise ValueError(f'validationData needs loss "squared", not "{self._params["loss"]}": the device evaluation\'s '
+                             "sums are regression sums (device log-loss and AUC are not built yet)")
         if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or int(every) < 1:
             raise ValueError("every must be an integer >= 1")
         return self._set("validationData", (dataset, int(every)))
@@ -433,6 +461,23 @@ class FactorizationMachinesSGD:
             raise ValueError("negativesPerPositive must be an integer in [0, 1024]")
         return self._set("negativesPerPositive", int(n))
 
+    def setLoss(self, loss: str):
+        """The objective each step descends (fm_config.loss): "squared" (default, the reference's),
+        "logistic" -- log loss of sigma(score) against labels in [0, 1], for click / binary labels and for
+        fitInteractions' 1.0 / 0.0 rows -- or "bpr" -- the pairwise ranking loss of every positive against
+        the negatives drawn for it, fitInteractions only (a frame has no groups).  Both run on one GPU
+        and without validationData (ValueError with either set)."""
+        if loss not in ("squared", "logistic", "bpr"):
+            raise ValueError('loss must be "squared", "logistic" or "bpr"')
+        if loss != "squared":
+            if self._params["parallel"] not in (None, "none"):
+                raise ValueError(f'loss "{loss}" trains on one GPU: multi-GPU objectives are not built yet')
+            if self._params["validationData"] is not None:
+                raise ValueError(f'loss "{loss}" cannot evaluate validationData: the device evaluation\'s sums are '
+                                 "regression sums (device log-loss and AUC are not built yet)")
+        return self._set("loss", loss)
+
+    def getLoss(self): return self._params["loss"]
     def getNegativesPerPositive(self): return self._params["negativesPerPositive"]
     def getDimFactorization(self): return self._params["dimFactorization"]
     def getMaxIter(self): return self._params["maxIter"]
@@ -458,6 +503,17 @@ class FactorizationMachinesSGD:
     def transformSchema(self, schema):
         return schema
 
+    def _check_loss(self):
+        """setLoss's rules again, for params that arrived through copy(extra)."""
+        p = self._params
+        if p["loss"] not in ("squared", "logistic", "bpr"):
+            raise ValueError('loss must be "squared", "logistic" or "bpr"')
+        if p["loss"] != "squared" and p["parallel"] not in (None, "none"):
+            raise ValueError(f'loss "{p["loss"]}" trains on one GPU: multi-GPU objectives are not built yet')
+        if p["loss"] != "squared" and p["validationData"] is not None:
+            raise ValueError(f'loss "{p["loss"]}" cannot evaluate validationData: the device evaluation\'s sums are '
+                             "regression sums")
+
     # fit (SGD.scala:76-216) --------------------------------------------------------------
     def fit(self, dataset: DataFrame, initial_tables=None, pipelined: bool | None = None) -> FactorizationMachinesModel:
         """createInitialModel (:218-252) + addSampleId + runMiniBatchSGD (:88-216).
@@ -470,15 +526,20 @@ class FactorizationMachinesSGD:
         loop has run.  False: every split crosses PCIe as a host CSR and its step returns its loss
         (the same model: the splits hold the same rows in the same order)."""
         p = self._params
+        self._check_loss()
+        if p["loss"] == "bpr":
+            raise ValueError('loss "bpr" needs groups of a positive and its negatives: a frame has none (fitInteractions)')
         _check_schema(dataset, p["featuresCol"], p["labelCol"])
         k = p["dimFactorization"]
         vectors = dataset[p["featuresCol"]]
         labels = np.asarray(dataset[p["labelCol"]], dtype=np.float64)
+        if p["loss"] == "logistic" and len(labels) and not (np.all(labels >= 0.0) and np.all(labels <= 1.0)):
+            raise ValueError('loss "logistic" needs labels in [0, 1]')
         rp, col, val = _explode(vectors)
         F = p["numFeatures"] or (int(col.max()) + 1 if len(col) else 1)
         ctx = FMContext(F, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0,
                         parallel=p["parallel"], n_gpus=p["nGpus"], devices=p["devices"], transport=p["transport"],
-                        wire=p["wire"])
+                        wire=p["wire"], loss=p["loss"])
         if pipelined is None:
             pipelined = True
         # randomSplit(Array.fill(maxIter)(miniBatchFraction), 1234L) (:111-112)
@@ -549,6 +610,7 @@ class FactorizationMachinesSGD:
                 val_run.finish(ctx, p["maxIter"])
         model = FactorizationMachinesModel(self.uid, k, 0.0, ctx=ctx)
         model.setMinLabel(p["minLabel"]).setMaxLabel(p["maxLabel"])
+        model._params["loss"] = p["loss"]
         model.parent = self
         if val_run is not None:
             model.validationHistory = val_run.history
@@ -562,7 +624,8 @@ class FactorizationMachinesSGD:
         `contexts`) and ``candidate`` (row of `candidates`) -- rankPositions' names -- one row per
         positive; both frames carry featuresCol, as recommend's.  A training row is a context row's
         entries followed by a candidate row's, the row recommend and rankPositions score; positives are
-        labelled 1.0 and each gets negativesPerPositive negatives labelled 0.0, drawn on the device
+        labelled 1.0 (what loss "logistic" reads; "bpr" reads the groups -- each positive and the negatives
+        behind it -- and needs negativesPerPositive >= 1) and each gets negativesPerPositive negatives labelled 0.0, drawn on the device
         uniformly over the candidate rows not on its context's ``exclude`` list (default: the context's
         interacted rows, built on the device from the interactions: fm_lists_from_pairs).  Both frames and
         the lists go to the device once and every mini-batch is assembled there
@@ -574,6 +637,9 @@ class FactorizationMachinesSGD:
         ``initial_tables`` = (ids, w, V) replaces the seeded draw over every id of either frame.  A
         multi-GPU estimator (setParallel) and a set validationData raise ValueError: not built yet."""
         p = self._params
+        self._check_loss()
+        if p["loss"] == "bpr" and p["negativesPerPositive"] < 1:
+            raise ValueError('loss "bpr" needs negativesPerPositive >= 1: a positive is ranked against its negatives')
         if p["parallel"] is not None:
             raise ValueError("fitInteractions runs on one GPU: a multi-GPU estimator (setParallel) is not supported yet")
         if p["validationData"] is not None:
@@ -598,7 +664,8 @@ class FactorizationMachinesSGD:
         rows = [_explode(df[fcol]) for df in (contexts, candidates)]
         k = p["dimFactorization"]
         top = max([int(col.max()) + 1 for _, col, _ in rows if len(col)], default=1)
-        ctx = FMContext(p["numFeatures"] or top, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0)
+        ctx = FMContext(p["numFeatures"] or top, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0,
+                        loss=p["loss"])
         bu, bc = (ctx.batch(N.CSRHost(rp, col, val, np.zeros(len(rp) - 1))) for rp, col, val in rows)
         # the exclude lists, resident for the whole loop: the given ones (normalised above, once), else what
         # the interactions say each context has seen, built on the device from the pairs themselves
@@ -640,6 +707,7 @@ class FactorizationMachinesSGD:
                 b.close()
         model = FactorizationMachinesModel(self.uid, k, 0.0, ctx=ctx)
         model.setMinLabel(p["minLabel"]).setMaxLabel(p["maxLabel"])
+        model._params["loss"] = p["loss"]
         model.parent = self
         return model
 

@@ -52,6 +52,9 @@ extern "C" {
 #define FM_FUSE_OFF (-1)
 #define FM_WIRE_FP32 0 /* fm_config.wire: the owners' partial sums cross as fp32 (default) */
 #define FM_WIRE_FP64 1 /* ... as fp64: the sharded step sums every sample in fp64, as the single table */
+#define FM_LOSS_SQUARED 0  /* fm_config.loss: the reference's squared error on the label (default) */
+#define FM_LOSS_LOGISTIC 1 /* log loss of sigma(yhat) against labels in [0, 1] */
+#define FM_LOSS_BPR 2      /* pairwise ranking loss over each positive row and the negatives behind it */
 
 typedef struct fm_ctx fm_ctx;
 typedef struct fm_batch fm_batch;
@@ -101,6 +104,29 @@ typedef struct fm_lists fm_lists;
  *                and its step and predict never read it (FM_PARALLEL_NONE with shard_count 1); a
  *                caller that drives the fm_shard_* phases itself (FM_PARALLEL_NONE, shard_index /
  *                shard_count) gets the format of that context's own value.
+ * loss         : the training objective of fm_step / fm_step_batch, a property of the context.
+ *                FM_LOSS_SQUARED (0, default): the reference's step, sum (yhat - y)^2 with its own
+ *                g_w = x*yhat - y, unchanged in every bit.
+ *                FM_LOSS_LOGISTIC: pointwise, labels y in [0, 1] (NOT checked on the device: a label
+ *                outside gives the gradient of that formula, not an error; check them where they are
+ *                host data).  r_s = sigma(yhat_s) - y_s; a row with at least one entry adds
+ *                softplus(yhat_s) - y_s*yhat_s to loss_sum and 1 to n_loss_rows.
+ *                FM_LOSS_BPR: pairwise, over groups of g = fm_batch_group(batch) consecutive rows: row
+ *                p = q*g is the positive, rows p+1 .. p+g-1 its negatives (fm_batch_sample_pairs' layout).
+ *                With d_j = yhat_p - yhat_{p+j}: r_{p+j} = sigma(-d_j), r_p = -sum_j sigma(-d_j); the group
+ *                adds sum_j softplus(-d_j) to loss_sum and one loss row per (positive, negative) pair.  A
+ *                row without entries scores w0 and takes part.  Labels are not read.
+ *                Both: w -= eta/m * sum_s x*r_s and V -= eta/m * sum_s r_s*(x*S - v*x^2), the true gradient
+ *                (m = n_rows, also under BPR), then the soft threshold as ever.  r is formed in fp64 from
+ *                the score as the step stores it -- yhat rounded to fp32 -- in forms that stay finite for
+ *                every finite score, and rounded to fp32 once.  A stage of its own between the forward
+ *                and the update (profile name "objective"); a squared context launches nothing new.
+ *                A non-squared loss needs parallel == FM_PARALLEL_NONE and shard_count == 1 (FM_ERR_ARG
+ *                naming the loss: multi-GPU objectives are left for later), refuses fuse_single ==
+ *                FM_FUSE_ON (the fused forward applies singleton rows with the squared residual before
+ *                the stage runs) and never fuses under FM_FUSE_DEFAULT (fm_fuse_active is 0).  fm_repl_grad
+ *                / fm_repl_apply refuse such a context.  Any other value is FM_ERR_ARG.  fm_loss_grad /
+ *                fm_calc_loss_grad stay the reference's squared columns on any context.
  * Zero-initialise the struct: every field's 0 is its default. */
 typedef struct fm_config {
   int64_t num_features;
@@ -121,6 +147,7 @@ typedef struct fm_config {
   int32_t fuse_single;
   int32_t xchg_chunks;
   int32_t wire;
+  int32_t loss;
 } fm_config;
 
 /* One mini-batch in CSR form: the result of explode(udfVecToMap(features))
@@ -136,11 +163,12 @@ typedef struct fm_csr {
   const double* label;    /* [n_rows] */
 } fm_csr;
 
-/* What one SGD iteration reports (SGD.scala:134-139 logs lossSum). */
+/* What one SGD iteration reports (SGD.scala:134-139 logs lossSum).  loss_sum and n_loss_rows are the
+ * context's objective's (fm_config.loss), and so is the loss history. */
 typedef struct fm_step_out {
-  double loss_sum;      /* sum over samples with >= 1 active entry of (yhat - y)^2 */
+  double loss_sum;      /* sum over samples with >= 1 active entry of (yhat - y)^2 (FM_LOSS_SQUARED) */
   int64_t n_rows;       /* miniBatchSize m */
-  int64_t n_loss_rows;  /* samples contributing to loss_sum */
+  int64_t n_loss_rows;  /* samples contributing to loss_sum (FM_LOSS_BPR: (positive, negative) pairs) */
   int64_t n_unique;     /* distinct feature ids touched (U) */
 } fm_step_out;
 
@@ -167,7 +195,7 @@ int fm_set_side_stream(fm_ctx* ctx, void* hip_stream);
 /* Wait for everything the context has enqueued: its step stream, its side stream (preparations) and
  * its copy stream (fm_step uploads, fm_batch_from_rows gathers); a multi-GPU context, every rank's. */
 int fm_sync(fm_ctx* ctx);
-/* Pre-size the per-step workspace (the forward's, sort's and update's scratch) so that no step on a
+/* Pre-size the per-step workspace (the forward's, the objective stage's, sort's and update's scratch) so that no step on a
  * device-resident batch of at most max_rows x max_nnz allocates.  What belongs to a batch is sized
  * when the batch is first seen, not here: a batch's own prepared view, a multi-GPU context's
  * per-batch routing state and wire buffers, and fm_step's two upload slots, each of which grows to
@@ -340,6 +368,15 @@ int fm_batch_split_view(fm_ctx* ctx, const fm_batch* data, int32_t split, fm_bat
 int32_t fm_fuse_active(fm_ctx* ctx);
 int64_t fm_batch_rows(const fm_batch* b);
 int64_t fm_batch_nnz(const fm_batch* b);
+/* The batch's rows per group, read by the FM_LOSS_BPR step alone (fm_config.loss): every `group`
+ * consecutive rows are a positive followed by its negatives.  0 = ungrouped.  fm_batch_sample_pairs and
+ * fm_batch_sample_pairs_lists set 1 + n_neg on their result (0 with n_neg == 0: no negatives, no groups);
+ * every other constructor or refill sets 0 (fm_batch_create, fm_batch_from_rows, fm_batch_from_pairs,
+ * fm_batch_split_view).  fm_batch_set_group accepts group == 0, or 2 <= group <= 1025 with n_rows % group
+ * == 0; anything else is FM_ERR_ARG, and so are a dataset made by fm_batch_create_splits and a multi-GPU
+ * context's batch.  Host-only: nothing is enqueued.  fm_batch_group returns -1 for NULL. */
+int fm_batch_set_group(fm_ctx* ctx, fm_batch* batch, int32_t group);
+int32_t fm_batch_group(const fm_batch* b);
 
 /* ---- the hot path ------------------------------------------------------------------- */
 /* One mini-batch SGD iteration = the foldLeft body, SGD.scala:116-211:
@@ -354,7 +391,11 @@ int64_t fm_batch_nnz(const fm_batch* b);
  * by host threads, then copied asynchronously); fm_step_batch uses a device-resident batch.
  * With out == NULL both only enqueue (no host synchronisation; losses are kept on the device,
  * see fm_loss_history): consecutive fm_step calls then overlap the next batch's host work and
- * copies with the current step (two upload slots used in turn). */
+ * copies with the current step (two upload slots used in turn).
+ * fm_config.loss: a logistic or BPR context runs its objective stage between the forward and the
+ * update.  On an FM_LOSS_BPR context a batch whose group is 0 is FM_ERR_ARG ("... needs a grouped batch
+ * ..."; fm_step's host batches always: they carry no group) -- nothing is enqueued, the epoch is
+ * unchanged; on other contexts the group is ignored. */
 int fm_step(fm_ctx* ctx, const fm_csr* batch, int32_t t, double step_size, double reg_param,
             fm_step_out* out);
 int fm_step_batch(fm_ctx* ctx, fm_batch* batch, int32_t t, double step_size,
@@ -592,7 +633,8 @@ int fm_batch_sample_pairs_lists(fm_ctx* ctx, const fm_batch* contexts, const fm_
  * pred[e] = yhat of its row (unclamped), loss[e] = (yhat - y)^2, delta_w[e] = x,
  * delta_v[e*k + f] = vfxiSum_f * x - (v_f * x) * x.  Any output may be NULL.
  * Ids absent from the model are an error here (the reference fills them with an
- * unseeded random draw, Model.scala:170-171, which is never reached from fit). */
+ * unseeded random draw, Model.scala:170-171, which is never reached from fit).  The reference's
+ * squared columns on any context, whatever its fm_config.loss. */
 int fm_loss_grad(fm_ctx* ctx, const fm_csr* csr, double* pred, double* loss, double* delta_w,
                  double* delta_v);
 /* calcLossGrad(dfSampleIndexed, initialSd) with the reference's fill for ids the model lacks
@@ -675,6 +717,7 @@ int fm_xorshift_next_doubles(int64_t seed, int64_t n, double* out);
  *              bytes: s_send / s_recv do not depend on fm_config.wire (they are the values the single
  *              table's update reads)
  * so the exchange is two all-to-alls per direction (the vector section, the scalar section).
+ * The phases are the squared step's: each refuses a context whose fm_config.loss is not FM_LOSS_SQUARED.
  * Every phase is keyed by `batch`, this rank's mini-batch of the iteration; its state lives with
  * the batch.  Phases 1 and 1b depend on the batch alone and run on the side stream
  * (fm_set_side_stream), so the next iteration's routing, entry exchange and slot sort overlap the
