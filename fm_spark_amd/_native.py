@@ -85,6 +85,18 @@ class fm_eval_out(C.Structure):
     ]
 
 
+class fm_binary_out(C.Structure):
+    _fields_ = [
+        ("n_rows", C.c_int64),
+        ("n_pos", C.c_int64),
+        ("epoch", C.c_int64),
+        ("tp", C.c_int64),
+        ("fp", C.c_int64),
+        ("two_u", C.c_int64),
+        ("sum_log_loss", C.c_double),
+    ]
+
+
 _P = C.c_void_p
 _I64P = C.POINTER(C.c_int64)
 _I32P = C.POINTER(C.c_int32)
@@ -129,6 +141,10 @@ SIGNATURES = {
     "fm_evaluate": (C.c_int, [_P, C.POINTER(fm_csr), C.c_double, C.c_double, _DP, C.POINTER(fm_eval_out)]),
     "fm_evaluate_batch": (C.c_int, [_P, _P, C.c_double, C.c_double, _DP, C.POINTER(fm_eval_out)]),
     "fm_eval_history": (C.c_int, [_P, C.POINTER(fm_eval_out), C.c_int64, _I64P]),
+    "fm_binary_metrics": (C.c_int, [_P, _DP, _DP, C.c_int64, C.POINTER(fm_binary_out)]),
+    "fm_evaluate_binary": (C.c_int, [_P, C.POINTER(fm_csr), _DP, C.POINTER(fm_binary_out)]),
+    "fm_evaluate_binary_batch": (C.c_int, [_P, _P, _DP, C.POINTER(fm_binary_out)]),
+    "fm_eval_binary_history": (C.c_int, [_P, C.POINTER(fm_binary_out), C.c_int64, _I64P]),
     "fm_rank_candidates": (C.c_int, [_P, C.POINTER(fm_csr), C.POINTER(fm_csr), C.c_int32, C.c_double, C.c_double,
                                      _I32P, _DP]),
     "fm_rank_batch": (C.c_int, [_P, _P, _P, C.c_int32, C.c_double, C.c_double, _I32P, _DP]),

@@ -17,7 +17,7 @@ ARCH = os.environ.get("FM_HIP_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["fm_forward.hip", "fm_objective.hip", "fm_update.hip", "fm_table.hip", "fm_batch.hip", "fm_sort.hip", "fm_capi.hip",
-           "fm_rank.hip", "fm_pairs.hip", "fm_lists.hip", "fm_shard.hip", "fm_group.hip", "fm_sampler.cpp", "fm_libsvm.cpp"]
+           "fm_rank.hip", "fm_pairs.hip", "fm_lists.hip", "fm_binary.hip", "fm_shard.hip", "fm_group.hip", "fm_sampler.cpp", "fm_libsvm.cpp"]
 HEADERS = ["fm_internal.h", "fm_device.h", "fm_context.h", "fm_hostpool.h"]
 
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]

@@ -9,6 +9,7 @@
 #include <condition_variable>
 #include <cstdio>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <set>
@@ -1140,6 +1141,138 @@ int fm_eval_history(fm_ctx* ctx, fm_eval_out* out, int64_t cap, int64_t* n) {
     FM_HIP_CHECK(hipMemcpyAsync(h.data(), ctx->eval_hist.p, sizeof(double) * kEvalRec * m, hipMemcpyDeviceToHost, ctx->stream));
     FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (int64_t i = 0; i < m; ++i) eval_read(h.data() + kEvalRec * i, ctx->eval_epoch[i], out + i);
+    return FM_OK;
+  });
+}
+
+// ---- binary evaluation (fm_binary_metrics, fm_evaluate_binary[_batch], fm_eval_binary_history; fm_binary.hip) ----
+static void binary_read(const int64_t* rec, int64_t epoch, fm_binary_out* out) {
+  out->n_rows = rec[0];
+  out->n_pos = rec[1];
+  out->epoch = epoch;
+  out->tp = rec[2];
+  out->fp = rec[3];
+  out->two_u = rec[4];
+  std::memcpy(&out->sum_log_loss, &rec[5], sizeof(double));
+}
+
+// a single-table context that holds the whole table: the binary evaluation is single-GPU, as the logistic step
+static void require_binary_ctx(const fm_ctx* ctx, const char* call) {
+  FM_REQUIRE(!ctx->group && ctx->cfg.shard_count == 1,
+             std::string(call) + " needs a single-table context: multi-GPU and sharded (shard_count > 1) contexts have no "
+                                 "binary evaluation");
+}
+
+// the stage over n device scores and labels into rec (device), on the main stream (profile "evaluate_binary",
+// its sort and its count -- scan, pair count, fold -- inside it); e0: a profile start recorded by the caller
+// ahead of its score pass, or null
+static void binary_stage(fm_ctx* ctx, const double* score, const double* label, int64_t n, int64_t* rec, hipEvent_t e0) {
+  hipStream_t st = ctx->stream;
+  BinaryWork& w = ctx->binary;
+  w.ensure(n);
+  if (!e0) e0 = ctx->prof_begin(st);
+  launch_binary_rows(w, score, label, n, st);
+  hipEvent_t es = ctx->prof_begin(st);
+  launch_binary_sort(w, n, st);
+  ctx->prof_end("binary_sort", es, st);
+  hipEvent_t ec = ctx->prof_begin(st);
+  launch_binary_count(w, n, rec, st);
+  ctx->prof_end("binary_count", ec, st);
+  ctx->prof_end("evaluate_binary", e0, st);
+}
+
+// the record at rec (device) read back: the main stream is waited for
+static void binary_fetch(fm_ctx* ctx, const int64_t* rec, fm_binary_out* out) {
+  ctx->pinned.ensure(64);
+  FM_HIP_CHECK(hipMemcpyAsync(ctx->pinned.p, rec, sizeof(int64_t) * kBinaryRec, hipMemcpyDeviceToHost, ctx->stream));
+  FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  binary_read(reinterpret_cast<const int64_t*>(ctx->pinned.p), ctx->epoch, out);
+}
+
+int fm_binary_metrics(fm_ctx* ctx, const double* score, const double* label, int64_t n, fm_binary_out* out) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(out != nullptr, "fm_binary_metrics: null out");
+    *out = fm_binary_out{};
+    require_binary_ctx(ctx, "fm_binary_metrics");
+    FM_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "fm_binary_metrics: n out of range");
+    if (n == 0) return FM_NOTHING_TO_DO;
+    FM_REQUIRE(score != nullptr && label != nullptr, "fm_binary_metrics: null score or label");
+    BinaryWork& w = ctx->binary;
+    w.score.ensure_slack(sizeof(double) * (size_t)n);
+    w.label.ensure_slack(sizeof(double) * (size_t)n);
+    w.rec.ensure(sizeof(int64_t) * kBinaryRec);
+    // (pageable host memory: the copies have left the caller's buffers when they return)
+    FM_HIP_CHECK(hipMemcpyAsync(w.score.p, score, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    FM_HIP_CHECK(hipMemcpyAsync(w.label.p, label, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    binary_stage(ctx, w.score.as<double>(), w.label.as<double>(), n, w.rec.as<int64_t>(), nullptr);
+    binary_fetch(ctx, w.rec.as<int64_t>(), out);
+    return FM_OK;
+  });
+}
+
+// One binary evaluation of a single-table context's batch on the main stream: launch_predict's unclamped
+// score of every row, the stage against the batch's labels into the history's next slot, the record counted;
+// score / out as fm_evaluate_binary_batch takes them.
+static int evaluate_binary_impl(fm_ctx* ctx, fm_batch* b, double* score, fm_binary_out* out) {
+  const int64_t B = b->dev.n_rows;
+  FM_REQUIRE(B < (int64_t(1) << 31), "fm_evaluate_binary: too many rows");
+  hipStream_t st = ctx->stream;
+  BinaryWork& w = ctx->binary;
+  ctx->ensure_bin_hist(ctx->bin_n + 1);
+  int64_t* slot = ctx->bin_hist.as<int64_t>() + kBinaryRec * ctx->bin_n;
+  w.score.ensure_slack(sizeof(double) * (size_t)B);
+  w.ensure(B);
+  wait_built(b, st);
+  hipEvent_t e0 = ctx->prof_begin(st);
+  const double inf = std::numeric_limits<double>::infinity();
+  launch_predict(ctx->view(), b->dev, ctx->cum_host.back(), ctx->cfg.w0, -inf, inf, w.score.as<double>(), st);
+  binary_stage(ctx, w.score.as<double>(), b->dev.label.as<double>(), B, slot, e0);
+  // a read of the batch: its next fm_batch_prepare or fm_batch_from_rows refill waits for it
+  if (b->last_use) FM_HIP_CHECK(hipEventRecord(b->last_use, st));
+  if (score) FM_HIP_CHECK(hipMemcpyAsync(score, w.score.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, st));
+  ctx->bin_epoch.push_back(ctx->epoch);
+  ctx->bin_n += 1;
+  if (out) binary_fetch(ctx, slot, out);
+  return FM_OK;
+}
+
+int fm_evaluate_binary(fm_ctx* ctx, const fm_csr* csr, double* score, fm_binary_out* out) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(csr != nullptr && out != nullptr, "fm_evaluate_binary: null argument");
+    *out = fm_binary_out{};
+    require_binary_ctx(ctx, "fm_evaluate_binary");
+    if (csr->n_rows == 0) return FM_NOTHING_TO_DO;
+    fm_batch* b = host_batch(ctx);
+    upload_batch(ctx, csr, b, false);
+    return evaluate_binary_impl(ctx, b, score, out);
+  });
+}
+
+int fm_evaluate_binary_batch(fm_ctx* ctx, fm_batch* b, double* score, fm_binary_out* out) {
+  return guarded(ctx, [&]() -> int {
+    if (out) *out = fm_binary_out{};
+    FM_REQUIRE(b != nullptr && b->owner == ctx, "fm_evaluate_binary_batch: batch belongs to another context");
+    FM_REQUIRE(out != nullptr || score == nullptr,
+               "fm_evaluate_binary_batch: score needs out: an evaluation that only enqueues returns no scores");
+    FM_REQUIRE(b->split_rows.empty(),
+               "fm_evaluate_binary_batch: a dataset made by fm_batch_create_splits is evaluated by split");
+    require_binary_ctx(ctx, "fm_evaluate_binary_batch");
+    if (b->dev.n_rows == 0) return FM_NOTHING_TO_DO;
+    return evaluate_binary_impl(ctx, b, score, out);
+  });
+}
+
+int fm_eval_binary_history(fm_ctx* ctx, fm_binary_out* out, int64_t cap, int64_t* n) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(n != nullptr, "fm_eval_binary_history: null n");
+    *n = ctx->bin_n;
+    if (cap <= 0 || ctx->bin_n == 0) return FM_OK;
+    FM_REQUIRE(out != nullptr, "fm_eval_binary_history: null history buffer");
+    const int64_t m = std::min<int64_t>(cap, ctx->bin_n);
+    std::vector<int64_t> h(kBinaryRec * m);
+    FM_HIP_CHECK(hipMemcpyAsync(h.data(), ctx->bin_hist.p, sizeof(int64_t) * kBinaryRec * m, hipMemcpyDeviceToHost, ctx->stream));
+    FM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < m; ++i) binary_read(h.data() + kBinaryRec * i, ctx->bin_epoch[i], out + i);
     return FM_OK;
   });
 }

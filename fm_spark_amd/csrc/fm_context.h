@@ -216,6 +216,12 @@ struct fm_ctx {
   std::vector<int64_t> eval_epoch;
   std::vector<fm_eval_out> eval_host;
   DevBuf eval_pred;  // the synchronous evaluation's predictions on their way to the host (grown to the largest call)
+  // fm_evaluate_binary*: the same for the binary records (fm_eval_binary_history), kBinaryRec int64 words each;
+  // single-table contexts only.  `binary`: the stage's scratch (fm_binary.hip), main stream only.
+  DevBuf bin_hist;  // [bin_cap][kBinaryRec] int64
+  int64_t bin_cap = 0, bin_n = 0;
+  std::vector<int64_t> bin_epoch;
+  BinaryWork binary;
   StepWork work;
   Pinned pinned;
   Pinned up_pin;                         // host CSR upload staging (upload_batch)
@@ -350,6 +356,21 @@ struct fm_ctx {
     eval_cap = c;
   }
 
+  // the binary evaluation history holds `need` records: grown as ensure_hist grows the loss history
+  void ensure_bin_hist(int64_t need) {
+    if (need <= bin_cap) return;
+    int64_t c = std::max<int64_t>(4096, bin_cap);
+    while (c < need) c *= 2;
+    FM_HIP_CHECK(hipStreamSynchronize(stream));
+    DevBuf nb;
+    nb.ensure(sizeof(int64_t) * kBinaryRec * c);
+    FM_HIP_CHECK(hipMemset(nb.p, 0, sizeof(int64_t) * kBinaryRec * c));
+    if (bin_cap > 0)
+      FM_HIP_CHECK(hipMemcpy(nb.p, bin_hist.p, sizeof(int64_t) * kBinaryRec * bin_cap, hipMemcpyDeviceToDevice));
+    bin_hist = std::move(nb);  // the old history is freed (the stream was drained above)
+    bin_cap = c;
+  }
+
   ~fm_ctx() {
     group.reset();
     (void)hipSetDevice(cfg.device);
@@ -376,7 +397,12 @@ struct fm_ctx {
     rec.release();
     loss_hist.release();
     eval_hist.release();
-    DevBuf* bufs[] = {&work.S, &work.yl, &work.loss_part, &work.part, &work.ucnt, &work.eval_part, &eval_pred,
+    bin_hist.release();
+    DevBuf* bufs[] = {&binary.score, &binary.label, &binary.key_lo, &binary.pay, &binary.key_hi, &binary.pay2, &binary.flag,
+                      &binary.cp, &binary.chunk_tot, &binary.chunk_off, &binary.total, &binary.rows_part,
+                      &binary.count_part, &binary.rec, &binary.sort.keys_a, &binary.sort.keys_b, &binary.sort.vals_a,
+                      &binary.sort.vals_b, &binary.sort.counts, &binary.sort.digit_tot,
+                      &work.S, &work.yl, &work.loss_part, &work.part, &work.ucnt, &work.eval_part, &eval_pred,
                       &work.sort.keys_a, &work.sort.keys_b, &work.sort.vals_a, &work.sort.vals_b,
                       &work.sort.counts, &work.sort.digit_tot, &side_sort.keys_a, &side_sort.keys_b,
                       &side_sort.vals_a, &side_sort.vals_b, &side_sort.counts, &side_sort.digit_tot,

@@ -129,6 +129,16 @@ __device__ __forceinline__ void block_eval_partial(EvalAcc a, double* __restrict
   }
 }
 
+// The logistic forms of the objective stage (fm_objective.hip) and the binary evaluation (fm_binary.hip),
+// fp64 and finite for every finite z:
+//   sigma(z) = 1 / (1 + e) or e / (1 + e), e = exp(-|z|);   softplus(z) = max(z, 0) + log1p(exp(-|z|)).
+__device__ __forceinline__ double sigmoid_d(double z) {
+  const double e = exp(-fabs(z));  // in (0, 1]
+  const double s = 1.0 / (1.0 + e);
+  return z >= 0.0 ? s : e * s;
+}
+__device__ __forceinline__ double softplus_d(double z) { return fmax(z, 0.0) + log1p(exp(-fabs(z))); }
+
 __device__ __forceinline__ void st_row4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 __device__ __forceinline__ float shrink_f(float z, double a) {

@@ -503,6 +503,33 @@ void launch_lists_offsets(const uint32_t* sctx, const uint32_t* scand, int64_t n
 void launch_lists_compact(const uint32_t* scand, const uint32_t* flag, const int64_t* off, int64_t n, int32_t* rows,
                           hipStream_t st);
 
+// ---------------------------------------------------------------- binary evaluation (fm_binary.hip)
+// int64 words of a binary evaluation record on the device (one 64-byte line): {n_rows, n_pos, tp, fp, two_u,
+// the bits of sum_log_loss, 0, 0}
+constexpr int kBinaryRec = 8;
+// Scratch of fm_binary_metrics / fm_evaluate_binary*, kept with the context (grown to the largest call, never
+// shrunk) and used on the main stream alone.  The sort workspace is the stage's own: the context's other
+// workspaces may be sorting a prepared batch on the side stream.
+struct BinaryWork {
+  DevBuf score, label;      // double [n]: the scores (launch_predict's, or fm_binary_metrics' upload) / its labels
+  DevBuf key_lo, pay;       // uint32 [n] low key words, uint2 [n] {high key word, positive flag}: the first sort's input
+  DevBuf key_hi, pay2;      // the same re-keyed: the second sort's input
+  DevBuf flag, cp;          // uint32 [n] sorted positive flags, int64 [n + 1] their exclusive scan
+  DevBuf chunk_tot, chunk_off, total;  // launch_len_scan's
+  DevBuf rows_part, count_part;        // the per-block partials of k_binary_rows / k_binary_count
+  DevBuf rec;               // int64 [kBinaryRec]: fm_binary_metrics' record (the evaluations write into the history)
+  SortWork sort;
+  const uint32_t* sorted_hi = nullptr;  // the second sort's output (inside `sort`), valid from launch_binary_sort
+  const uint2* sorted_pay = nullptr;    // until the next one
+  void ensure(int64_t n);  // everything but score / label / rec, for n rows
+};
+// The stage in three launches, so that a profile can tell them apart; n in [1, 2^31), score / label device [n]:
+// the per-row pass (its partials and the sort's input), the two stable sorts, then the flags' scan, the pair
+// count and the fold of both partials into rec[kBinaryRec] (device).
+void launch_binary_rows(BinaryWork& w, const double* score, const double* label, int64_t n, hipStream_t st);
+void launch_binary_sort(BinaryWork& w, int64_t n, hipStream_t st);
+void launch_binary_count(BinaryWork& w, int64_t n, int64_t* rec, hipStream_t st);
+
 // fm_batch_create_splits: each split's own row_ptr (rebased to its first entry) into split_rp
 // [B + n_splits] and every entry's sample index made relative to its split's first row
 // (split_rows [n_splits + 1], device)

@@ -37,12 +37,7 @@ namespace {
 constexpr int kObjGrid = 256;
 static_assert(kObjGrid <= kLossPartBlocks, "the stage's loss partials fit the reserved loss_part");
 
-__device__ __forceinline__ double sigmoid_d(double z) {
-  const double e = exp(-fabs(z));  // in (0, 1]
-  const double s = 1.0 / (1.0 + e);
-  return z >= 0.0 ? s : e * s;
-}
-__device__ __forceinline__ double softplus_d(double z) { return fmax(z, 0.0) + log1p(exp(-fabs(z))); }
+// (sigmoid_d / softplus_d: fm_device.h, shared with the binary evaluation)
 
 template <int LOSS, int TEAM>
 __global__ __launch_bounds__(kBlock) void k_objective(float2* __restrict__ yl, int64_t ystr,

@@ -63,6 +63,62 @@ class EvalSums:
         return 1.0 - self.sum_sq_err / ss_tot
 
 
+def _ratio(num, den) -> float:
+    return float(num) / float(den) if den else float("nan")
+
+
+@dataclass(frozen=True)
+class BinarySums:
+    """One binary evaluation record (fm_binary_out): the class counts, the confusion counts at the
+    threshold score > 0, twice the Mann-Whitney U of the positives over the negatives and the log loss
+    sum, formed on the device, and the metrics BinaryClassificationEvaluator derives from them.  A metric
+    whose denominator is 0 is NaN."""
+
+    n_rows: int
+    n_pos: int
+    epoch: int
+    tp: int
+    fp: int
+    two_u: int
+    sum_log_loss: float
+    executed: bool = True
+
+    @staticmethod
+    def from_struct(o: "N.fm_binary_out", executed: bool = True) -> "BinarySums":
+        return BinarySums(int(o.n_rows), int(o.n_pos), int(o.epoch), int(o.tp), int(o.fp), int(o.two_u),
+                          float(o.sum_log_loss), executed)
+
+    @property
+    def n_neg(self) -> int:
+        return self.n_rows - self.n_pos
+
+    @property
+    def logLoss(self) -> float:
+        """mean softplus(score) - label * score"""
+        return _ratio(self.sum_log_loss, self.n_rows)
+
+    @property
+    def auc(self) -> float:
+        """area under the ROC curve, ties counted as half: two_u / (2 n_pos n_neg), from exact integers"""
+        return _ratio(self.two_u, 2 * self.n_pos * self.n_neg)
+
+    @property
+    def accuracy(self) -> float:
+        return _ratio(self.tp + (self.n_neg - self.fp), self.n_rows)
+
+    @property
+    def precision(self) -> float:
+        return _ratio(self.tp, self.tp + self.fp)
+
+    @property
+    def recall(self) -> float:
+        return _ratio(self.tp, self.n_pos)
+
+    @property
+    def f1(self) -> float:
+        return _ratio(2 * self.tp, self.tp + self.fp + self.n_pos)
+
+
 class DeviceBatch:
     """A CSR mini-batch resident in HBM (fm_batch_create)."""
 
@@ -581,6 +637,53 @@ class FMContext:
         buf = (N.fm_eval_out * n.value)()
         N.check(self._lib.fm_eval_history(self.handle, buf, n.value, C.byref(n)), "fm_eval_history")
         return [EvalSums.from_struct(o) for o in buf[: n.value]]
+
+    def binary_metrics(self, score, label) -> BinarySums:
+        """The binary record of host scores (logits, from any model) against labels, computed on the
+        device (fm_binary_metrics); nothing is appended to the history."""
+        score = np.ascontiguousarray(score, dtype=np.float64)
+        label = np.ascontiguousarray(label, dtype=np.float64)
+        if score.shape != label.shape or score.ndim != 1:
+            raise ValueError("score and label must be 1-d arrays of one length")
+        out = N.fm_binary_out()
+        rc = N.check(self._lib.fm_binary_metrics(self.handle, N.ptr(score, C.c_double), N.ptr(label, C.c_double),
+                                                 len(score), C.byref(out)), "fm_binary_metrics")
+        return BinarySums.from_struct(out, executed=rc != N.FM_NOTHING_TO_DO)
+
+    def evaluate_binary(self, csr: N.CSRHost, want_score: bool = False):
+        """The binary record of the unclamped scores of csr's rows against its labels, on the device
+        (fm_evaluate_binary): BinarySums, or (BinarySums, scores) with want_score."""
+        return self._evaluate_binary(self._lib.fm_evaluate_binary, "fm_evaluate_binary", C.byref(csr.c), csr.n_rows, True,
+                                     want_score)
+
+    def evaluate_binary_batch(self, b: DeviceBatch, sync: bool = True, want_score: bool = False):
+        """The same over a device-resident batch (fm_evaluate_binary_batch).  sync=False only enqueues (the
+        record is read later through eval_binary_history) and returns None."""
+        if not sync and want_score:
+            raise ValueError("want_score needs sync=True")
+        return self._evaluate_binary(self._lib.fm_evaluate_binary_batch, "fm_evaluate_binary_batch", b.handle, b.n_rows,
+                                     sync, want_score)
+
+    def _evaluate_binary(self, fn, what, rows, n_rows, sync, want_score):
+        if not sync:
+            N.check(fn(self.handle, rows, None, None), what)
+            return None
+        score = np.zeros(max(n_rows, 1)) if want_score else None
+        out = N.fm_binary_out()
+        rc = N.check(fn(self.handle, rows, N.ptr(score, C.c_double) if want_score else None, C.byref(out)), what)
+        sums = BinarySums.from_struct(out, executed=rc != N.FM_NOTHING_TO_DO)
+        return (sums, score[:n_rows]) if want_score else sums
+
+    def eval_binary_history(self) -> list:
+        """Every binary evaluation record of this context so far, in order (fm_eval_binary_history; waits
+        for the main stream)."""
+        n = C.c_int64()
+        N.check(self._lib.fm_eval_binary_history(self.handle, None, 0, C.byref(n)), "fm_eval_binary_history")
+        if not n.value:
+            return []
+        buf = (N.fm_binary_out * n.value)()
+        N.check(self._lib.fm_eval_binary_history(self.handle, buf, n.value, C.byref(n)), "fm_eval_binary_history")
+        return [BinarySums.from_struct(o) for o in buf[: n.value]]
 
     def rank(self, contexts: N.CSRHost, candidates: N.CSRHost, n_top: int, min_label: float, max_label: float, *,
              only=None, exclude=None):

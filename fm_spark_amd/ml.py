@@ -26,7 +26,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _native as N
-from .engine import EvalSums, FMContext, normalize_row_lists
+from .engine import BinarySums, EvalSums, FMContext, normalize_row_lists
 from .linalg import DenseVector, Vector, Vectors, active_map
 
 log = logging.getLogger("org.apache.spark.ml.fm")
@@ -178,6 +178,8 @@ class FactorizationMachinesModel:
         self.parent = None
         # fit with setValidationData: [(iteration, EvalSums)] of the held-out frame during the fit
         self.validationHistory = []
+        # fit with setBinaryValidationData: [(iteration, BinarySums)] likewise
+        self.binaryValidationHistory = []
         if ctx is not None:
             self._ctx = ctx
         else:
@@ -216,6 +218,7 @@ class FactorizationMachinesModel:
         m._params.update(extra or {})
         m.parent = self.parent
         m.validationHistory = list(self.validationHistory)
+        m.binaryValidationHistory = list(self.binaryValidationHistory)
         return m
 
     # tables ------------------------------------------------------------------------------
@@ -265,6 +268,18 @@ class FactorizationMachinesModel:
         rp, col, val = _explode(dataset[fcol])
         csr = N.CSRHost(rp, col, val, np.asarray(dataset[lcol], dtype=np.float64))
         return self._ctx.evaluate(csr, self.getMinLabel(), self.getMaxLabel())
+
+    def evaluateBinary(self, dataset: DataFrame) -> BinarySums:
+        """The binary record of dataset's rows against labelCol, formed on the device in one call
+        (fm_evaluate_binary): no score column is built or downloaded.  The score is transform's
+        ``rawPrediction`` -- the unclamped score, globalBias for a row without a learned feature -- read as
+        a logit whatever loss the model was fitted with; a label > 0.5 is a positive.  logLoss, auc (exact,
+        ties counted as half), accuracy, precision, recall and f1 are properties of the result."""
+        fcol, lcol = self._params["featuresCol"], self._params["labelCol"]
+        _check_schema(dataset, fcol, lcol)
+        rp, col, val = _explode(dataset[fcol])
+        csr = N.CSRHost(rp, col, val, np.asarray(dataset[lcol], dtype=np.float64))
+        return self._ctx.evaluate_binary(csr)
 
     def recommend(self, contexts: DataFrame, candidates: DataFrame, numItems: int, exclude=None, only=None) -> DataFrame:
         """The numItems best rows of `candidates` for every row of `contexts` (the shape of
@@ -388,6 +403,8 @@ class FactorizationMachinesSGD:
         "parallel": None, "nGpus": 1, "devices": None, "transport": "auto", "wire": "fp32",
         # not in the reference: a held-out frame evaluated on the device during fit, (frame, every)
         "validationData": None,
+        # not in the reference: a held-out frame whose log loss and AUC the device forms during fit, (frame, every)
+        "binaryValidationData": None,
         # not in the reference: negatives drawn per positive by fitInteractions
         "negativesPerPositive": 4,
         # not in the reference (its loss is the squared error, SGD.scala:134-146): the step's objective
@@ -431,6 +448,8 @@ class FactorizationMachinesSGD:
             raise ValueError('wire must be "fp32" or "fp64"')
         if mode not in (None, "none") and self._params["loss"] != "squared":
             raise ValueError(f'loss "{self._params["loss"]}" trains on one GPU: multi-GPU objectives are not built yet')
+        if mode not in (None, "none") and self._params["binaryValidationData"] is not None:
+            raise ValueError("binaryValidationData needs a single-GPU estimator: the binary evaluation is not multi-GPU")
         self._set("parallel", mode)
         self._set("wire", wire)
         self._set("nGpus", int(n_gpus))
@@ -450,10 +469,31 @@ class FactorizationMachinesSGD:
             return self._set("validationData", None)
         if self._params["loss"] != "squared":
             raise ValueError(f'validationData needs loss "squared", not "{self._params["loss"]}": the device evaluation\'s '
-                             "sums are regression sums (device log-loss and AUC are not built yet)")
+                             "sums are regression sums (device log-loss and AUC are not built yet); log loss and AUC "
+                             "during fit: setBinaryValidationData")
         if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or int(every) < 1:
             raise ValueError("every must be an integer >= 1")
         return self._set("validationData", (dataset, int(every)))
+
+    def setBinaryValidationData(self, dataset: DataFrame | None, every: int = 1):
+        """A held-out frame (featuresCol, labelCol) whose binary record -- log loss, exact AUC and the
+        confusion counts at score > 0 (FactorizationMachinesModel.evaluateBinary's) -- is formed on the device
+        during fit, after every `every`-th executed iteration and after the last, and appended to the fitted
+        model's ``binaryValidationHistory`` as (iteration, BinarySums), with one log line per entry.  Upload,
+        schedule and read-back are validationData's: the pipelined fit only enqueues
+        (fm_evaluate_binary_batch without out).  Accepted with loss "squared" and "logistic" (the score is
+        read as a logit); "bpr", a multi-GPU estimator and fitInteractions refuse it.  Independent of
+        validationData: either, both or neither may be set.  None (default): off."""
+        if dataset is None:
+            return self._set("binaryValidationData", None)
+        if self._params["loss"] == "bpr":
+            raise ValueError('binaryValidationData needs loss "squared" or "logistic": "bpr" scores order candidates, '
+                             "they are no logit of a label")
+        if self._params["parallel"] not in (None, "none"):
+            raise ValueError("binaryValidationData needs a single-GPU estimator: the binary evaluation is not multi-GPU")
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or int(every) < 1:
+            raise ValueError("every must be an integer >= 1")
+        return self._set("binaryValidationData", (dataset, int(every)))
 
     def setNegativesPerPositive(self, n: int):
         """fitInteractions draws n negatives for every positive of a mini-batch (0 .. 1024; default 4)."""
@@ -466,7 +506,8 @@ class FactorizationMachinesSGD:
         "logistic" -- log loss of sigma(score) against labels in [0, 1], for click / binary labels and for
         fitInteractions' 1.0 / 0.0 rows -- or "bpr" -- the pairwise ranking loss of every positive against
         the negatives drawn for it, fitInteractions only (a frame has no groups).  Both run on one GPU
-        and without validationData (ValueError with either set)."""
+        and without validationData (ValueError with either set); "logistic" takes binaryValidationData
+        (log loss and AUC during fit), "bpr" does not."""
         if loss not in ("squared", "logistic", "bpr"):
             raise ValueError('loss must be "squared", "logistic" or "bpr"')
         if loss != "squared":
@@ -474,7 +515,10 @@ class FactorizationMachinesSGD:
                 raise ValueError(f'loss "{loss}" trains on one GPU: multi-GPU objectives are not built yet')
             if self._params["validationData"] is not None:
                 raise ValueError(f'loss "{loss}" cannot evaluate validationData: the device evaluation\'s sums are '
-                                 "regression sums (device log-loss and AUC are not built yet)")
+                                 "regression sums (device log-loss and AUC are not built yet); log loss and AUC "
+                                 "during fit: setBinaryValidationData")
+        if loss == "bpr" and self._params["binaryValidationData"] is not None:
+            raise ValueError('loss "bpr" cannot evaluate binaryValidationData: its scores are no logit of a label')
         return self._set("loss", loss)
 
     def getLoss(self): return self._params["loss"]
@@ -513,6 +557,11 @@ class FactorizationMachinesSGD:
         if p["loss"] != "squared" and p["validationData"] is not None:
             raise ValueError(f'loss "{p["loss"]}" cannot evaluate validationData: the device evaluation\'s sums are '
                              "regression sums")
+        if p["binaryValidationData"] is not None:
+            if p["loss"] == "bpr":
+                raise ValueError('loss "bpr" cannot evaluate binaryValidationData: its scores are no logit of a label')
+            if p["parallel"] not in (None, "none"):
+                raise ValueError("binaryValidationData needs a single-GPU estimator: the binary evaluation is not multi-GPU")
 
     # fit (SGD.scala:76-216) --------------------------------------------------------------
     def fit(self, dataset: DataFrame, initial_tables=None, pipelined: bool | None = None) -> FactorizationMachinesModel:
@@ -581,14 +630,18 @@ class FactorizationMachinesSGD:
             # createInitialModel (:224-241): the draw for every distinct active feature id, on the
             # device over the whole dataset's entries
             ctx.init_from_batch(data)
-        val_run = None
+        val_run = bin_run = None
         if p["validationData"] is not None:
             val_run = _Validation.upload(ctx, p["validationData"], p["featuresCol"], p["labelCol"], F, p["minLabel"],
                                          p["maxLabel"])
+        if p["binaryValidationData"] is not None:
+            bin_run = _Validation.upload(ctx, p["binaryValidationData"], p["featuresCol"], p["labelCol"], F, p["minLabel"],
+                                         p["maxLabel"], binary=True)
+        val_runs = [v for v in (val_run, bin_run) if v is not None]
         if pipelined:
             if data is not None:
                 run_minibatch_sgd_splits(ctx, data, p["stepSize"], p["regParam"], n_iter=p["maxIter"],
-                                         validation=val_run)
+                                         validation=val_runs)
             else:
                 for i in range(p["maxIter"]):
                     log.warning("Iteration (%d/%d). The size of sampled batch is zero", i + 1, p["maxIter"])
@@ -604,10 +657,11 @@ class FactorizationMachinesSGD:
                 out = ctx.step(csr, it, p["stepSize"], p["regParam"])
                 log.info("Loss of Iteration (%d/%d): %s", it, p["maxIter"], out.loss_sum)
                 j += 1
-                if val_run is not None and val_run.due(j, n_exec):
-                    val_run.evaluate(ctx, it, sync=True)
-            if val_run is not None:
-                val_run.finish(ctx, p["maxIter"])
+                for v in val_runs:
+                    if v.due(j, n_exec):
+                        v.evaluate(ctx, it, sync=True)
+            for v in val_runs:
+                v.finish(ctx, p["maxIter"])
         model = FactorizationMachinesModel(self.uid, k, 0.0, ctx=ctx)
         model.setMinLabel(p["minLabel"]).setMaxLabel(p["maxLabel"])
         model._params["loss"] = p["loss"]
@@ -615,6 +669,9 @@ class FactorizationMachinesSGD:
         if val_run is not None:
             model.validationHistory = val_run.history
             val_run.close()
+        if bin_run is not None:
+            model.binaryValidationHistory = bin_run.history
+            bin_run.close()
         return model
 
 
@@ -644,6 +701,9 @@ class FactorizationMachinesSGD:
             raise ValueError("fitInteractions runs on one GPU: a multi-GPU estimator (setParallel) is not supported yet")
         if p["validationData"] is not None:
             raise ValueError("fitInteractions does not evaluate validationData yet")
+        if p["binaryValidationData"] is not None:
+            raise ValueError("fitInteractions does not evaluate binaryValidationData: its metric is a ranking metric over "
+                             "held-out positives (RankingEvaluator)")
         fcol = p["featuresCol"]
         _check_schema(contexts, fcol, None)
         _check_schema(candidates, fcol, None)
@@ -713,17 +773,18 @@ class FactorizationMachinesSGD:
 
 
 class _Validation:
-    """fit's held-out frame (setValidationData): one device batch of the fit's context, the iterations
-    at which it was evaluated and, once the loop has run, their records."""
+    """fit's held-out frame (setValidationData; binary: setBinaryValidationData): one device batch of the
+    fit's context, the iterations at which it was evaluated and, once the loop has run, their records."""
 
-    def __init__(self, batch, lo: float, hi: float, every: int):
-        self.batch, self.lo, self.hi, self.every = batch, lo, hi, every
-        self.history = []   # [(iteration, EvalSums)]
+    def __init__(self, batch, lo: float, hi: float, every: int, binary: bool = False):
+        self.batch, self.lo, self.hi, self.every, self.binary = batch, lo, hi, every, binary
+        self.history = []   # [(iteration, EvalSums)]; binary: [(iteration, BinarySums)]
         self._queued = []   # iterations whose evaluation was only enqueued
         self._h0 = 0        # the context's evaluation records before this fit's first
 
     @staticmethod
-    def upload(ctx: FMContext, spec, features_col: str, label_col: str, num_features: int, lo: float, hi: float):
+    def upload(ctx: FMContext, spec, features_col: str, label_col: str, num_features: int, lo: float, hi: float,
+               binary: bool = False):
         df, every = spec
         _check_schema(df, features_col, label_col)
         rp, col, val = _explode(df[features_col])
@@ -736,9 +797,17 @@ class _Validation:
             col, val = col[keep], val[keep]
         y = np.asarray(df[label_col], dtype=np.float64)
         batch = ctx.batch(N.CSRHost(rp, col, val, y)) if len(y) else None
-        v = _Validation(batch, float(lo), float(hi), every)
-        v._h0 = len(ctx.eval_history())
+        v = _Validation(batch, float(lo), float(hi), every, binary)
+        v._h0 = len(v._records(ctx))
         return v
+
+    def _records(self, ctx: FMContext) -> list:
+        return ctx.eval_binary_history() if self.binary else ctx.eval_history()
+
+    def _evaluate(self, ctx: FMContext, sync: bool):
+        if self.binary:
+            return ctx.evaluate_binary_batch(self.batch, sync=sync)
+        return ctx.evaluate_batch(self.batch, self.lo, self.hi, sync=sync)
 
     def due(self, n_done: int, n_total: int) -> bool:
         """after the n_done-th executed iteration of n_total"""
@@ -746,18 +815,22 @@ class _Validation:
 
     def evaluate(self, ctx: FMContext, iteration: int, sync: bool):
         if sync:
-            self.history.append((iteration, ctx.evaluate_batch(self.batch, self.lo, self.hi)))
+            self.history.append((iteration, self._evaluate(ctx, True)))
         else:
-            ctx.evaluate_batch(self.batch, self.lo, self.hi, sync=False)
+            self._evaluate(ctx, False)
             self._queued.append(iteration)
 
     def finish(self, ctx: FMContext, n_iter: int):
         """The enqueued evaluations' records read (one host synchronisation), and the log lines."""
         if self._queued:
-            recs = ctx.eval_history()[self._h0:]
+            recs = self._records(ctx)[self._h0:]
             self.history.extend(zip(self._queued, recs))
             self._queued = []
         for it, s in self.history:
+            if self.binary:
+                log.info("Binary validation of Iteration (%d/%d): logLoss %s auc %s accuracy %s (%d rows, %d positive)",
+                         it, n_iter, s.logLoss, s.auc, s.accuracy, s.n_rows, s.n_pos)
+                continue
             log.info("Validation of Iteration (%d/%d): mae %s rmse %s bias %s (%d rows, %d without a learned feature)",
                      it, n_iter, s.mae, s.rmse, s.bias, s.n_rows, s.n_unlearned)
 
@@ -835,7 +908,7 @@ def _log_losses(ctx, e0, iters, n_splits, n_iter):
 
 
 def run_minibatch_sgd_splits(ctx: FMContext, data, step_size: float, reg_param: float, n_iter: int | None = None,
-                             bufs: list | None = None, validation: "_Validation | None" = None):
+                             bufs: list | None = None, validation=None):
     """The foldLeft of runMiniBatchSGD (FactorizationMachinesSGD.scala:114-211) over a dataset kept on
     the device laid out split after split (`data`, FMContext.batch_splits: dfData.cache() at :93 with
     the randomSplit splits of :111-112 in iteration order): iteration i steps split i in place
@@ -845,7 +918,8 @@ def run_minibatch_sgd_splits(ctx: FMContext, data, step_size: float, reg_param: 
     written in iteration order after the loop.  n_iter: the iterations are splits 0 .. n_iter - 1
     (default: every split; fit's dataset ends with a split of the rows no iteration samples and
     passes maxIter).  `bufs`: a list of two views (or Nones) to re-point and leave open for the
-    caller.  `validation` (fit's setValidationData): its frame is evaluated between the steps it names,
+    caller.  `validation` (fit's setValidationData / setBinaryValidationData: a _Validation or a list of them):
+    each one's frame is evaluated between the steps it names,
     on the main stream behind the step -- enqueued only on a single-table context (the records are
     read once, after the loop), synchronously on a multi-GPU one; its log lines follow the loss
     lines.  Returns the loss sums of the executed iterations."""
@@ -854,6 +928,7 @@ def run_minibatch_sgd_splits(ctx: FMContext, data, step_size: float, reg_param: 
     if n_iter > len(sizes):
         raise ValueError("n_iter exceeds the dataset's splits")
     work = [i for i in range(n_iter) if sizes[i] > 0]
+    validations = [] if validation is None else [validation] if isinstance(validation, _Validation) else list(validation)
     own = bufs is None
     if own:
         bufs = [None, None]
@@ -871,12 +946,13 @@ def run_minibatch_sgd_splits(ctx: FMContext, data, step_size: float, reg_param: 
         if j + 1 < len(work):
             view(j + 1)  # re-points the batch step j - 1 read (its sort waits for that step)
             bufs[(j + 1) % nb].prepare()  # sorted on the side stream while this step runs
-        if validation is not None and validation.due(j + 1, len(work)):
-            validation.evaluate(ctx, i + 1, sync=ctx.parallel is not None)
+        for v in validations:
+            if v.due(j + 1, len(work)):
+                v.evaluate(ctx, i + 1, sync=ctx.parallel is not None)
     ctx.sync()
     out = _log_losses(ctx, e0, work, n_iter, n_iter)
-    if validation is not None:
-        validation.finish(ctx, n_iter)
+    for v in validations:
+        v.finish(ctx, n_iter)
     if own:
         for b in bufs:
             if b is not None:

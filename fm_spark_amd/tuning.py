@@ -20,11 +20,12 @@ import itertools
 
 import numpy as np
 
+from .engine import BinarySums
 from .ml import DataFrame, Param
 from .sampler import next_doubles
 
 __all__ = ["Param", "ParamGridBuilder", "CrossValidator", "CrossValidatorModel", "RegressionEvaluator", "RankingEvaluator",
-           "ranking_metric", "k_fold"]
+           "BinaryClassificationEvaluator", "binary_sums", "ranking_metric", "k_fold"]
 
 
 def java_string_hash(s: str) -> int:
@@ -132,6 +133,86 @@ class RegressionEvaluator:
             return float(s.rmse)
         y = np.asarray(dataset[model._params["labelCol"]], dtype=np.float64)
         return float(s.r2(float(np.sum((y - y.mean()) ** 2))))
+
+
+def binary_sums(score, label) -> BinarySums:
+    """The binary record (engine.BinarySums, epoch 0) of scores read as logits against labels, in NumPy,
+    with the device's definitions (include/fm_hip.h, fm_binary_out): positive where label > 0.5, predicted
+    positive where score > 0, the log loss term max(s, 0) + log1p(exp(-|s|)) - label * s, and two_u over the
+    ascending scores: a run [s, e) of equal scores with cp positives / A negatives before a position adds
+    (cp[e] - cp[s]) (A[s] + A[e]).  -0.0 and +0.0 are one score."""
+    s = np.asarray(score, dtype=np.float64) + 0.0
+    y = np.asarray(label, dtype=np.float64)
+    if s.shape != y.shape or s.ndim != 1:
+        raise ValueError("score and label must be 1-d arrays of one length")
+    n = len(s)
+    pos = y > 0.5
+    hit = s > 0.0
+    with np.errstate(over="ignore", invalid="ignore"):
+        loss = float(np.sum(np.maximum(s, 0.0) + np.log1p(np.exp(-np.abs(s))) - y * s)) if n else 0.0
+    order = np.argsort(s, kind="stable")
+    ss, sp = s[order], pos[order]
+    cp = np.concatenate([[0], np.cumsum(sp, dtype=np.int64)])
+    heads = np.flatnonzero(np.concatenate([[True], ss[1:] != ss[:-1]])) if n else np.zeros(0, np.int64)
+    ends = np.concatenate([heads[1:], [n]]).astype(np.int64) if n else heads
+    two_u = sum(int(cp[e] - cp[b]) * int((b - cp[b]) + (e - cp[e])) for b, e in zip(heads.tolist(), ends.tolist()))
+    return BinarySums(n, int(pos.sum()), 0, int(np.sum(pos & hit)), int(np.sum(~pos & hit)), int(two_u), loss)
+
+
+class BinaryClassificationEvaluator:
+    """org.apache.spark.ml.evaluation.BinaryClassificationEvaluator's shape over a raw score read as a
+    logit: metricName areaUnderROC (default; exact, ties counted as half), logLoss (mean softplus(score) -
+    label * score) or accuracy (score > 0 against label > 0.5).
+
+    ``evaluate(frame)`` runs in NumPy over rawPredictionCol (default "rawPrediction") and labelCol.  Only a
+    model fitted with loss "logistic" writes ``rawPrediction`` in transform; a squared model's frame has none
+    and evaluate raises the frame's own missing-column error -- its ``prediction`` is clamped to [minLabel,
+    maxLabel], which is no logit, though setRawPredictionCol("prediction") will rank by it for areaUnderROC
+    (ties wherever the clamp binds).  ``evaluateModel(model, frame)`` asks the device
+    (model.evaluateBinary -> fm_evaluate_binary), which scores every model by its unclamped score; for a
+    logistic model the two agree in the integers and differ in logLoss by the summation order only."""
+
+    def __init__(self):
+        self._params = {"metricName": "areaUnderROC", "rawPredictionCol": "rawPrediction", "labelCol": "label"}
+
+    def setMetricName(self, v):
+        if v not in ("areaUnderROC", "logLoss", "accuracy"):
+            raise ValueError(f"unsupported metric {v!r}")
+        self._params["metricName"] = v
+        return self
+
+    def setRawPredictionCol(self, v):
+        self._params["rawPredictionCol"] = v
+        return self
+
+    def setLabelCol(self, v):
+        self._params["labelCol"] = v
+        return self
+
+    def getMetricName(self):
+        return self._params["metricName"]
+
+    def getRawPredictionCol(self):
+        return self._params["rawPredictionCol"]
+
+    def getLabelCol(self):
+        return self._params["labelCol"]
+
+    def isLargerBetter(self) -> bool:
+        return self._params["metricName"] != "logLoss"
+
+    def metric(self, sums: BinarySums) -> float:
+        """this evaluator's metric of a record"""
+        m = self._params["metricName"]
+        return float(sums.auc if m == "areaUnderROC" else sums.logLoss if m == "logLoss" else sums.accuracy)
+
+    def evaluate(self, dataset: DataFrame) -> float:
+        return self.metric(binary_sums(dataset[self._params["rawPredictionCol"]], dataset[self._params["labelCol"]]))
+
+    def evaluateModel(self, model, dataset: DataFrame) -> float:
+        """The metric from the record the device forms (model.evaluateBinary): no score column is built.
+        The model's labelCol is the label."""
+        return self.metric(model.evaluateBinary(dataset))
 
 
 RANKING_METRICS = ("ndcgAtK", "precisionAtK", "recallAtK", "hitRateAtK", "meanAveragePrecision", "meanReciprocalRank",

@@ -209,7 +209,10 @@ int fm_sync(fm_ctx* ctx);
  * row_ptr (28 bytes per result row) and the scan's per-chunk sums, sized by the largest call.  The
  * _lists forms of these calls (fm_rank_batch_select_lists, fm_rank_positions_batch_lists,
  * fm_batch_sample_pairs_lists) keep no list copies in the context's scratch: they read the fm_lists'
- * own buffers, and the rest of their scratch is the host-list forms'. */
+ * own buffers, and the rest of their scratch is the host-list forms'.  Nor is the scratch of
+ * fm_binary_metrics / fm_evaluate_binary*: the scores (and fm_binary_metrics' labels), the sort's keys and
+ * payloads before and after the re-key, the flags and their scan (44 bytes per row, 52 with the labels), the per-block
+ * partials and a sort workspace of the stage's own (24 bytes per row), sized by the largest call. */
 int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz);
 
 /* ---- tables (C9: Strength / FactorizedInteraction, Model.scala:275-289) ------------ */
@@ -461,6 +464,57 @@ int fm_evaluate(fm_ctx* ctx, const fm_csr* csr, double min_label, double max_lab
 int fm_evaluate_batch(fm_ctx* ctx, fm_batch* batch, double min_label, double max_label, double* pred,
                       fm_eval_out* out);
 int fm_eval_history(fm_ctx* ctx, fm_eval_out* out, int64_t cap, int64_t* n);
+/* Binary evaluation on the device: what a click model is chosen by -- log loss and the area under the ROC
+ * curve -- and the confusion counts at the threshold score > 0 (sigma(score) > 0.5), from a per-row score
+ * and the labels, without downloading the scores.
+ *   score : fm_predict's value with the bounds -inf / +inf: the unclamped yhat, w0 for a row without a
+ *           learned entry (ids >= num_features or absent dropped, lazy L1 caught up on read).  Whatever
+ *           fm_config.loss the context trains with, the score is read as a logit.
+ *   label : positive where label > 0.5 (BinaryLabelCounter's rule; 0.5 itself is negative).  The log loss
+ *           term softplus(score) - label * score takes the label as given: labels are not checked, and a
+ *           fractional label is a soft target there, as in the logistic step.
+ *   two_u : twice the Mann-Whitney U of the positives' scores over the negatives': 2 per (positive,
+ *           negative) pair the positive wins, 1 per tied pair; AUC = two_u / (2 n_pos n_neg).  Computed in
+ *           integers over the fully sorted scores (two stable radix sorts of the scores' 64-bit images, a
+ *           scan of the positive flags, one term per run of equal scores): exact, not binned, and bit for
+ *           bit reproducible.  -0.0 and +0.0 are one score.  The order of NaN scores is unspecified.
+ *           All rows of one class: two_u = 0 (the AUC is undefined: 0 / 0).
+ *   sums  : sum_log_loss in fp64, reduced in a fixed order (per thread, per block, one fold), no atomics:
+ *           two evaluations of the same batch on the same table give bitwise equal records.
+ *   fm_binary_metrics : the same record over n host scores and labels from any model (1 <= n < 2^31; n = 0:
+ *           FM_NOTHING_TO_DO, *out zeroed).  Synchronous; appends nothing to the history; epoch = fm_epoch().
+ *   fm_evaluate_binary[_batch] : score is an optional host buffer of n_rows doubles, bit for bit
+ *           fm_predict[_batch](-inf, +inf)'s.  Every evaluation of a non-empty batch appends one record to
+ *           the context's binary evaluation history (fm_eval_binary_history, its own: the regression
+ *           history of fm_eval_history is untouched), kept on the device until asked for.
+ *           fm_evaluate_binary_batch with out == NULL and score == NULL only enqueues (no host
+ *           synchronisation); out == NULL with score != NULL is FM_ERR_ARG.  fm_eval_binary_history waits
+ *           for the main stream; call it with cap 0 to size.
+ *   order : on the main stream behind every queued step; a batch refilled by fm_batch_from_rows is
+ *           waited for.  The table, the epoch, the loss history, the regression evaluation history and
+ *           fm_last_stats are unchanged.
+ *   arguments : zero rows: FM_NOTHING_TO_DO, *out zeroed, nothing appended.  A dataset made by
+ *           fm_batch_create_splits is FM_ERR_ARG (its split views are accepted).  A null or foreign batch
+ *           is FM_ERR_ARG.  Any single-table context is accepted, whatever its loss; a multi-GPU context
+ *           or shard_count > 1 is FM_ERR_ARG (the message names the call).
+ *   memory: the history starts at 4096 records of 64 bytes and doubles; the scratch (scores, keys, flags,
+ *           scan arrays, a sort workspace of the stage's own) is kept with the context and grows to the
+ *           largest call: two equal calls leave fm_device_bytes_live / fm_device_allocs_live equal.
+ * Profile names: "evaluate_binary" (the score pass through the fold), and inside it "binary_sort" and
+ * "binary_count" (the flags' scan, the pair count, the fold). */
+typedef struct fm_binary_out {
+  int64_t n_rows;   /* rows evaluated; n_neg = n_rows - n_pos */
+  int64_t n_pos;    /* rows with label > 0.5 */
+  int64_t epoch;    /* fm_epoch() when the evaluation was enqueued */
+  int64_t tp;       /* score > 0 among the positives */
+  int64_t fp;       /* score > 0 among the negatives */
+  int64_t two_u;    /* AUC = two_u / (2 n_pos n_neg) */
+  double sum_log_loss; /* sum softplus(score) - label * score -> logLoss = / n_rows */
+} fm_binary_out;
+int fm_binary_metrics(fm_ctx* ctx, const double* score, const double* label, int64_t n, fm_binary_out* out);
+int fm_evaluate_binary(fm_ctx* ctx, const fm_csr* csr, double* score, fm_binary_out* out);
+int fm_evaluate_binary_batch(fm_ctx* ctx, fm_batch* batch, double* score, fm_binary_out* out);
+int fm_eval_binary_history(fm_ctx* ctx, fm_binary_out* out, int64_t cap, int64_t* n);
 /* Top-N ranking, the serving side of transform (the shape of ALSModel.recommendForUserSubset): for
  * every row of `contexts` (a user and their history, a page view) the n_top rows of `candidates`
  * (movies, ads) with the largest FM score of the two rows' entries taken together, without
