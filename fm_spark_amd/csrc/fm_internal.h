@@ -328,6 +328,25 @@ struct UpdGeometry {
   int32_t scan_round_chunks;  // split chunks k_split_scan takes per round
 };
 UpdGeometry update_geometry(int kp);
+// The same kind of seam for the sharded step's own kernels (fm_shard.hip; tests/native/shard_probe.hip):
+// the sizes at which a route, pair-table, combine or pack kernel takes another tile, trip or grid-stride
+// sweep, read from the constants its launches use.  No kernel reads it.
+struct ShardGeometry {
+  int32_t pair_tile;       // samples per tile of the pair numbering (k_pair_count / k_pair_index: one block)
+  int32_t route_team;      // lanes per sample of k_sample_mask
+  int64_t mask_sweep;      // samples one grid-stride sweep of k_sample_mask takes
+  int32_t scan_trip;       // tiles one trip of k_rows_scan takes
+  int64_t route_sweep;     // entries one sweep of k_route_keys takes at unroll step 0 (u >= 1 starts beyond them)
+  int32_t route_unroll;    // entries a k_route_keys thread takes per sweep
+  int64_t table_sweep;     // the same of k_pair_table
+  int32_t table_unroll;
+  int32_t slot_regs;       // up to this many owners the combine keeps a sample's pair slots in registers
+  int32_t max_r;           // the most ranks
+  int32_t combine_team;    // at this kp: lanes per sample of k_shard_combine / predict / evaluate
+  int64_t combine_sweep;   // at this kp: samples one grid-stride sweep of them takes
+  int64_t pack_sweep;      // at this kp: pairs one sweep of k_pack_srec takes (0: no packed record at this kp)
+};
+ShardGeometry shard_geometry(int kp);
 // replicated mode: apply the all-reduced gradient sums grad[rows][kp + 4] to every touched row;
 // the number of touched rows -> *n_touched (device, fp64 stats slot), through per-block counts in
 // blk_touched[kReplApplyBlocks]

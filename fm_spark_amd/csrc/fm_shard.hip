@@ -48,6 +48,9 @@ namespace fmhip {
 namespace {
 
 constexpr int kMaxR = 64;     // owner masks are uint64
+// the most blocks of the streaming kernels here (k_sample_mask, k_route_keys, k_key_slots, k_pair_table,
+// k_pack_srec): beyond it a block takes further sweeps.  The launches and shard_geometry both read it.
+constexpr int64_t kShardGrid = 256 * 16;
 
 __device__ __forceinline__ uint32_t incl_scan_u32(uint32_t v, int lane) {
 #pragma unroll
@@ -106,13 +109,13 @@ __global__ __launch_bounds__(kBlock) void k_sample_mask(const int64_t* __restric
 // send buffers.  Ids >= F get owner R: they sort after every owner's block and are not sent.  One
 // lane per entry: the exploded entry {sample, x} names its sample, so the pass streams the id and
 // entry arrays without the CSR row walk (neighbouring lanes share a sample's pair indices).
+constexpr int kRkU = 4;  // entries a thread takes per sweep
 __global__ __launch_bounds__(kBlock) void k_route_keys(const uint32_t* __restrict__ col, const uint2* __restrict__ ent,
                                                        int64_t N, uint32_t R, int sb, uint64_t F,
                                                        const int32_t* __restrict__ pairidx, uint32_t* __restrict__ key,
                                                        uint2* __restrict__ pay) {
   // kRkU entries per thread at once: their ids and entries, then their pair indices, each a single
   // round trip (clamped indices)
-  constexpr int kRkU = 4;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t e0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; e0 < N; e0 += kRkU * stride) {
     uint32_t id[kRkU];
@@ -247,13 +250,13 @@ __global__ __launch_bounds__(kBlock) void k_pair_index(const uint64_t* __restric
 // index within that source's block: ent2 = {pair = pbase[source] + local, x}, and the first
 // entry of every pair opens it in pair_ptr (one pass, no scan).
 // ent2 == nullptr (one source: its pairs start at 0, so ent2 would equal ent): the pair table only.
+constexpr int kPtU = 4;  // entries a thread takes per sweep
 __global__ __launch_bounds__(kBlock) void k_pair_table(const uint2* __restrict__ ent, int64_t n,
                                                        const int64_t* __restrict__ src_off,
                                                        const int64_t* __restrict__ pbase, int R,
                                                        int64_t* __restrict__ pair_ptr, uint2* __restrict__ ent2) {
   // the source offsets and pair bases in LDS (a loop of dependent global loads per entry otherwise);
   // an entry and its predecessor loaded together (clamped index), kPtU entries per thread at once
-  constexpr int kPtU = 4;
   __shared__ int64_t so[kMaxR + 1], pb[kMaxR];
   for (int t = threadIdx.x; t <= R; t += kBlock) so[t] = src_off[t];
   for (int t = threadIdx.x; t < R; t += kBlock) pb[t] = pbase[t];
@@ -725,7 +728,7 @@ void shard_route_launch(fm_ctx* ctx, fm_batch* b, void* send_slot, void* send_en
   const uint64_t F = (uint64_t)ctx->cfg.num_features;
   const bool drop = b->max_id >= (int64_t)F;  // a predict batch with ids outside the model
   if (B > 0) {
-    hipLaunchKernelGGL(k_sample_mask, dim3(grid_for(B * kTeamR, kBlock)), dim3(kBlock), 0, st, b->dev.row_ptr.as<int64_t>(),
+    hipLaunchKernelGGL(k_sample_mask, dim3(grid_for(B * kTeamR, kBlock, kShardGrid)), dim3(kBlock), 0, st, b->dev.row_ptr.as<int64_t>(),
                        b->dev.col.as<uint32_t>(), B, (uint32_t)R, F, ctx->sh_mask.as<uint64_t>(), tot + R);
     hipLaunchKernelGGL(k_pair_count, dim3((unsigned)ntiles), dim3(kBlock), 0, st, ctx->sh_mask.as<uint64_t>(), B,
                        R, ntiles, ctx->sh_tcnt.as<uint32_t>());
@@ -745,18 +748,18 @@ void shard_route_launch(fm_ctx* ctx, fm_batch* b, void* send_slot, void* send_en
     if (R == 1 && !drop) {
       // one owner: CSR order is already the owner order and the key is the slot -- the keys and
       // payloads go straight to the send buffers, no partition pass
-      hipLaunchKernelGGL(k_route_keys, dim3(grid_for(N, kBlock)), dim3(kBlock), 0, st, b->dev.col.as<uint32_t>(),
+      hipLaunchKernelGGL(k_route_keys, dim3(grid_for(N, kBlock, kShardGrid)), dim3(kBlock), 0, st, b->dev.col.as<uint32_t>(),
                          b->dev.ent.as<uint2>(), N, (uint32_t)R, sb, F, S.pairidx.as<int32_t>(),
                          reinterpret_cast<uint32_t*>(send_slot), reinterpret_cast<uint2*>(send_ent));
     } else {
       ctx->sh_pay.ensure(sizeof(uint2) * std::max<int64_t>(N, 4) + 16);
       ctx->sh_skey.ensure(sizeof(uint32_t) * std::max<int64_t>(N, 4) + 16);
-      hipLaunchKernelGGL(k_route_keys, dim3(grid_for(N, kBlock)), dim3(kBlock), 0, st, b->dev.col.as<uint32_t>(),
+      hipLaunchKernelGGL(k_route_keys, dim3(grid_for(N, kBlock, kShardGrid)), dim3(kBlock), 0, st, b->dev.col.as<uint32_t>(),
                          b->dev.ent.as<uint2>(), N, (uint32_t)R, sb, F, S.pairidx.as<int32_t>(),
                          ctx->sh_okey.as<uint32_t>(), ctx->sh_pay.as<uint2>());
       radix_sort_pairs64_bits(ctx->route_sort, ctx->sh_okey.as<uint32_t>(), ctx->sh_pay.as<uint2>(), N, sb, sb + ob, st,
                               ctx->sh_skey.as<uint32_t>(), reinterpret_cast<uint2*>(send_ent));
-      hipLaunchKernelGGL(k_key_slots, dim3(grid_for(N, kBlock)), dim3(kBlock), 0, st, ctx->sh_skey.as<uint32_t>(), N,
+      hipLaunchKernelGGL(k_key_slots, dim3(grid_for(N, kBlock, kShardGrid)), dim3(kBlock), 0, st, ctx->sh_skey.as<uint32_t>(), N,
                          (uint32_t)((sb >= 32) ? 0xFFFFFFFFu : ((1u << sb) - 1u)), reinterpret_cast<uint32_t*>(send_slot));
     }
   }
@@ -829,7 +832,7 @@ int fm_shard_owner_prepare(fm_ctx* ctx, fm_batch* b, const void* recv_slot, cons
         ctx->sh_ent2.ensure(sizeof(uint2) * n);
         ent2 = ctx->sh_ent2.as<uint2>();
       }
-      hipLaunchKernelGGL(k_pair_table, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, reinterpret_cast<const uint2*>(recv_ent),
+      hipLaunchKernelGGL(k_pair_table, dim3(grid_for(n, kBlock, kShardGrid)), dim3(kBlock), 0, st, reinterpret_cast<const uint2*>(recv_ent),
                          n, S.src_off.as<int64_t>(), S.src_off.as<int64_t>() + (R + 1), R, pair_ptr,
                          R > 1 ? ctx->sh_ent2.as<uint2>() : nullptr);
       FM_HIP_CHECK(hipGetLastError());
@@ -979,7 +982,7 @@ int fm_shard_owner_update(fm_ctx* ctx, fm_batch* b, const void* s_recv, int32_t 
       const int rec = s_rec_floats(kp);
       ctx->work.S.ensure(sizeof(float) * (size_t)S.P * rec);
       const int64_t nq = S.P * (rec / 4);
-      hipLaunchKernelGGL(k_pack_srec, dim3(grid_for(nq, kBlock)), dim3(kBlock), 0, st, Srow, src.yl, S.P, kp, rec,
+      hipLaunchKernelGGL(k_pack_srec, dim3(grid_for(nq, kBlock, kShardGrid)), dim3(kBlock), 0, st, Srow, src.yl, S.P, kp, rec,
                          ctx->work.S.as<float>());
       FM_HIP_CHECK(hipGetLastError());
       src = SegSource{ctx->work.S.as<float>(), rec, reinterpret_cast<const float2*>(ctx->work.S.as<float>() + kp), rec / 2};
@@ -1002,3 +1005,25 @@ int fm_shard_owner_update(fm_ctx* ctx, fm_batch* b, const void* s_recv, int32_t 
 }
 
 }  // extern "C"
+
+namespace fmhip {
+
+ShardGeometry shard_geometry(int kp) {
+  ShardGeometry g{};
+  g.pair_tile = kBlock;
+  g.route_team = kTeamR;
+  g.mask_sweep = kShardGrid * (kBlock / kTeamR);
+  g.scan_trip = kBlock;
+  g.route_sweep = kShardGrid * kBlock;
+  g.route_unroll = kRkU;
+  g.table_sweep = kShardGrid * kBlock;
+  g.table_unroll = kPtU;
+  g.slot_regs = kSlotRegs;
+  g.max_r = kMaxR;
+  g.combine_team = team_for(kp / 4);
+  g.combine_sweep = (int64_t)kLossPartBlocks * (kBlock / g.combine_team);
+  g.pack_sweep = s_rec_yl(kp) ? kShardGrid * kBlock / (s_rec_floats(kp) / 4) : 0;
+  return g;
+}
+
+}  // namespace fmhip

@@ -4,9 +4,13 @@ math and the same fp32 wire formats, so the exchange protocol of
 fm_spark_amd.distributed.ShardedTrainer can run on CPU under gloo."""
 
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
+
+# NumpyShardEngine.combine_exact's result, per sample (pair_sample: per pair)
+CombineRef = namedtuple("CombineRef", "S yhat r sum_a2 abs_vv abs_wx pair_sample has_pair")
 
 
 def rows_to_soa(rows, kp):
@@ -56,10 +60,16 @@ class NumpyShardEngine:
 
     # requester -------------------------------------------------------------------
     def route(self, b):
+        """Ids >= F (a predict batch's ids outside the model) belong to no owner: they are absent from
+        the masks, counts and send buffers, and a row holding only such ids has no pair."""
         csr = b.csr
         ids = csr.col.astype(np.int64)
-        owner = ids % self.R
         sample = np.repeat(np.arange(csr.n_rows), np.diff(csr.row_ptr))
+        val = csr.val
+        inside = ids < self.F
+        if not inside.all():
+            ids, sample, val = ids[inside], sample[inside], val[inside]
+        owner = ids % self.R
         order = np.argsort(owner, kind="stable")
         send_slot = (ids[order] // self.R).astype(np.int32)
         ents = np.bincount(owner, minlength=self.R)
@@ -70,7 +80,7 @@ class NumpyShardEngine:
         b.pairs_out = pairs
         # wire entry = {index of its (sample, owner) pair within this rank's pairs to the owner, x}
         local = b.pairidx[sample[order], owner[order]].astype(np.uint32)
-        ent = np.stack([local, csr.val[order].astype(np.float32).view(np.uint32)], axis=1)
+        ent = np.stack([local, val[order].astype(np.float32).view(np.uint32)], axis=1)
         counts = np.concatenate([ents, pairs]).astype(np.int64)
         return torch.from_numpy(send_slot), torch.from_numpy(ent.view(np.int32).reshape(-1).copy()), counts
 
@@ -91,7 +101,7 @@ class NumpyShardEngine:
             vv[m] += rows[:, kp]
             wx[m] += rows[:, kp + 1]
         yhat = 0.5 * (np.sum(S * S, axis=1) - vv) + wx + self.w0
-        has = np.diff(csr.row_ptr) > 0
+        has = (b.pairidx >= 0).any(axis=1)  # a row with a pair (every entry outside the model: none)
         d = (yhat - csr.label)[has]
         b.loss = (float(np.sum(d * d)), int(has.sum()))
         out = np.zeros((int(n_pairs_out), kp + 2), dtype=np.float64)
@@ -103,7 +113,76 @@ class NumpyShardEngine:
             out[poff[o] + ix[m], kp + 1] = yhat[m]
         return torch.from_numpy(rows_to_soa(out, kp))
 
+    def combine_exact(self, b, vec, sc, label=None):
+        """The combine of arbitrary given partials, for a check of the kernel word by word: vec [Ps][kp]
+        and sc [Ps][2] (fp32 or fp64 words, the pairs in owner blocks as route numbered them).
+        Returns a CombineRef over the batch's samples: S, the fp64 sum in owner order rounded once to fp32
+        (what every pair of the sample must get, bit for bit); yhat and r = yhat - label as np.longdouble
+        (the squares and the sums carried in it, nothing rounded to fp32); and the magnitudes an error bound
+        needs: sum_a2 = sum of the squared S columns, abs_vv = sum over owners of |sum v^2 x^2|, abs_wx
+        likewise; pair_sample [Ps]: the sample of every pair."""
+        kp, B, L = self.kp, b.csr.n_rows, np.longdouble
+        vec = np.asarray(vec).reshape(-1, kp).astype(np.float64)
+        sc = np.asarray(sc).reshape(-1, 2).astype(np.float64)
+        label = b.csr.label if label is None else np.asarray(label, dtype=np.float64)
+        poff = np.concatenate([[0], np.cumsum(b.pairs_out)])
+        assert len(vec) == len(sc) == poff[-1]
+        S = np.zeros((B, kp))
+        vv, wx, avv, awx = (np.zeros(B, dtype=L) for _ in range(4))
+        pair_sample = np.full(int(poff[-1]), -1, dtype=np.int64)
+        for o in range(self.R):  # owner order, fp64 adds: nothing is reassociated
+            ix = b.pairidx[:, o]
+            m = ix >= 0
+            p = poff[o] + ix[m]
+            S[m] += vec[p]
+            vv[m] += sc[p, 0]
+            wx[m] += sc[p, 1]
+            avv[m] += np.abs(sc[p, 0])
+            awx[m] += np.abs(sc[p, 1])
+            pair_sample[p] = np.nonzero(m)[0]
+        assert (pair_sample >= 0).all()
+        a2 = (S.astype(L) ** 2).sum(axis=1)
+        yhat = L(0.5) * (a2 - vv) + wx + L(self.w0)
+        return CombineRef(S.astype(np.float32), yhat, yhat - label.astype(L), a2, avv, awx, pair_sample,
+                          (b.pairidx >= 0).any(axis=1))
+
     # owner -----------------------------------------------------------------------
+    def owner_forward_exact(self, recv_slot, recv_ent, src_entries, src_pairs):
+        """The owner's partial sums of received entries, for a check of the kernel word by word.  The
+        pair of an entry is its source's pair offset plus the local index it carries (the wire's rule,
+        not a guess from where the index changes).  Returns (vec [P][kp], sc [P][2], abs_vec, abs_sc,
+        n [P]) as np.longdouble: the three sums {sum v x | sum v^2 x^2, sum w x} per pair, the sums of
+        their terms' absolute values, and the pair's entries.  Table rows absent from the model
+        contribute nothing."""
+        L = np.longdouble
+        slots = np.asarray(recv_slot).astype(np.int64).reshape(-1)
+        ent = np.ascontiguousarray(np.asarray(recv_ent)).view(np.uint32).reshape(-1, 2)
+        src_entries, src_pairs = np.asarray(src_entries, dtype=np.int64), np.asarray(src_pairs, dtype=np.int64)
+        n, P = len(slots), int(src_pairs.sum())
+        assert n == int(src_entries.sum()) == len(ent)
+        vec, avec = np.zeros((P, self.kp), dtype=L), np.zeros((P, self.kp), dtype=L)
+        sc, asc = np.zeros((P, 2), dtype=L), np.zeros((P, 2), dtype=L)
+        cnt = np.zeros(P, dtype=np.int64)
+        if n == 0:
+            return vec, sc, avec, asc, cnt
+        pbase = np.concatenate([[0], np.cumsum(src_pairs)])
+        pair = pbase[np.repeat(np.arange(self.R), src_entries)] + ent[:, 0].astype(np.int64)
+        x = ent[:, 1].view(np.float32).astype(L)
+        assert (np.diff(pair) >= 0).all() and pair[0] == 0 and pair[-1] == P - 1 and (np.diff(pair) <= 1).all()
+        start = np.nonzero(np.diff(pair, prepend=-1))[0]  # every pair's first entry
+        here = self.present[slots]
+        V = np.where(here[:, None], self.V[slots], 0.0).astype(L)
+        w = np.where(here, self.w[slots], 0.0).astype(L)
+        tv = V * x[:, None]
+        tq = (V * V).sum(axis=1) * x * x
+        tw = w * x
+        vec[:, : self.k] = np.add.reduceat(tv, start, axis=0)
+        avec[:, : self.k] = np.add.reduceat(np.abs(tv), start, axis=0)
+        sc[:, 0], sc[:, 1] = np.add.reduceat(tq, start), np.add.reduceat(tw, start)
+        asc[:, 0], asc[:, 1] = np.add.reduceat(np.abs(tq), start), np.add.reduceat(np.abs(tw), start)
+        cnt[:] = np.diff(start, append=n)
+        return vec, sc, avec, asc, cnt
+
     def owner_prepare(self, b, recv_slot, recv_ent, src_entries, src_pairs):
         b.recv_in = (recv_slot.clone(), recv_ent.clone(), np.asarray(src_entries), np.asarray(src_pairs))
 

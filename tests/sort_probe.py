@@ -6,7 +6,8 @@ radix_sort_pairs64_bits of the built library directly.  __graft_entry__.build() 
 build_probe() after the library; the tests only load what was built.  The same library carries a
 second source, tests/native/forward_probe.hip: the door to the forward's launch-size seam
 (tests/forward_probe.py wraps it), and a third, tests/native/update_probe.hip: the door to the update
-side's geometry seam (tests/update_probe.py wraps it).
+side's geometry seam (tests/update_probe.py wraps it), and a fourth, tests/native/shard_probe.hip: the
+door to the sharded step's geometry seam (tests/shard_probe.py wraps it).
 """
 
 from __future__ import annotations
@@ -23,8 +24,9 @@ HERE = Path(__file__).resolve().parent
 ROOT = HERE.parent
 SRC = HERE / "native" / "sort_probe.hip"
 # the same library carries the forward's launch-size door (tests/forward_probe.py) and the update
-# side's geometry door (tests/update_probe.py)
-SRCS = [SRC, HERE / "native" / "forward_probe.hip", HERE / "native" / "update_probe.hip"]
+# side's geometry door (tests/update_probe.py) and the sharded step's (tests/shard_probe.py)
+SRCS = [SRC, HERE / "native" / "forward_probe.hip", HERE / "native" / "update_probe.hip",
+        HERE / "native" / "shard_probe.hip"]
 LIB_DIR = ROOT / "fm_spark_amd" / "lib"
 PROBE = LIB_DIR / "libfm_sort_probe.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -249,6 +249,40 @@ def test_group_sharded_predict_matches_oracle(gpu, R, transport):
     ctx.close()
 
 
+@pytest.mark.parametrize("k", [3, 33])
+def test_group_sharded_r16_steps_and_predict(gpu, k):
+    """The most ranks one context takes (FM_MAX_LOCAL = 16; R = 13..16 ran nowhere else): two steps against
+    the oracle, then a transform with ids >= F -- at a power-of-two R the dropped bucket takes one more owner
+    bit of the route key -- and rows left without a learned feature.  k = 3 and k = 33: the requester's
+    narrowest and widest team (one lane, and sixteen)."""
+    R, F, w0 = 16, 16 * 32 + 1, 0.25
+    _, _, w, V = make_problem(5, 1, F, k, 1)
+    present = np.sort(np.random.default_rng(2).choice(F, size=400, replace=False)).astype(np.int32)
+    ctx = _ctx(F, k, R, w0=w0)
+    ctx.load_tables(present, w[present], V[present])
+    model = R_.Model.empty(F, k, w0=w0)
+    model.load(present, w[present], V[present])
+    for t in (1, 2):
+        p = make_problem(70 + t, 300 + 11 * t, F - 60, k, 9, hot=7)[0]  # the last 60 ids are never trained
+        o = ctx.step(_host(p), t, 0.3, 1e-4)
+        ref = R_.sgd_step_fast(model, p, t, 0.3, 1e-4)
+        assert o.loss_sum == pytest.approx(ref.loss_sum, rel=1e-5)
+        assert (o.n_rows, o.n_loss_rows, o.n_unique) == (ref.n_rows, ref.n_loss_rows, ref.n_unique)
+    _check_tables(ctx, model)
+    p = make_problem(6, 300, F + 40, k, 6, empty_frac=0.15)[0]  # ids up to F + 39: some outside
+    lone = np.nonzero(~model.present)[0][:3]  # a row holding only absent ids
+    assert len(lone) == 3 and (p.col >= F).any()
+    rp = np.concatenate([p.row_ptr, [p.row_ptr[-1] + len(lone)]]).astype(np.int64)
+    csr = R_.CSR(rp, np.concatenate([p.col, lone]).astype(np.int32), np.concatenate([p.val, np.ones(len(lone))]),
+                 np.concatenate([p.label, [0.0]]))
+    for lo, hi in ((0.0, 1.0), (-math.inf, math.inf)):
+        got = ctx.predict(_host(csr), lo, hi)
+        ref = R_.predict(model, csr, lo, hi, num_features=F)
+        np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-7)
+    assert got[-1] == w0
+    ctx.close()
+
+
 def test_group_c3_r8_matches_single_table(gpu):
     """Config c3's table (100M hashed features, k = 16) sharded over R = 8 ranks of one context
     (COPY transport, every rank on this GPU): two iterations of 8 x 32K rows against the
