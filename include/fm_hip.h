@@ -243,7 +243,10 @@ int64_t fm_num_present(fm_ctx* ctx);
 int64_t fm_epoch(fm_ctx* ctx);
 
 /* ---- mini-batches --------------------------------------------------------------------- */
-/* Copy a CSR batch into device memory once (validated: ids in range, row_ptr monotone). */
+/* Copy a CSR batch into device memory once (validated: ids in range, row_ptr monotone).
+ * A feature id may occur more than once in a row; each occurrence is an entry of its own in the
+ * score, the gradients and fm_loss_grad's output, and is counted once in n_unique (fm_step's host
+ * batches alike). */
 int fm_batch_create(fm_ctx* ctx, const fm_csr* csr, fm_batch** out);
 /* Frees the batch's device memory once the work queued on it has run.  A batch may outlive its
  * context, also a multi-GPU context's (fm_destroy drains the context's streams; the batch's

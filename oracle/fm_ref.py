@@ -256,6 +256,8 @@ def sgd_step(model: Model, csr: CSR, t: int, step_size: float, reg_param: float)
         every present row: strength' = strength - deltaWiSum (0 if untouched)   (:171)
                            vec' = vec - deltaViSum                              (:172-175)
         L1 on every row: S_lambda(strength'), S_lambda(vec')     (:177-181)
+    A feature id may occur more than once in a row: each occurrence is an entry of its own (S and
+    sum v^2 x^2 take every one, g_w its -y once per entry) and the id counts once in n_unique.
     Rows touched by the batch but absent from the model would be created by the outer
     joins (:157-166); fit never produces them (createInitialModel covers every id)."""
     m = csr.n_rows
