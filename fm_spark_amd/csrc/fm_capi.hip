@@ -796,13 +796,15 @@ int fm_batch_from_rows(fm_ctx* ctx, const fm_batch* data, const int64_t* rows, i
     // a split view refilled as a selection: its borrowed pointers are dropped, its own buffers grown below
     b->detach_view();
     b->ensure_events(ctx->stream);
+    // the staging {rows, row_ptr} of this batch's previous selection has been copied out (a batch never
+    // refilled before has no staging in flight: its events are made and nothing is waited for, so the
+    // first refill returns once it is enqueued whatever the streams hold)
     if (!b->built) {
       FM_HIP_CHECK(hipEventCreateWithFlags(&b->built, hipEventDisableTiming));
       FM_HIP_CHECK(hipEventCreateWithFlags(&b->sel_copied, hipEventDisableTiming));
-      FM_HIP_CHECK(hipEventRecord(b->sel_copied, ctx->side));
+    } else {
+      FM_HIP_CHECK(hipEventSynchronize(b->sel_copied));
     }
-    // the staging {rows, row_ptr} of this batch's previous selection has been copied out
-    FM_HIP_CHECK(hipEventSynchronize(b->sel_copied));
     const size_t img = sizeof(int64_t) * (2 * (size_t)n + 1);
     b->sel_pin.ensure_slack(img);
     int64_t* hrows = reinterpret_cast<int64_t*>(b->sel_pin.p);
@@ -1814,10 +1816,11 @@ static int pair_row_ptr(const int64_t* urp, int64_t U, const int64_t* crp, int64
 static hipStream_t pair_refill_begin(fm_ctx* ctx, fm_batch* b) {
   b->detach_view();
   b->ensure_events(ctx->stream);
+  // (sel_copied is recorded only behind a staging copy, on the copy stream: fm_batch_sample_pairs stages
+  // nothing in the batch, and a wait for an event never recorded returns at once)
   if (!b->built) {
     FM_HIP_CHECK(hipEventCreateWithFlags(&b->built, hipEventDisableTiming));
     FM_HIP_CHECK(hipEventCreateWithFlags(&b->sel_copied, hipEventDisableTiming));
-    FM_HIP_CHECK(hipEventRecord(b->sel_copied, ctx->side));
   }
   if (!ctx->copy_stream) FM_HIP_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
   hipStream_t gs = ctx->copy_stream;

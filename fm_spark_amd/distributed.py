@@ -56,8 +56,7 @@ class HipShardEngine:
         self.side_stream = torch.cuda.Stream(self.device)
         self.ctx.set_stream(self.main_stream.cuda_stream)
         self._lib = N.load()
-        N.check(self._lib.fm_set_side_stream(self.ctx.handle, C.c_void_p(self.side_stream.cuda_stream)),
-                "fm_set_side_stream")
+        self.ctx.set_side_stream(self.side_stream.cuda_stream)
         self.kp = (k + 3) // 4 * 4
         self.width = self.kp + 2  # words per pair on the wire: [P][kp] vectors, then [P][2] scalars
 

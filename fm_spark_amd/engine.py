@@ -344,6 +344,11 @@ class FMContext:
         0 / None = the device's default (null) stream."""
         N.check(self._lib.fm_set_stream(self.handle, C.c_void_p(stream_ptr or None)), "fm_set_stream")
 
+    def set_side_stream(self, stream_ptr: int | None):
+        """Run the batch-only work (fm_batch_prepare, the inline sort, the sharded route and owner
+        prepare) on this hipStream_t (fm_set_side_stream); 0 / None = the context's own side stream."""
+        N.check(self._lib.fm_set_side_stream(self.handle, C.c_void_p(stream_ptr or None)), "fm_set_side_stream")
+
     def sync(self):
         N.check(self._lib.fm_sync(self.handle), "fm_sync")
 

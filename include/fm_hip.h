@@ -270,7 +270,8 @@ int fm_batch_prepare(fm_ctx* ctx, fm_batch* batch);
  * too, so the result is sized without a device read; the host pass runs on a pool of host threads).  *out == NULL: a new
  * batch is created; otherwise *out (a batch of this context, not data) is refilled in place.  The
  * gather runs on the context's copy stream behind every queued step, preparation and sharded
- * iteration that reads *out, and the host returns once it is enqueued (rows is copied); steps,
+ * iteration that reads *out, and the host returns once it is enqueued (rows is copied; the one host
+ * wait is for the staging copy of *out's previous refill -- a batch's first refill waits for nothing); steps,
  * fm_batch_prepare, fm_predict_batch and fm_init_from_batch on the result are ordered after it.
  * data must stay alive until the gather has run: fm_sync waits for the context's step, side and
  * copy streams.  A multi-GPU context splits the selected rows contiguously over its local ranks,

@@ -7,7 +7,9 @@ build_probe() after the library; the tests only load what was built.  The same l
 second source, tests/native/forward_probe.hip: the door to the forward's launch-size seam
 (tests/forward_probe.py wraps it), and a third, tests/native/update_probe.hip: the door to the update
 side's geometry seam (tests/update_probe.py wraps it), and a fourth, tests/native/shard_probe.hip: the
-door to the sharded step's geometry seam (tests/shard_probe.py wraps it).
+door to the sharded step's geometry seam (tests/shard_probe.py wraps it), and a fifth,
+tests/native/stream_probe.hip: the delay and the stream handles with which
+tests/test_gpu_stream_order.py holds one stream of a context back (tests/stream_probe.py wraps it).
 """
 
 from __future__ import annotations
@@ -24,9 +26,10 @@ HERE = Path(__file__).resolve().parent
 ROOT = HERE.parent
 SRC = HERE / "native" / "sort_probe.hip"
 # the same library carries the forward's launch-size door (tests/forward_probe.py) and the update
-# side's geometry door (tests/update_probe.py) and the sharded step's (tests/shard_probe.py)
+# side's geometry door (tests/update_probe.py), the sharded step's (tests/shard_probe.py) and the stream
+# order tests' delay door (tests/stream_probe.py)
 SRCS = [SRC, HERE / "native" / "forward_probe.hip", HERE / "native" / "update_probe.hip",
-        HERE / "native" / "shard_probe.hip"]
+        HERE / "native" / "shard_probe.hip", HERE / "native" / "stream_probe.hip"]
 LIB_DIR = ROOT / "fm_spark_amd" / "lib"
 PROBE = LIB_DIR / "libfm_sort_probe.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -49,7 +52,8 @@ def build_probe(verbose: bool = False, force: bool = False, lib: Path | None = N
     out = Path(out) if out else lib.parent / PROBE.name
     if not lib.exists():
         raise RuntimeError(f"{lib} is missing: build the library first")
-    deps = [*SRCS, ROOT / "fm_spark_amd" / "csrc" / "fm_internal.h", ROOT / "include" / "fm_hip.h", lib]
+    deps = [*SRCS, ROOT / "fm_spark_amd" / "csrc" / "fm_internal.h", ROOT / "fm_spark_amd" / "csrc" / "fm_context.h",
+            ROOT / "include" / "fm_hip.h", lib]
     if not force and out.exists() and all(d.stat().st_mtime <= out.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, f"--offload-arch={ARCH}", "-O2", "-std=c++17", "-fPIC", "-Wall", "-shared", *map(str, SRCS), "-o",
