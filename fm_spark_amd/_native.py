@@ -22,6 +22,7 @@ FM_MAX_LOCAL = 16
 FM_FUSE_DEFAULT, FM_FUSE_ON, FM_FUSE_OFF = 0, 1, -1
 FM_WIRE_FP32, FM_WIRE_FP64 = 0, 1
 FM_LOSS_SQUARED, FM_LOSS_LOGISTIC, FM_LOSS_BPR = 0, 1, 2
+FM_OPT_SGD, FM_OPT_ADAGRAD = 0, 1
 FM_RANK_MAX_TOP = 1024
 FM_RANK_SELECT_ALL, FM_RANK_SELECT_ONLY, FM_RANK_SELECT_EXCEPT = 0, 1, 2
 
@@ -50,6 +51,8 @@ class fm_config(C.Structure):
         ("fuse_single", C.c_int32),
         ("xchg_chunks", C.c_int32),
         ("wire", C.c_int32),
+        ("opt_init", C.c_double),
+        ("optimizer", C.c_int32),
         ("loss", C.c_int32),
     ]
 
@@ -111,6 +114,7 @@ SIGNATURES = {
     "fm_set_stream": (C.c_int, [_P, _P]),
     "fm_sync": (C.c_int, [_P]),
     "fm_reserve": (C.c_int, [_P, C.c_int64, C.c_int64]),
+    "fm_optimizer_reset": (C.c_int, [_P]),
     "fm_load_tables": (C.c_int, [_P, _I32P, C.c_int64, _DP, _DP]),
     "fm_init_random": (C.c_int, [_P, _I32P, C.c_int64]),
     "fm_init_random_range": (C.c_int, [_P, C.c_int64, C.c_int64]),

@@ -240,6 +240,8 @@ bool fuse_rule(const fm_ctx* ctx) {
   // the fused forward applies the singleton rows with the squared residual, before the objective stage
   // (fm_objective.hip) has replaced it: another loss never fuses
   if (ctx->cfg.loss != FM_LOSS_SQUARED) return false;
+  // ... and with the SGD row update: another optimizer never fuses either
+  if (ctx->cfg.optimizer != FM_OPT_SGD) return false;
   if (ctx->cfg.fuse_single == FM_FUSE_OFF || ctx->kp > 16) return false;
   const double table_bytes = (double)ctx->rows * ctx->stride * sizeof(float);
   return ctx->cfg.fuse_single == FM_FUSE_ON || table_bytes > 256.0 * 1024 * 1024;
@@ -252,6 +254,8 @@ static const char* loss_name(int32_t loss) {
 void require_squared(const fm_ctx* ctx, const char* call) {
   FM_REQUIRE(ctx->cfg.loss == FM_LOSS_SQUARED, std::string(call) + " runs the squared step only: this context's loss is " +
                                                    loss_name(ctx->cfg.loss));
+  FM_REQUIRE(ctx->cfg.optimizer == FM_OPT_SGD,
+             std::string(call) + " runs the SGD update only: this context's optimizer is FM_OPT_ADAGRAD");
 }
 
 static bool fuse_on(const fm_ctx* ctx) { return ctx->cfg.shard_count == 1 && fuse_rule(ctx); }
@@ -347,6 +351,7 @@ void reserve_work(fm_ctx* ctx, int64_t B, int64_t N) {
   w.part.ensure_slack(sizeof(double) * (size_t)std::max<int64_t>(nranges, 1) * 2 * (ctx->kp + 2));
   w.ucnt.ensure_slack(sizeof(uint32_t) * (size_t)std::max<int64_t>((N + 1023) / 1024, 1));
   w.loss_part.ensure(sizeof(double2) * kLossPartBlocks);
+  if (ctx->cfg.optimizer == FM_OPT_ADAGRAD) ctx->ada.ensure(N, ctx->kp);
 }
 
 }  // namespace fmhip
@@ -436,15 +441,23 @@ int step_impl(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_
   if (!fused) FM_HIP_CHECK(hipStreamWaitEvent(ctx->stream, prepared ? b->ready : ctx->ev_join, 0));
   e0 = ctx->prof_begin(ctx->stream);
   double* stats = ctx->loss_hist.as<double>() + 3 * (int64_t)ctx->epoch;
-  launch_segment_update(T, b->dev, ctx->work, p, skeys, sents, nfwd, stats, ctx->stream, emit,
-                        fused ? b->split_n.as<int64_t>() : nullptr);
+  const bool adagrad = ctx->cfg.optimizer == FM_OPT_ADAGRAD;
+  if (adagrad) {
+    // the AdaGrad stage in the segmented update's place (fm_adagrad.hip): it closes the step as well
+    FM_REQUIRE(!fused && !emit, "the fused and the replicated step are the SGD update's: this context's optimizer is "
+                                "FM_OPT_ADAGRAD");
+    launch_adagrad(T, ctx->accum_view(), N, ctx->work, ctx->ada, p, skeys, sents, nfwd, stats, ctx->stream);
+  } else {
+    launch_segment_update(T, b->dev, ctx->work, p, skeys, sents, nfwd, stats, ctx->stream, emit,
+                          fused ? b->split_n.as<int64_t>() : nullptr);
+  }
   // the shared sort workspace is read by the main stream only when the batch was sorted inline
   // (not prepared): only then must the next fm_batch_prepare's sort wait for this update
   if (!prepared) FM_HIP_CHECK(hipEventRecord(ctx->ev_upd_done, ctx->stream));
   // the last read of the batch (its next fm_batch_prepare or fm_batch_from_rows refill waits for it)
   if (b->last_use) FM_HIP_CHECK(hipEventRecord(b->last_use, ctx->stream));
   b->prepared = false;
-  ctx->prof_end("update", e0, ctx->stream);
+  ctx->prof_end(adagrad ? "adagrad" : "update", e0, ctx->stream);
   if (emit) return FM_OK;
   ctx->epoch += 1;
   ctx->cum_host.push_back(p.cum_next);
@@ -484,6 +497,18 @@ int fm_create(const fm_config* cfg, fm_ctx** out) {
                  "loss = " + nm + " cannot take fuse_single = FM_FUSE_ON: the fused forward applies singleton rows with the "
                  "squared residual");
     }
+    FM_REQUIRE(cfg->optimizer == FM_OPT_SGD || cfg->optimizer == FM_OPT_ADAGRAD, "optimizer must be FM_OPT_SGD or FM_OPT_ADAGRAD");
+    if (cfg->optimizer == FM_OPT_ADAGRAD) {
+      FM_REQUIRE(std::isfinite(cfg->opt_init) && cfg->opt_init > 0.0,
+                 "optimizer = FM_OPT_ADAGRAD needs a finite opt_init > 0 (the accumulators' starting value)");
+      FM_REQUIRE(cfg->parallel == FM_PARALLEL_NONE,
+                 "optimizer = FM_OPT_ADAGRAD needs parallel == FM_PARALLEL_NONE: the multi-GPU steps run the SGD update");
+      FM_REQUIRE(cfg->shard_count == 1,
+                 "optimizer = FM_OPT_ADAGRAD needs shard_count == 1: the sharded step runs the SGD update");
+      FM_REQUIRE(cfg->fuse_single != FM_FUSE_ON,
+                 "optimizer = FM_OPT_ADAGRAD cannot take fuse_single = FM_FUSE_ON: the fused forward applies singleton rows "
+                 "with the SGD update");
+    }
     FM_REQUIRE(cfg->wire == FM_WIRE_FP32 || cfg->wire == FM_WIRE_FP64, "wire must be FM_WIRE_FP32 or FM_WIRE_FP64");
     FM_REQUIRE(cfg->wire != FM_WIRE_FP64 || cfg->parallel != FM_PARALLEL_REPLICATED,
                "wire = FM_WIRE_FP64 applies to the sharded step only: the replicated gradient all-reduce is fp32");
@@ -516,6 +541,10 @@ int fm_create(const fm_config* cfg, fm_ctx** out) {
     c->stride = record_stride(c->kp);
     c->rec.ensure(sizeof(float) * (size_t)std::max<int64_t>(c->rows, 1) * c->stride);
     c->ensure_hist(4096);
+    if (cfg->optimizer == FM_OPT_ADAGRAD) {
+      c->accum.ensure(sizeof(float) * (size_t)std::max<int64_t>(c->rows, 1) * (c->kp + 4));
+      launch_ada_fill(c->accum_view(), c->rows, c->kp, cfg->opt_init, c->stream);
+    }
     launch_table_reset(c->view(), c->stream);
     FM_HIP_CHECK(hipStreamSynchronize(c->stream));
     *out = c.release();
@@ -581,6 +610,15 @@ int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz) {
     FM_REQUIRE(max_rows >= 0 && max_nnz >= 0, "negative reserve");
     if (ctx->group) return group_reserve(ctx, max_rows, max_nnz);
     reserve_work(ctx, max_rows, max_nnz);
+    return FM_OK;
+  });
+}
+
+int fm_optimizer_reset(fm_ctx* ctx) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(!ctx->group, "fm_optimizer_reset on a multi-GPU context: it keeps no optimizer state");
+    if (ctx->cfg.optimizer == FM_OPT_ADAGRAD)
+      launch_ada_fill(ctx->accum_view(), ctx->rows, ctx->kp, ctx->cfg.opt_init, ctx->stream);
     return FM_OK;
   });
 }

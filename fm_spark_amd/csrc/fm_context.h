@@ -203,6 +203,11 @@ struct fm_ctx {
   hipEvent_t ev_upd_done = nullptr;  // last main-stream read of the shared sort workspace (an inline-sorted step)
   DevBuf rec;  // [rows * stride] float records (V row + header)
   int32_t stride = 0;
+  // FM_OPT_ADAGRAD contexts only: the accumulators [rows][kp + 4] = {G_V[kp], G_w, 0, 0, 0} (fm_adagrad.hip),
+  // filled with fm_config.opt_init at fm_create and by fm_optimizer_reset; and the stage's scratch
+  DevBuf accum;
+  AdaWork ada;
+  float* accum_view() const { return accum.as<float>(); }
   std::vector<double> cum_host{0.0};  // cum[e] = sum of lambda over executed steps 1..e
   int32_t epoch = 0;
   DevBuf loss_hist;  // [hist_cap][3] double {loss, n_loss, n_unique}
@@ -395,6 +400,7 @@ struct fm_ctx {
     // The buffers would free themselves (DevBuf's destructor): released here only for the order -- on
     // the context's device, after its streams drained and before the main stream is destroyed.
     rec.release();
+    accum.release();
     loss_hist.release();
     eval_hist.release();
     bin_hist.release();
@@ -413,7 +419,8 @@ struct fm_ctx {
                       &rank.bias_u, &rank.bias_c, &rank.lkey, &rank.lidx, &rank.out_idx, &rank.out_score,
                       &rank.sel_ptr, &rank.sel_rows, &rank.tgt_ptr, &rank.tgt_rows, &rank.position, &rank.pos_score,
                       &pairs.lists, &pairs.pair_ctx, &pairs.pair_cand, &pairs.label, &pairs.len, &pairs.row_ptr,
-                      &pairs.chunk_tot, &pairs.chunk_off, &pairs.total};
+                      &pairs.chunk_tot, &pairs.chunk_off, &pairs.total,
+                      &ada.flag, &ada.off, &ada.chunk_tot, &ada.chunk_off, &ada.cnt, &ada.part, &ada.hot, &ada.ucnt};
     for (auto* b : bufs) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
@@ -492,6 +499,7 @@ inline int bits_for(int64_t max_value) {
 bool fuse_rule(const fm_ctx* ctx);
 // the manual multi-GPU phases (fm_shard_*, fm_repl_*) are the squared step's: FM_ERR_ARG on a context
 // with another fm_config.loss
+// ... nor with another fm_config.optimizer than FM_OPT_SGD (the message names it)
 void require_squared(const fm_ctx* ctx, const char* call);
 // stream st waits until a batch refilled by fm_batch_from_rows has been gathered (copy stream)
 void wait_built(const fm_batch* b, hipStream_t st);

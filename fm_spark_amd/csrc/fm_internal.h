@@ -301,6 +301,29 @@ void launch_segment_update(const TableView& T, const BatchDev& b, StepWork& w, c
 // the number of those partials (<= kLossPartBlocks), which launch_segment_update takes in place of the
 // forward's block count.
 int64_t launch_objective(int32_t loss, int32_t group, int kp, const BatchDev& b, StepWork& w, hipStream_t st);
+// The AdaGrad stage (fm_adagrad.hip), in launch_segment_update's place on a context whose optimizer is
+// FM_OPT_ADAGRAD: the same sorted view, S records, {r, yh} and loss partials in; the table rows and the
+// accumulator rows G[rows][kp + 4] = {G_V[kp], G_w, 0, 0, 0} of every touched row updated, stats_out[3]
+// closed in k_segment_combine's order.  Its scratch grows with the context (main stream only).
+struct AdaWork {
+  DevBuf flag;                  // uint32 [N]: 1 where a piece begins
+  DevBuf off;                   // int64 [N + 1]: the flags' exclusive scan
+  DevBuf chunk_tot, chunk_off;  // launch_len_scan's
+  DevBuf cnt;                   // int64 {pieces, the two alternating counters of the multi-piece run list}
+  DevBuf part;                  // double [2 (N / piece + 1)][kp + 2]: the partials of the runs of several pieces
+  DevBuf hot;                   // int64 [N / piece + 1]: the first entries of those runs
+  DevBuf ucnt;                  // uint32 per flag block: run heads (distinct ids)
+  uint64_t tick = 0;            // steps launched: which counter is this step's
+  void ensure(int64_t N, int kp);  // everything, for N entries
+};
+void launch_adagrad(const TableView& T, float* G, int64_t N, const StepWork& w, AdaWork& aw, const StepParams& p,
+                    const uint32_t* skeys, const uint2* sents, int64_t n_loss_blocks, double* stats_out, hipStream_t st);
+// every accumulator of G[rows][kp + 4] = g0 (the pad words 0)
+void launch_ada_fill(float* G, int64_t rows, int kp, double g0, hipStream_t st);
+// A seam for the suite (tests/test_gpu_adagrad.py), not configuration and not in include/fm_hip.h: the
+// entries per piece of a run, exported as the C symbol fm_seam_adagrad_piece so that the tests place their
+// run lengths against the built library's constant and follow a retuned kernel.  No kernel reads it.
+extern "C" int32_t fm_seam_adagrad_piece(void);
 // the fused step's singleton split of a prepared sorted view, at the step (fm_update.hip; fm_device.h
 // "Singleton rows"): the entries of runs of two or more, in order, into mkeys / ments (capacity N); n_out[0] =
 // their count, n_out[1] = the number of singleton runs (device); each multi run's row in tag_T gets

@@ -409,6 +409,10 @@ class FactorizationMachinesSGD:
         "negativesPerPositive": 4,
         # not in the reference (its loss is the squared error, SGD.scala:134-146): the step's objective
         "loss": "squared",
+        # not in the reference (one rate stepSize / sqrt(t) for every row): the row update and, for "adagrad",
+        # the accumulators' starting value
+        "optimizer": "sgd",
+        "initialAccumulator": 0.1,
     }
 
     def __init__(self, uid: str | None = None):
@@ -450,6 +454,9 @@ class FactorizationMachinesSGD:
             raise ValueError(f'loss "{self._params["loss"]}" trains on one GPU: multi-GPU objectives are not built yet')
         if mode not in (None, "none") and self._params["binaryValidationData"] is not None:
             raise ValueError("binaryValidationData needs a single-GPU estimator: the binary evaluation is not multi-GPU")
+        if mode not in (None, "none") and self._params["optimizer"] != "sgd":
+            raise ValueError(f'optimizer "{self._params["optimizer"]}" trains on one GPU: the multi-GPU steps run the '
+                             "SGD update")
         self._set("parallel", mode)
         self._set("wire", wire)
         self._set("nGpus", int(n_gpus))
@@ -521,6 +528,27 @@ class FactorizationMachinesSGD:
             raise ValueError('loss "bpr" cannot evaluate binaryValidationData: its scores are no logit of a label')
         return self._set("loss", loss)
 
+    def setOptimizer(self, optimizer: str):
+        """The row update of each step (fm_config.optimizer): "sgd" (default, the reference's: every row moves
+        by stepSize / sqrt(t)) or "adagrad" -- every coordinate of a touched row keeps an accumulator G
+        (starting at initialAccumulator) and moves by stepSize / sqrt(t) * g / sqrt(G + g^2), the usual choice
+        for click and implicit-feedback data, where a few hot rows take thousands of entries a step and most
+        rows one.  regParam's soft threshold is not scaled by the adaptive rate.  Serves every loss, through
+        fit and fitInteractions; one GPU (ValueError with setParallel), never fused."""
+        if optimizer not in ("sgd", "adagrad"):
+            raise ValueError('optimizer must be "sgd" or "adagrad"')
+        if optimizer != "sgd" and self._params["parallel"] not in (None, "none"):
+            raise ValueError(f'optimizer "{optimizer}" trains on one GPU: the multi-GPU steps run the SGD update')
+        return self._set("optimizer", optimizer)
+
+    def setInitialAccumulator(self, value: float):
+        """G0, the starting value of every "adagrad" accumulator (finite, > 0; default 0.1)."""
+        if isinstance(value, bool) or not np.isfinite(value) or not float(value) > 0.0:
+            raise ValueError("initialAccumulator must be finite and > 0")
+        return self._set("initialAccumulator", float(value))
+
+    def getOptimizer(self): return self._params["optimizer"]
+    def getInitialAccumulator(self): return self._params["initialAccumulator"]
     def getLoss(self): return self._params["loss"]
     def getNegativesPerPositive(self): return self._params["negativesPerPositive"]
     def getDimFactorization(self): return self._params["dimFactorization"]
@@ -562,6 +590,13 @@ class FactorizationMachinesSGD:
                 raise ValueError('loss "bpr" cannot evaluate binaryValidationData: its scores are no logit of a label')
             if p["parallel"] not in (None, "none"):
                 raise ValueError("binaryValidationData needs a single-GPU estimator: the binary evaluation is not multi-GPU")
+        # setOptimizer's and setInitialAccumulator's rules
+        if p["optimizer"] not in ("sgd", "adagrad"):
+            raise ValueError('optimizer must be "sgd" or "adagrad"')
+        if p["optimizer"] != "sgd" and p["parallel"] not in (None, "none"):
+            raise ValueError(f'optimizer "{p["optimizer"]}" trains on one GPU: the multi-GPU steps run the SGD update')
+        if p["optimizer"] != "sgd" and not (np.isfinite(p["initialAccumulator"]) and p["initialAccumulator"] > 0.0):
+            raise ValueError("initialAccumulator must be finite and > 0")
 
     # fit (SGD.scala:76-216) --------------------------------------------------------------
     def fit(self, dataset: DataFrame, initial_tables=None, pipelined: bool | None = None) -> FactorizationMachinesModel:
@@ -588,7 +623,7 @@ class FactorizationMachinesSGD:
         F = p["numFeatures"] or (int(col.max()) + 1 if len(col) else 1)
         ctx = FMContext(F, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0,
                         parallel=p["parallel"], n_gpus=p["nGpus"], devices=p["devices"], transport=p["transport"],
-                        wire=p["wire"], loss=p["loss"])
+                        wire=p["wire"], loss=p["loss"], optimizer=p["optimizer"], opt_init=p["initialAccumulator"])
         if pipelined is None:
             pipelined = True
         # randomSplit(Array.fill(maxIter)(miniBatchFraction), 1234L) (:111-112)
@@ -725,7 +760,7 @@ class FactorizationMachinesSGD:
         k = p["dimFactorization"]
         top = max([int(col.max()) + 1 for _, col, _ in rows if len(col)], default=1)
         ctx = FMContext(p["numFeatures"] or top, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0,
-                        loss=p["loss"])
+                        loss=p["loss"], optimizer=p["optimizer"], opt_init=p["initialAccumulator"])
         bu, bc = (ctx.batch(N.CSRHost(rp, col, val, np.zeros(len(rp) - 1))) for rp, col, val in rows)
         # the exclude lists, resident for the whole loop: the given ones (normalised above, once), else what
         # the interactions say each context has seen, built on the device from the pairs themselves

@@ -55,6 +55,8 @@ extern "C" {
 #define FM_LOSS_SQUARED 0  /* fm_config.loss: the reference's squared error on the label (default) */
 #define FM_LOSS_LOGISTIC 1 /* log loss of sigma(yhat) against labels in [0, 1] */
 #define FM_LOSS_BPR 2      /* pairwise ranking loss over each positive row and the negatives behind it */
+#define FM_OPT_SGD 0     /* fm_config.optimizer: the reference's row update, one rate stepSize / sqrt(t) (default) */
+#define FM_OPT_ADAGRAD 1 /* per-coordinate AdaGrad on the touched rows (single tables) */
 
 typedef struct fm_ctx fm_ctx;
 typedef struct fm_batch fm_batch;
@@ -127,6 +129,36 @@ typedef struct fm_lists fm_lists;
  *                the stage runs) and never fuses under FM_FUSE_DEFAULT (fm_fuse_active is 0).  fm_repl_grad
  *                / fm_repl_apply refuse such a context.  Any other value is FM_ERR_ARG.  fm_loss_grad /
  *                fm_calc_loss_grad stay the reference's squared columns on any context.
+ * optimizer    : the row update of fm_step / fm_step_batch, a property of the context.  FM_OPT_SGD (0,
+ *                default): the reference's update, unchanged in every bit and in the kernels it launches.
+ *                FM_OPT_ADAGRAD: every table coordinate keeps an accumulator G (fp32, starting at opt_init).
+ *                For a row the batch touches, g is the fp64 gradient sum the SGD update forms -- g_V[f] =
+ *                A[f] - v_cur[f]*b with A = sum S*(x*r), b = sum x*x*r; g_w = sum (x - 1)*yh + r, i.e. the
+ *                reference's own expression under FM_LOSS_SQUARED and x*r under the other losses -- with
+ *                v_cur / w_cur the row brought current by its pending L1 exactly as the SGD update does.
+ *                With gh = g / m, eta = stepSize / sqrt(t), lam = eta * regParam:
+ *                    G' = G + gh*gh                         (fp64; G read from its fp32 word)
+ *                    v' = S_lam(v_cur - eta * gh / sqrt(G'))  (fp64, rounded once to fp32)
+ *                    G  = (float) G'
+ *                The soft threshold S_lam is deliberately NOT scaled by the adaptive rate: S_a(S_b(z)) =
+ *                S_{a+b}(z) then still holds with the one global cumulative shrink, so the lazy L1, the
+ *                forward's catch-up on read, predict, rank and export are exactly the SGD context's.  A row
+ *                absent before the step is handled as by the SGD update (it enters as zero; header t =
+ *                epoch + 1, cum = cum_next); a row the batch does not touch keeps its G.  The update serves
+ *                every fm_config.loss (the loss reaches it through {r, yh} alone).  The accumulators are one
+ *                fp32 array [rows][kp + 4] = {G_V[kp], G_w, 0, 0, 0}, kp = k rounded up to 4, allocated by
+ *                FM_OPT_ADAGRAD contexts only, counted by fm_device_bytes_live, filled with opt_init at
+ *                fm_create and by fm_optimizer_reset; fm_load_tables and fm_init_* do not touch them, and
+ *                they are neither exported nor imported (the reference has no persistence).  A stage of its
+ *                own in the update's place (fm_adagrad.hip; profile name "adagrad" instead of "update"):
+ *                every sum in a fixed order that depends on the run of equal ids alone, no float atomics,
+ *                equal inputs give equal bits whether the batch was prepared or is sorted inline.
+ *                Single tables only: parallel != FM_PARALLEL_NONE and shard_count > 1 are FM_ERR_ARG naming
+ *                the optimizer, and so are fm_repl_grad / fm_repl_apply and the fm_shard_* phases on such a
+ *                context.  It never fuses: fuse_single == FM_FUSE_ON is FM_ERR_ARG, FM_FUSE_DEFAULT behaves
+ *                as for the non-squared losses (fm_fuse_active is 0).  Any other value is FM_ERR_ARG.
+ * opt_init     : G0, the accumulators' starting value (fp64; stored as fp32).  FM_OPT_ADAGRAD: finite and
+ *                > 0, else FM_ERR_ARG.  Ignored under FM_OPT_SGD.
  * Zero-initialise the struct: every field's 0 is its default. */
 typedef struct fm_config {
   int64_t num_features;
@@ -147,6 +179,10 @@ typedef struct fm_config {
   int32_t fuse_single;
   int32_t xchg_chunks;
   int32_t wire;
+  /* opt_init and optimizer were inserted here, not appended: loss stays the struct's last field, so its
+   * offset moved by 12 bytes against earlier headers -- callers are rebuilt against this header */
+  double opt_init;
+  int32_t optimizer;
   int32_t loss;
 } fm_config;
 
@@ -214,6 +250,12 @@ int fm_sync(fm_ctx* ctx);
  * payloads before and after the re-key, the flags and their scan (44 bytes per row, 52 with the labels), the per-block
  * partials and a sort workspace of the stage's own (24 bytes per row), sized by the largest call. */
 int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz);
+/* Refill an FM_OPT_ADAGRAD context's accumulators with fm_config.opt_init (enqueued on the main stream;
+ * the table is not touched): the next step behaves as a first step on the current table.  A no-op on an
+ * FM_OPT_SGD context; FM_ERR_ARG on a multi-GPU context.  fm_reserve on an FM_OPT_ADAGRAD context also
+ * sizes the stage's scratch (12 bytes per entry for the piece flags and their scan, a count per 256 entries,
+ * and the partial sums of the runs longer than a piece). */
+int fm_optimizer_reset(fm_ctx* ctx);
 
 /* ---- tables (C9: Strength / FactorizedInteraction, Model.scala:275-289) ------------ */
 /* Inject rows (id, w, V[k]) and mark them present: the M0 injection point. */
