@@ -254,8 +254,8 @@ static const char* loss_name(int32_t loss) {
 void require_squared(const fm_ctx* ctx, const char* call) {
   FM_REQUIRE(ctx->cfg.loss == FM_LOSS_SQUARED, std::string(call) + " runs the squared step only: this context's loss is " +
                                                    loss_name(ctx->cfg.loss));
-  FM_REQUIRE(ctx->cfg.optimizer == FM_OPT_SGD,
-             std::string(call) + " runs the SGD update only: this context's optimizer is FM_OPT_ADAGRAD");
+  FM_REQUIRE(ctx->cfg.optimizer == FM_OPT_SGD, std::string(call) + " runs the SGD update only: this context's optimizer is " +
+                                                   (ctx->cfg.optimizer == FM_OPT_FTRL ? "FM_OPT_FTRL" : "FM_OPT_ADAGRAD"));
 }
 
 static bool fuse_on(const fm_ctx* ctx) { return ctx->cfg.shard_count == 1 && fuse_rule(ctx); }
@@ -352,6 +352,7 @@ void reserve_work(fm_ctx* ctx, int64_t B, int64_t N) {
   w.ucnt.ensure_slack(sizeof(uint32_t) * (size_t)std::max<int64_t>((N + 1023) / 1024, 1));
   w.loss_part.ensure(sizeof(double2) * kLossPartBlocks);
   if (ctx->cfg.optimizer == FM_OPT_ADAGRAD) ctx->ada.ensure(N, ctx->kp);
+  if (ctx->cfg.optimizer == FM_OPT_FTRL) ctx->ftrl.ensure(N, ctx->kp);
 }
 
 }  // namespace fmhip
@@ -386,6 +387,14 @@ int step_impl(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_
   p.cumE = ctx->cum_host.back();
   p.cum_next = p.cumE + p.lam;
   p.w0 = ctx->cfg.w0;
+  p.alpha = step_size;
+  const bool ftrl = ctx->cfg.optimizer == FM_OPT_FTRL;
+  if (ftrl) {
+    // FTRL's L1 is part of its closed form: the lazy soft threshold stands still on such a context
+    FM_REQUIRE(step_size > 0.0 && reg_param >= 0.0, "an FM_OPT_FTRL step needs step_size (alpha) > 0 and reg_param (lambda1) >= 0");
+    p.lam = 0.0;
+    p.cum_next = p.cumE;
+  }
   const TableView T = ctx->view();
   wait_built(b, ctx->stream);
   int64_t nfwd = 0;
@@ -447,6 +456,12 @@ int step_impl(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_
     FM_REQUIRE(!fused && !emit, "the fused and the replicated step are the SGD update's: this context's optimizer is "
                                 "FM_OPT_ADAGRAD");
     launch_adagrad(T, ctx->accum_view(), N, ctx->work, ctx->ada, p, skeys, sents, nfwd, stats, ctx->stream);
+  } else if (ftrl) {
+    // the FTRL-Proximal stage in the same place (fm_ftrl.hip)
+    FM_REQUIRE(!fused && !emit, "the fused and the replicated step are the SGD update's: this context's optimizer is "
+                                "FM_OPT_FTRL");
+    const FtrlHyper hy{reg_param, ctx->cfg.opt_init, ctx->cfg.opt_l2};
+    launch_ftrl(T, ctx->ftrl_state.as<float>(), N, ctx->work, ctx->ftrl, p, hy, skeys, sents, nfwd, stats, ctx->stream);
   } else {
     launch_segment_update(T, b->dev, ctx->work, p, skeys, sents, nfwd, stats, ctx->stream, emit,
                           fused ? b->split_n.as<int64_t>() : nullptr);
@@ -457,7 +472,7 @@ int step_impl(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_
   // the last read of the batch (its next fm_batch_prepare or fm_batch_from_rows refill waits for it)
   if (b->last_use) FM_HIP_CHECK(hipEventRecord(b->last_use, ctx->stream));
   b->prepared = false;
-  ctx->prof_end(adagrad ? "adagrad" : "update", e0, ctx->stream);
+  ctx->prof_end(adagrad ? "adagrad" : ftrl ? "ftrl" : "update", e0, ctx->stream);
   if (emit) return FM_OK;
   ctx->epoch += 1;
   ctx->cum_host.push_back(p.cum_next);
@@ -497,7 +512,19 @@ int fm_create(const fm_config* cfg, fm_ctx** out) {
                  "loss = " + nm + " cannot take fuse_single = FM_FUSE_ON: the fused forward applies singleton rows with the "
                  "squared residual");
     }
-    FM_REQUIRE(cfg->optimizer == FM_OPT_SGD || cfg->optimizer == FM_OPT_ADAGRAD, "optimizer must be FM_OPT_SGD or FM_OPT_ADAGRAD");
+    FM_REQUIRE(cfg->optimizer == FM_OPT_SGD || cfg->optimizer == FM_OPT_ADAGRAD || cfg->optimizer == FM_OPT_FTRL,
+               "optimizer must be FM_OPT_SGD, FM_OPT_ADAGRAD or FM_OPT_FTRL");
+    if (cfg->optimizer == FM_OPT_FTRL) {
+      FM_REQUIRE(std::isfinite(cfg->opt_init) && cfg->opt_init > 0.0,
+                 "optimizer = FM_OPT_FTRL needs a finite opt_init > 0 (beta of the per-coordinate rate)");
+      FM_REQUIRE(std::isfinite(cfg->opt_l2) && cfg->opt_l2 >= 0.0, "optimizer = FM_OPT_FTRL needs a finite opt_l2 >= 0 (lambda2)");
+      FM_REQUIRE(cfg->parallel == FM_PARALLEL_NONE,
+                 "optimizer = FM_OPT_FTRL needs parallel == FM_PARALLEL_NONE: the multi-GPU steps run the SGD update");
+      FM_REQUIRE(cfg->shard_count == 1, "optimizer = FM_OPT_FTRL needs shard_count == 1: the sharded step runs the SGD update");
+      FM_REQUIRE(cfg->fuse_single != FM_FUSE_ON,
+                 "optimizer = FM_OPT_FTRL cannot take fuse_single = FM_FUSE_ON: the fused forward applies singleton rows "
+                 "with the SGD update");
+    }
     if (cfg->optimizer == FM_OPT_ADAGRAD) {
       FM_REQUIRE(std::isfinite(cfg->opt_init) && cfg->opt_init > 0.0,
                  "optimizer = FM_OPT_ADAGRAD needs a finite opt_init > 0 (the accumulators' starting value)");
@@ -544,6 +571,10 @@ int fm_create(const fm_config* cfg, fm_ctx** out) {
     if (cfg->optimizer == FM_OPT_ADAGRAD) {
       c->accum.ensure(sizeof(float) * (size_t)std::max<int64_t>(c->rows, 1) * (c->kp + 4));
       launch_ada_fill(c->accum_view(), c->rows, c->kp, cfg->opt_init, c->stream);
+    }
+    if (cfg->optimizer == FM_OPT_FTRL) {
+      c->ftrl_state.ensure(sizeof(float) * (size_t)std::max<int64_t>(c->rows, 1) * 2 * (c->kp + 4));
+      launch_ftrl_zero(c->ftrl_state.as<float>(), c->rows, c->kp, c->stream);
     }
     launch_table_reset(c->view(), c->stream);
     FM_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -619,6 +650,7 @@ int fm_optimizer_reset(fm_ctx* ctx) {
     FM_REQUIRE(!ctx->group, "fm_optimizer_reset on a multi-GPU context: it keeps no optimizer state");
     if (ctx->cfg.optimizer == FM_OPT_ADAGRAD)
       launch_ada_fill(ctx->accum_view(), ctx->rows, ctx->kp, ctx->cfg.opt_init, ctx->stream);
+    if (ctx->cfg.optimizer == FM_OPT_FTRL) launch_ftrl_zero(ctx->ftrl_state.as<float>(), ctx->rows, ctx->kp, ctx->stream);
     return FM_OK;
   });
 }

@@ -208,6 +208,10 @@ struct fm_ctx {
   DevBuf accum;
   AdaWork ada;
   float* accum_view() const { return accum.as<float>(); }
+  // FM_OPT_FTRL contexts only: the state rows [rows][2 (kp + 4)] = {z_V[kp], z_w, 0, 0, 0, n_V[kp], n_w, 0, 0, 0}
+  // (fm_ftrl.hip), zero at fm_create and after fm_optimizer_reset; and the stage's scratch
+  DevBuf ftrl_state;
+  FtrlWork ftrl;
   std::vector<double> cum_host{0.0};  // cum[e] = sum of lambda over executed steps 1..e
   int32_t epoch = 0;
   DevBuf loss_hist;  // [hist_cap][3] double {loss, n_loss, n_unique}
@@ -401,6 +405,7 @@ struct fm_ctx {
     // the context's device, after its streams drained and before the main stream is destroyed.
     rec.release();
     accum.release();
+    ftrl_state.release();
     loss_hist.release();
     eval_hist.release();
     bin_hist.release();
@@ -420,7 +425,8 @@ struct fm_ctx {
                       &rank.sel_ptr, &rank.sel_rows, &rank.tgt_ptr, &rank.tgt_rows, &rank.position, &rank.pos_score,
                       &pairs.lists, &pairs.pair_ctx, &pairs.pair_cand, &pairs.label, &pairs.len, &pairs.row_ptr,
                       &pairs.chunk_tot, &pairs.chunk_off, &pairs.total,
-                      &ada.flag, &ada.off, &ada.chunk_tot, &ada.chunk_off, &ada.cnt, &ada.part, &ada.hot, &ada.ucnt};
+                      &ada.flag, &ada.off, &ada.chunk_tot, &ada.chunk_off, &ada.cnt, &ada.part, &ada.hot, &ada.ucnt,
+                      &ftrl.part, &ftrl.ucnt};
     for (auto* b : bufs) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
@@ -499,7 +505,7 @@ inline int bits_for(int64_t max_value) {
 bool fuse_rule(const fm_ctx* ctx);
 // the manual multi-GPU phases (fm_shard_*, fm_repl_*) are the squared step's: FM_ERR_ARG on a context
 // with another fm_config.loss
-// ... nor with another fm_config.optimizer than FM_OPT_SGD (the message names it)
+// ... nor with another fm_config.optimizer than FM_OPT_SGD (the message names it: FM_OPT_ADAGRAD or FM_OPT_FTRL)
 void require_squared(const fm_ctx* ctx, const char* call);
 // stream st waits until a batch refilled by fm_batch_from_rows has been gathered (copy stream)
 void wait_built(const fm_batch* b, hipStream_t st);

@@ -212,6 +212,7 @@ struct StepParams {
   double cumE;       // cum[E]
   double cum_next;   // cum[E] + lam = cum[E+1]
   double w0;
+  double alpha = 0.0;  // the step call's stepSize as given (FM_OPT_FTRL's alpha; the other updates read eta)
 };
 
 // k_forward's modes (fm_forward.hip): the step's forward, plain or with the singleton rows' updates
@@ -324,6 +325,27 @@ void launch_ada_fill(float* G, int64_t rows, int kp, double g0, hipStream_t st);
 // entries per piece of a run, exported as the C symbol fm_seam_adagrad_piece so that the tests place their
 // run lengths against the built library's constant and follow a retuned kernel.  No kernel reads it.
 extern "C" int32_t fm_seam_adagrad_piece(void);
+// The FTRL-Proximal stage (fm_ftrl.hip), in launch_segment_update's place on a context whose optimizer is
+// FM_OPT_FTRL: the same inputs; the table rows and the state rows Z[rows][2 (kp + 4)] = {z_V[kp], z_w, 0, 0, 0,
+// n_V[kp], n_w, 0, 0, 0} of every touched row updated, stats_out[3] closed in k_segment_combine's order.  alpha is
+// p.alpha; p.lam is 0 and p.cum_next == p.cumE (the cumulative shrink stands still).  Main stream only.
+struct FtrlHyper {
+  double l1, beta, l2;  // regParam as given, fm_config.opt_init, fm_config.opt_l2
+};
+struct FtrlWork {
+  DevBuf part;  // double [2 windows][kp + 2]: the partials of the runs that reach past a window
+  DevBuf ucnt;  // uint32 per window block: run heads (distinct ids)
+  void ensure(int64_t N, int kp);
+};
+void launch_ftrl(const TableView& T, float* Z, int64_t N, const StepWork& w, FtrlWork& fw, const StepParams& p,
+                 const FtrlHyper& h, const uint32_t* skeys, const uint2* sents, int64_t n_loss_blocks, double* stats_out,
+                 hipStream_t st);
+// every word of Z[rows][2 (kp + 4)] = 0
+void launch_ftrl_zero(float* Z, int64_t rows, int kp, hipStream_t st);
+// Seams for the suite (tests/test_gpu_ftrl.py), as fm_seam_adagrad_piece: the window W in the low 16 bits with the
+// kp <= 16 lane groups' stretch in the high 16, and the stretch of the lane groups that serve a given kp.
+extern "C" int32_t fm_seam_ftrl_window(void);
+extern "C" int32_t fm_seam_ftrl_stretch(int32_t kp);
 // the fused step's singleton split of a prepared sorted view, at the step (fm_update.hip; fm_device.h
 // "Singleton rows"): the entries of runs of two or more, in order, into mkeys / ments (capacity N); n_out[0] =
 // their count, n_out[1] = the number of singleton runs (device); each multi run's row in tag_T gets

@@ -275,24 +275,28 @@ class FMContext:
     never fuse, and "bpr" steps grouped batches only (DeviceBatch.set_group, batch_sample_pairs).
     ``optimizer`` "sgd" | "adagrad" (fm_config.optimizer): "adagrad" keeps a per-coordinate accumulator that
     starts at ``opt_init`` (> 0) and steps every touched coordinate by eta * g / sqrt(G + g^2); the soft
-    threshold stays unscaled.  Single GPU, never fused; serves every loss."""
+    threshold stays unscaled.  "ftrl" is FTRL-Proximal: two state words per coordinate, alpha = the step's
+    step_size as given, lambda1 = its reg_param, beta = ``opt_init`` (> 0), lambda2 = ``opt_l2`` (>= 0); its L1
+    is part of the closed-form update, so coordinates come out exactly 0 and untouched rows do not move.
+    Single GPU, never fused; each serves every loss."""
 
     _PAR = {None: N.FM_PARALLEL_NONE, "none": N.FM_PARALLEL_NONE, "sharded": N.FM_PARALLEL_SHARDED,
             "replicated": N.FM_PARALLEL_REPLICATED}
     _TR = {"auto": N.FM_TRANSPORT_AUTO, "rccl": N.FM_TRANSPORT_RCCL, "copy": N.FM_TRANSPORT_COPY}
     _WIRE = {"fp32": N.FM_WIRE_FP32, "fp64": N.FM_WIRE_FP64}
     _LOSS = {"squared": N.FM_LOSS_SQUARED, "logistic": N.FM_LOSS_LOGISTIC, "bpr": N.FM_LOSS_BPR}
-    _OPT = {"sgd": N.FM_OPT_SGD, "adagrad": N.FM_OPT_ADAGRAD}
+    _OPT = {"sgd": N.FM_OPT_SGD, "adagrad": N.FM_OPT_ADAGRAD, "ftrl": N.FM_OPT_FTRL}
 
     def __init__(self, num_features: int, k: int, *, device: int = 0, seed: int = 0, init_sd: float = 0.01,
                  w0: float = 0.0, shard_index: int = 0, shard_count: int = 1, parallel: str | None = None,
                  n_gpus: int = 1, devices=None, transport: str = "auto", n_procs: int = 1, proc_rank: int = 0,
                  comm_id: bytes | None = None, fuse: bool | None = None, xchg_chunks: int = 0, wire: str = "fp32",
-                 loss: str = "squared", optimizer: str = "sgd", opt_init: float = 0.1):
+                 loss: str = "squared", optimizer: str = "sgd", opt_init: float = 0.1,
+                 opt_l2: float = 0.0):
         if loss not in self._LOSS:
             raise ValueError('loss must be "squared", "logistic" or "bpr"')
         if optimizer not in self._OPT:
-            raise ValueError('optimizer must be "sgd" or "adagrad"')
+            raise ValueError('optimizer must be "sgd", "adagrad" or "ftrl"')
         self._lib = N.load()
         if wire not in self._WIRE:
             raise ValueError('wire must be "fp32" or "fp64"')
@@ -315,6 +319,7 @@ class FMContext:
         cfg.loss = self._LOSS[loss]
         cfg.optimizer = self._OPT[optimizer]
         cfg.opt_init = float(opt_init)
+        cfg.opt_l2 = float(opt_l2)
         cfg.n_procs = int(n_procs)
         cfg.proc_rank = int(proc_rank)
         if comm_id is not None:
@@ -365,8 +370,8 @@ class FMContext:
         N.check(self._lib.fm_reserve(self.handle, int(max_rows), int(max_nnz)), "fm_reserve")
 
     def optimizer_reset(self):
-        """Refill an "adagrad" context's accumulators with opt_init (fm_optimizer_reset; enqueued on the main
-        stream, the table untouched).  Nothing to do on an "sgd" context."""
+        """Refill an "adagrad" context's accumulators with opt_init, or zero an "ftrl" context's z and n
+        (fm_optimizer_reset; enqueued on the main stream, the table untouched).  Nothing to do on an "sgd" context."""
         N.check(self._lib.fm_optimizer_reset(self.handle), "fm_optimizer_reset")
 
     # --------------------------------------------------------------------- tables

@@ -413,6 +413,8 @@ class FactorizationMachinesSGD:
         # the accumulators' starting value
         "optimizer": "sgd",
         "initialAccumulator": 0.1,
+        # "ftrl" only: lambda2 of its closed-form update
+        "l2": 0.0,
     }
 
     def __init__(self, uid: str | None = None):
@@ -533,20 +535,31 @@ class FactorizationMachinesSGD:
         by stepSize / sqrt(t)) or "adagrad" -- every coordinate of a touched row keeps an accumulator G
         (starting at initialAccumulator) and moves by stepSize / sqrt(t) * g / sqrt(G + g^2), the usual choice
         for click and implicit-feedback data, where a few hot rows take thousands of entries a step and most
-        rows one.  regParam's soft threshold is not scaled by the adaptive rate.  Serves every loss, through
-        fit and fitInteractions; one GPU (ValueError with setParallel), never fused."""
-        if optimizer not in ("sgd", "adagrad"):
-            raise ValueError('optimizer must be "sgd" or "adagrad"')
+        rows one.  regParam's soft threshold is not scaled by the adaptive rate.  "ftrl" is FTRL-Proximal
+        (McMahan et al., 2013), the choice when the model must come out sparse: alpha = stepSize as given (no
+        1 / sqrt(t)), lambda1 = regParam, beta = initialAccumulator, lambda2 = setL2; the L1 is part of its closed
+        form, so coordinates are exactly 0 while |z| <= lambda1 and untouched rows do not move.  Each serves every
+        loss, through fit and fitInteractions; one GPU (ValueError with setParallel), never fused."""
+        if optimizer not in ("sgd", "adagrad", "ftrl"):
+            raise ValueError('optimizer must be "sgd", "adagrad" or "ftrl"')
         if optimizer != "sgd" and self._params["parallel"] not in (None, "none"):
             raise ValueError(f'optimizer "{optimizer}" trains on one GPU: the multi-GPU steps run the SGD update')
         return self._set("optimizer", optimizer)
 
     def setInitialAccumulator(self, value: float):
-        """G0, the starting value of every "adagrad" accumulator (finite, > 0; default 0.1)."""
+        """G0, the starting value of every "adagrad" accumulator; under "ftrl", beta of the per-coordinate rate
+        alpha / (beta + sqrt(n)) (finite, > 0; default 0.1)."""
         if isinstance(value, bool) or not np.isfinite(value) or not float(value) > 0.0:
             raise ValueError("initialAccumulator must be finite and > 0")
         return self._set("initialAccumulator", float(value))
 
+    def setL2(self, value: float):
+        """lambda2 of the "ftrl" update (finite, >= 0; default 0); the other optimizers ignore it."""
+        if isinstance(value, bool) or not np.isfinite(value) or not float(value) >= 0.0:
+            raise ValueError("l2 must be finite and >= 0")
+        return self._set("l2", float(value))
+
+    def getL2(self): return self._params["l2"]
     def getOptimizer(self): return self._params["optimizer"]
     def getInitialAccumulator(self): return self._params["initialAccumulator"]
     def getLoss(self): return self._params["loss"]
@@ -591,8 +604,10 @@ class FactorizationMachinesSGD:
             if p["parallel"] not in (None, "none"):
                 raise ValueError("binaryValidationData needs a single-GPU estimator: the binary evaluation is not multi-GPU")
         # setOptimizer's and setInitialAccumulator's rules
-        if p["optimizer"] not in ("sgd", "adagrad"):
-            raise ValueError('optimizer must be "sgd" or "adagrad"')
+        if p["optimizer"] not in ("sgd", "adagrad", "ftrl"):
+            raise ValueError('optimizer must be "sgd", "adagrad" or "ftrl"')
+        if p["optimizer"] == "ftrl" and not (np.isfinite(p["l2"]) and p["l2"] >= 0.0):
+            raise ValueError("l2 must be finite and >= 0")
         if p["optimizer"] != "sgd" and p["parallel"] not in (None, "none"):
             raise ValueError(f'optimizer "{p["optimizer"]}" trains on one GPU: the multi-GPU steps run the SGD update')
         if p["optimizer"] != "sgd" and not (np.isfinite(p["initialAccumulator"]) and p["initialAccumulator"] > 0.0):
@@ -623,7 +638,8 @@ class FactorizationMachinesSGD:
         F = p["numFeatures"] or (int(col.max()) + 1 if len(col) else 1)
         ctx = FMContext(F, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0,
                         parallel=p["parallel"], n_gpus=p["nGpus"], devices=p["devices"], transport=p["transport"],
-                        wire=p["wire"], loss=p["loss"], optimizer=p["optimizer"], opt_init=p["initialAccumulator"])
+                        wire=p["wire"], loss=p["loss"], optimizer=p["optimizer"], opt_init=p["initialAccumulator"],
+                        opt_l2=p["l2"])
         if pipelined is None:
             pipelined = True
         # randomSplit(Array.fill(maxIter)(miniBatchFraction), 1234L) (:111-112)
@@ -760,7 +776,8 @@ class FactorizationMachinesSGD:
         k = p["dimFactorization"]
         top = max([int(col.max()) + 1 for _, col, _ in rows if len(col)], default=1)
         ctx = FMContext(p["numFeatures"] or top, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0,
-                        loss=p["loss"], optimizer=p["optimizer"], opt_init=p["initialAccumulator"])
+                        loss=p["loss"], optimizer=p["optimizer"], opt_init=p["initialAccumulator"],
+                        opt_l2=p["l2"])
         bu, bc = (ctx.batch(N.CSRHost(rp, col, val, np.zeros(len(rp) - 1))) for rp, col, val in rows)
         # the exclude lists, resident for the whole loop: the given ones (normalised above, once), else what
         # the interactions say each context has seen, built on the device from the pairs themselves

@@ -57,6 +57,7 @@ extern "C" {
 #define FM_LOSS_BPR 2      /* pairwise ranking loss over each positive row and the negatives behind it */
 #define FM_OPT_SGD 0     /* fm_config.optimizer: the reference's row update, one rate stepSize / sqrt(t) (default) */
 #define FM_OPT_ADAGRAD 1 /* per-coordinate AdaGrad on the touched rows (single tables) */
+#define FM_OPT_FTRL 2    /* FTRL-Proximal on the touched rows: L1 in the closed form, exact zeros (single tables) */
 
 typedef struct fm_ctx fm_ctx;
 typedef struct fm_batch fm_batch;
@@ -157,8 +158,38 @@ typedef struct fm_lists fm_lists;
  *                the optimizer, and so are fm_repl_grad / fm_repl_apply and the fm_shard_* phases on such a
  *                context.  It never fuses: fuse_single == FM_FUSE_ON is FM_ERR_ARG, FM_FUSE_DEFAULT behaves
  *                as for the non-squared losses (fm_fuse_active is 0).  Any other value is FM_ERR_ARG.
- * opt_init     : G0, the accumulators' starting value (fp64; stored as fp32).  FM_OPT_ADAGRAD: finite and
- *                > 0, else FM_ERR_ARG.  Ignored under FM_OPT_SGD.
+ *                FM_OPT_FTRL: FTRL-Proximal (McMahan et al., KDD 2013, algorithm 1), the optimizer for a model
+ *                that must come out sparse.  Every table coordinate keeps two fp32 state words z and n, in one
+ *                array [rows][2 (kp + 4)] = {z_V[kp], z_w, 0, 0, 0, n_V[kp], n_w, 0, 0, 0}: a row's state is one
+ *                contiguous, 16-byte-aligned stretch.  Parameters: alpha = the step call's stepSize AS GIVEN
+ *                (not divided by sqrt(t): the per-coordinate rate alpha / (beta + sqrt(n)) decays with n by
+ *                itself), lambda1 = the step call's regParam as given, beta = opt_init, lambda2 = opt_l2.  For
+ *                a row the batch touches, with g, gh = g / m and v_cur as under FM_OPT_ADAGRAD (an absent row
+ *                reads as zero), all in fp64 and each stored word rounded once:
+ *                    if n == 0:  z = -v_cur (beta / alpha + lambda2) - sgn(v_cur) lambda1     (first touch)
+ *                    n' = n + gh*gh
+ *                    z' = z + gh - ((sqrt(n') - sqrt(n)) / alpha) v_cur
+ *                    v' = 0                                      if |z'| <= lambda1
+ *                         -(z' - sgn(z') lambda1) / ((beta + sqrt(n')) / alpha + lambda2)   otherwise
+ *                The first-touch line takes for z the value whose closed form is the current v_cur, which is
+ *                what lets a loaded or randomly initialised V survive: the gradients here are divided by m,
+ *                so from z = 0 the first update would collapse V to about |gh| v, and an FM whose V is 0 has
+ *                no V gradient at all.  The L1 is part of the closed form -- a coordinate is exactly 0 while
+ *                |z| <= lambda1 -- so the context's cumulative lazy shrink does not advance (lam = 0, cum
+ *                stands still, nothing is ever pending) and a row the batch does not touch keeps every byte of
+ *                its record and state; the touched row leaves present with t = epoch + 1.  Forward, predict,
+ *                rank, evaluate and export read the table as ever.  The state is allocated by FM_OPT_FTRL
+ *                contexts only, counted by fm_device_bytes_live, zero at fm_create and after
+ *                fm_optimizer_reset; fm_load_tables and fm_init_* leave it alone; it is neither exported nor
+ *                imported.  A stage of its own in the update's place (fm_ftrl.hip; profile name "ftrl"): one
+ *                wave per window of 256 sorted entries, fixed-order fp64 sums, no float atomics; equal batches
+ *                give equal bits, prepared or sorted inline, though (unlike FM_OPT_ADAGRAD) the bits may depend
+ *                on where a run lies in the sorted view.  Serves every loss.  Single tables only and never
+ *                fused: the refusals are FM_OPT_ADAGRAD's, naming FM_OPT_FTRL.  A step on such a context needs
+ *                stepSize > 0 and regParam >= 0.
+ * opt_init     : FM_OPT_ADAGRAD: G0, the accumulators' starting value (fp64; stored as fp32).  FM_OPT_FTRL:
+ *                beta.  Either: finite and > 0, else FM_ERR_ARG.  Ignored under FM_OPT_SGD.
+ * opt_l2       : FM_OPT_FTRL's lambda2: finite and >= 0, else FM_ERR_ARG.  Ignored by the other optimizers.
  * Zero-initialise the struct: every field's 0 is its default. */
 typedef struct fm_config {
   int64_t num_features;
@@ -182,6 +213,7 @@ typedef struct fm_config {
   /* opt_init and optimizer were inserted here, not appended: loss stays the struct's last field, so its
    * offset moved by 12 bytes against earlier headers -- callers are rebuilt against this header */
   double opt_init;
+  double opt_l2; /* inserted after opt_init for the same reason */
   int32_t optimizer;
   int32_t loss;
 } fm_config;
@@ -250,11 +282,13 @@ int fm_sync(fm_ctx* ctx);
  * payloads before and after the re-key, the flags and their scan (44 bytes per row, 52 with the labels), the per-block
  * partials and a sort workspace of the stage's own (24 bytes per row), sized by the largest call. */
 int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz);
-/* Refill an FM_OPT_ADAGRAD context's accumulators with fm_config.opt_init (enqueued on the main stream;
+/* Zero-fill an FM_OPT_FTRL context's state rows, or
+ * refill an FM_OPT_ADAGRAD context's accumulators with fm_config.opt_init (enqueued on the main stream;
  * the table is not touched): the next step behaves as a first step on the current table.  A no-op on an
  * FM_OPT_SGD context; FM_ERR_ARG on a multi-GPU context.  fm_reserve on an FM_OPT_ADAGRAD context also
  * sizes the stage's scratch (12 bytes per entry for the piece flags and their scan, a count per 256 entries,
- * and the partial sums of the runs longer than a piece). */
+ * and the partial sums of the runs longer than a piece); on an FM_OPT_FTRL context, the two partial sums per
+ * window of 256 entries and a count per 1024 entries. */
 int fm_optimizer_reset(fm_ctx* ctx);
 
 /* ---- tables (C9: Strength / FactorizedInteraction, Model.scala:275-289) ------------ */
