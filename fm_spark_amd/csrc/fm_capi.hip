@@ -1961,13 +1961,25 @@ int fm_batch_from_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* c
 // Both forms of the sampled call: the exclude lists as host arrays (excl_ptr / excl_rows: checked, staged and
 // uploaded with the positives) or -- resident -- as an fm_lists (rex; null: none), whose device buffers the
 // draw reads where they are: only the positives are staged, and the E >= 1 rule reads the object's host offsets.
+// hard: the score-aware forms (fm_batch_sample_pairs_hard*, `call` their name) -- the same body with
+// k_pair_sample_hard in k_pair_sample's place, behind the summary snapshot's refresh (refresh != 0: main stream)
+// and its two events; n_neg == 0 there is the uniform call.
 static int sample_pairs_call(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, const int32_t* pos_ctx,
                              const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, const int64_t* excl_ptr,
                              const int32_t* excl_rows, bool resident, const fm_lists* rex, double pos_label, double neg_label,
-                             uint64_t seed, fm_batch** out, int32_t* sampled) {
+                             uint64_t seed, fm_batch** out, int32_t* sampled, const char* call = "fm_batch_sample_pairs",
+                             bool hard = false, int32_t n_draw = 0, int32_t refresh = 0) {
   return guarded(ctx, [&]() -> int {
-    pair_args_check(ctx, contexts, candidates, out, pos_ctx, pos_cand, n_pos, "fm_batch_sample_pairs");
-    FM_REQUIRE(n_neg >= 0 && n_neg <= 1024, "n_neg must be in [0, 1024], got " + std::to_string(n_neg));
+    pair_args_check(ctx, contexts, candidates, out, pos_ctx, pos_cand, n_pos, call);
+    if (!hard) {
+      FM_REQUIRE(n_neg >= 0 && n_neg <= 1024, "n_neg must be in [0, 1024], got " + std::to_string(n_neg));
+    } else {
+      FM_REQUIRE(n_neg >= 0 && n_neg <= n_draw && n_draw <= 1024,
+                 "0 <= n_neg <= n_draw <= 1024 must hold, got n_neg " + std::to_string(n_neg) + ", n_draw " +
+                     std::to_string(n_draw));
+      FM_REQUIRE(ctx->cfg.shard_count == 1, std::string(call) + " scores its draws against the whole table on one device "
+                                                                "(shard_count == 1): a row-sharded table is not sampled yet");
+    }
     const int64_t per = (int64_t)n_neg + 1, B = n_pos * per;
     FM_REQUIRE(B < (int64_t(1) << 31), "n_pos * (1 + n_neg) must be < 2^31");
     const int64_t U = contexts->dev.n_rows, Cn = candidates->dev.n_rows;
@@ -1990,14 +2002,56 @@ static int sample_pairs_call(fm_ctx* ctx, const fm_batch* contexts, const fm_bat
       FM_REQUIRE(Cn - L >= 1, "context " + std::to_string(u) + " (positive " + std::to_string(i) +
                                   ") has no eligible candidate row: its exclude list holds every row");
     }
+    PairWork& w = ctx->pairs;
+    // score-aware: the draws are scored and selected (n_neg == 0 or no positive: nothing to select, the uniform path)
+    const bool select = hard && n_neg >= 1 && n_pos > 0;
+    if (select && !refresh) {
+      if (w.snap_U < 0) throw ::fmhip::Error{FM_ERR_STATE, std::string(call) + " with refresh == 0 needs the snapshot of an earlier refreshing call"};
+      if (w.snap_U != U || w.snap_C != Cn)
+        throw ::fmhip::Error{FM_ERR_STATE, std::string(call) + " with refresh == 0: the snapshot is of " + std::to_string(w.snap_U) +
+                                      " context and " + std::to_string(w.snap_C) + " candidate rows, these sources have " +
+                                      std::to_string(U) + " and " + std::to_string(Cn)};
+    }
     OutBatch res = pair_out_batch(ctx, contexts, candidates, out);
     fm_batch* b = res.b;
+    const int kp = ctx->kp;
+    if (select && refresh) {
+      // The snapshot: both row sets' summaries, counts and biases as rank_summaries forms them, into the pair
+      // scratch's own buffers on the main stream -- behind every queued step, and behind the copy stream's
+      // last selection kernel that read the previous snapshot.  The copy stream waits for snap_ready below, so
+      // this call's one host wait covers the queued steps too.
+      if (!w.snap_read) {
+        FM_HIP_CHECK(hipEventCreateWithFlags(&w.snap_read, hipEventDisableTiming));
+        FM_HIP_CHECK(hipEventCreateWithFlags(&w.snap_ready, hipEventDisableTiming));
+      }
+      const size_t srow = sizeof(double) * (size_t)(kp + 2);
+      w.snap_sum_u.ensure_slack(srow * U);
+      w.snap_sum_c.ensure_slack(srow * Cn);
+      w.snap_cnt_u.ensure_slack(sizeof(uint32_t) * U);
+      w.snap_cnt_c.ensure_slack(sizeof(uint32_t) * Cn);
+      w.snap_bias_u.ensure_slack(sizeof(double) * U);
+      w.snap_bias_c.ensure_slack(sizeof(double) * Cn);
+      hipStream_t st = ctx->stream;
+      wait_built(contexts, st);
+      wait_built(candidates, st);
+      FM_HIP_CHECK(hipStreamWaitEvent(st, w.snap_read, 0));  // (never recorded: returns at once)
+      const TableView T = ctx->view();
+      const double cumE = ctx->cum_host.back();
+      hipEvent_t es = ctx->prof_begin(st);
+      launch_summary(T, contexts->dev, cumE, w.snap_sum_u.as<double>(), w.snap_cnt_u.as<uint32_t>(), st);
+      launch_summary(T, candidates->dev, cumE, w.snap_sum_c.as<double>(), w.snap_cnt_c.as<uint32_t>(), st);
+      launch_rank_bias(w.snap_sum_u.as<double>(), U, kp, w.snap_bias_u.as<double>(), st);
+      launch_rank_bias(w.snap_sum_c.as<double>(), Cn, kp, w.snap_bias_c.as<double>(), st);
+      ctx->prof_end("pair_snapshot", es, st);
+      FM_HIP_CHECK(hipEventRecord(w.snap_ready, st));
+      w.snap_U = U;
+      w.snap_C = Cn;
+    }
     // The draw, the lengths, the scan and the read-back of the entry count run in the context's scratch on
     // the copy stream before *out is touched or waited for: the one host wait of this call is for them (and
     // for what the copy stream held before: earlier gathers), never for the main or the side stream.
     if (!ctx->copy_stream) FM_HIP_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     hipStream_t gs = ctx->copy_stream;
-    PairWork& w = ctx->pairs;
     const size_t n_ex = excl_ptr ? (size_t)excl_ptr[U] : 0;
     // staging: {total int64, pad} | excl_ptr int64 [U + 1] | pos_ctx, pos_cand int32 [n_pos] | excl_rows int32 [n_ex]
     // | the drawn pairs' candidate rows int32 [B] on their way back (sampled != NULL)
@@ -2034,14 +2088,31 @@ static int sample_pairs_call(fm_ctx* ctx, const fm_batch* contexts, const fm_bat
     ctx->prof_end("pair_lists_upload", e0, gs);
     e0 = ctx->prof_begin(gs);
     const char* dl = w.lists.as<char>();  // the staging from o_ptr on
-    launch_pair_sample(reinterpret_cast<const int32_t*>(dl + (o_pc - o_ptr)), reinterpret_cast<const int32_t*>(dl + (o_pd - o_ptr)),
-                       n_pos, n_neg, ex.dev_ptr ? ex.dev_ptr : excl_ptr ? reinterpret_cast<const int64_t*>(dl) : nullptr,
-                       ex.dev_ptr ? ex.dev_rows : reinterpret_cast<const int32_t*>(dl + (o_ex - o_ptr)), pos_label, neg_label, seed,
+    const int32_t* d_pc = reinterpret_cast<const int32_t*>(dl + (o_pc - o_ptr));
+    const int32_t* d_pd = reinterpret_cast<const int32_t*>(dl + (o_pd - o_ptr));
+    const int64_t* d_xp = ex.dev_ptr ? ex.dev_ptr : excl_ptr ? reinterpret_cast<const int64_t*>(dl) : nullptr;
+    const int32_t* d_xr = ex.dev_ptr ? ex.dev_rows : reinterpret_cast<const int32_t*>(dl + (o_ex - o_ptr));
+    if (select) {
+      // the selection reads the snapshot: behind its last refresh, and the next refresh behind this read
+      FM_HIP_CHECK(hipStreamWaitEvent(gs, w.snap_ready, 0));
+      launch_pair_sample_hard(d_pc, d_pd, n_pos, n_neg, n_draw, d_xp, d_xr, pos_label, neg_label, seed, contexts->dev,
+                              candidates->dev,
+                              RankSide{w.snap_sum_u.as<double>(), w.snap_bias_u.as<double>(), w.snap_cnt_u.as<uint32_t>(), U},
+                              RankSide{w.snap_sum_c.as<double>(), w.snap_bias_c.as<double>(), w.snap_cnt_c.as<uint32_t>(), Cn},
+                              kp, ctx->cfg.w0, w.pair_ctx.as<int32_t>(), w.pair_cand.as<int32_t>(), w.label.as<double>(),
+                              w.len.as<uint32_t>(), w.row_ptr.as<int64_t>(), w.chunk_tot.as<int64_t>(),
+                              w.chunk_off.as<int64_t>(), w.total.as<int64_t>(), gs);
+      FM_HIP_CHECK(hipEventRecord(w.snap_read, gs));
+    } else {
+      launch_pair_sample(d_pc, d_pd,
+                       n_pos, n_neg, d_xp,
+                       d_xr, pos_label, neg_label, seed,
                        contexts->dev,
                        candidates->dev,
                        w.pair_ctx.as<int32_t>(), w.pair_cand.as<int32_t>(), w.label.as<double>(), w.len.as<uint32_t>(),
                        w.row_ptr.as<int64_t>(), w.chunk_tot.as<int64_t>(), w.chunk_off.as<int64_t>(), w.total.as<int64_t>(),
                        gs);
+    }
     ctx->prof_end("pair_draw", e0, gs);
     FM_HIP_CHECK(hipMemcpyAsync(pin, w.total.p, sizeof(int64_t), hipMemcpyDeviceToHost, gs));
     if (sampled && B > 0)
@@ -2084,6 +2155,22 @@ int fm_batch_sample_pairs_lists(fm_ctx* ctx, const fm_batch* contexts, const fm_
                                 double neg_label, uint64_t seed, fm_batch** out, int32_t* sampled) {
   return sample_pairs_call(ctx, contexts, candidates, pos_ctx, pos_cand, n_pos, n_neg, nullptr, nullptr, true, excl, pos_label,
                            neg_label, seed, out, sampled);
+}
+
+int fm_batch_sample_pairs_hard(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, const int32_t* pos_ctx,
+                               const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, int32_t n_draw, int32_t refresh,
+                               const int64_t* excl_ptr, const int32_t* excl_rows, double pos_label, double neg_label,
+                               uint64_t seed, fm_batch** out, int32_t* sampled) {
+  return sample_pairs_call(ctx, contexts, candidates, pos_ctx, pos_cand, n_pos, n_neg, excl_ptr, excl_rows, false, nullptr,
+                           pos_label, neg_label, seed, out, sampled, "fm_batch_sample_pairs_hard", true, n_draw, refresh);
+}
+
+int fm_batch_sample_pairs_hard_lists(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, const int32_t* pos_ctx,
+                                     const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, int32_t n_draw, int32_t refresh,
+                                     const fm_lists* excl, double pos_label, double neg_label, uint64_t seed,
+                                     fm_batch** out, int32_t* sampled) {
+  return sample_pairs_call(ctx, contexts, candidates, pos_ctx, pos_cand, n_pos, n_neg, nullptr, nullptr, true, excl, pos_label,
+                           neg_label, seed, out, sampled, "fm_batch_sample_pairs_hard_lists", true, n_draw, refresh);
 }
 
 int fm_init_from_batch(fm_ctx* ctx, fm_batch* b, int64_t* n_present) {

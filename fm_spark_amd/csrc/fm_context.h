@@ -390,6 +390,8 @@ struct fm_ctx {
       if (h.consumed) (void)hipEventDestroy(h.consumed);
     }
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
+    if (pairs.snap_read) (void)hipEventDestroy(pairs.snap_read);
+    if (pairs.snap_ready) (void)hipEventDestroy(pairs.snap_ready);
     for (auto& pe : pending) {
       (void)hipEventDestroy(pe.second.first);
       (void)hipEventDestroy(pe.second.second);
@@ -424,7 +426,8 @@ struct fm_ctx {
                       &rank.bias_u, &rank.bias_c, &rank.lkey, &rank.lidx, &rank.out_idx, &rank.out_score,
                       &rank.sel_ptr, &rank.sel_rows, &rank.tgt_ptr, &rank.tgt_rows, &rank.position, &rank.pos_score,
                       &pairs.lists, &pairs.pair_ctx, &pairs.pair_cand, &pairs.label, &pairs.len, &pairs.row_ptr,
-                      &pairs.chunk_tot, &pairs.chunk_off, &pairs.total,
+                      &pairs.chunk_tot, &pairs.chunk_off, &pairs.total, &pairs.snap_sum_u, &pairs.snap_sum_c,
+                      &pairs.snap_cnt_u, &pairs.snap_cnt_c, &pairs.snap_bias_u, &pairs.snap_bias_c,
                       &ada.flag, &ada.off, &ada.chunk_tot, &ada.chunk_off, &ada.cnt, &ada.part, &ada.hot, &ada.ucnt,
                       &ftrl.part, &ftrl.ucnt};
     for (auto* b : bufs) b->release();

@@ -289,4 +289,54 @@ __device__ __forceinline__ float gauss_draw(uint64_t seed, int64_t id, int f, do
   return (float)(g * sd);
 }
 
+// ---- a (context, candidate) pair's score as an ordered key: what the ranking kernels (fm_rank.hip) and the
+// score-aware pair sampler (fm_pairs.hip) both sort.
+constexpr uint64_t kWorstKey = 0;  // below every finite score's key
+
+// yhat -> an integer whose unsigned order is yhat's (both signs; -0 was folded into +0 before)
+__device__ __forceinline__ uint64_t key_of(double y) {
+  const uint64_t b = (uint64_t)__double_as_longlong(y);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+// (ka, ia) ranks before (kb, ib): the larger key, then the smaller row
+__device__ __forceinline__ bool before(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
+  return ka > kb || (ka == kb && ia < ib);
+}
+
+// A block's context u and its split s of n rows: w0 + a_u, whether u has a learned entry, and the
+// split's chunks [nch s / splits, nch (s + 1) / splits) of kRankChunk rows.  (S_u goes into LDS in the
+// kernel itself, one line: staged from inside a helper, k_rank_position takes 84 SGPRs for its 82.)
+struct RankContext {
+  double base;
+  bool learned;
+  int64_t ch0, ch1;
+};
+
+// The key of the context (su, x) and candidate row c: ((w0 + a_u) + b_c) + dot, the dot product one
+// chain over f = 0 .. kp - 1.  The only place a pair is scored.  kFreeUnroll: the loop's unrolling is
+// the compiler's choice (the bits are the chain's either way).
+template <bool kFreeUnroll = false>
+__device__ __forceinline__ uint64_t score_row(const double* su, const RankContext& x, const double* __restrict__ sum_c,
+                                              const double* __restrict__ bias_c, const uint32_t* __restrict__ cnt_c,
+                                              int64_t c, int kp, double w0) {
+  const double2* Sc = reinterpret_cast<const double2*>(sum_c + c * kp);
+  double dot = 0.0;
+  auto step = [&](int f) {
+    const double2 v = Sc[f];
+    dot = fma(su[2 * f], v.x, dot);
+    dot = fma(su[2 * f + 1], v.y, dot);
+  };
+  if (kFreeUnroll) {
+    // k_rank_score: more loads in flight at its 71 VGPRs (6 waves per SIMD either way)
+    for (int f = 0; f < kp / 2; ++f) step(f);
+  } else {
+    // beside the list code, unrolled further the four rows of a thread hold 83 to 90 VGPRs (5 waves per SIMD)
+#pragma unroll 2
+    for (int f = 0; f < kp / 2; ++f) step(f);
+  }
+  double y = (x.base + bias_c[c]) + dot;
+  if (!x.learned && cnt_c[c] == 0) y = w0;  // no learned entry on either side ranks at w0
+  return key_of(y + 0.0);
+}
+
 }  // namespace fmhip

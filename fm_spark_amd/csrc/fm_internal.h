@@ -534,6 +534,13 @@ struct PairWork {
   DevBuf row_ptr;              // int64 [B + 1]: their exclusive scan
   DevBuf chunk_tot, chunk_off;  // int64 per scan chunk
   DevBuf total;                // int64 [1]: the result's entries, read back by the host
+  // fm_batch_sample_pairs_hard's summary snapshot: RankWork's six per-row arrays again, of the pair scratch's
+  // own (a ranking call between two sampling calls leaves them alone).  Written on the main stream by a
+  // refreshing call (behind snap_read), read on the copy stream by the selection kernel (behind snap_ready).
+  DevBuf snap_sum_u, snap_sum_c, snap_cnt_u, snap_cnt_c, snap_bias_u, snap_bias_c;
+  int64_t snap_U = -1, snap_C = -1;  // the row counts of the two batches it was taken of; -1: no snapshot
+  hipEvent_t snap_read = nullptr;    // behind the copy stream's last selection kernel
+  hipEvent_t snap_ready = nullptr;   // behind the main stream's last refresh
 };
 // fm_batch_from_pairs / fm_batch_sample_pairs: dst row s = contexts row pair_ctx[s] followed by candidates
 // row pair_cand[s] (device lists [B]); row_ptr_in [B + 1] and label_in [B] (device) are the result's
@@ -554,6 +561,16 @@ void launch_pair_sample(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t
                         const int32_t* excl_rows, double pos_label, double neg_label, uint64_t seed, const BatchDev& contexts,
                         const BatchDev& candidates, int32_t* pair_ctx, int32_t* pair_cand, double* label, uint32_t* len,
                         int64_t* row_ptr, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total, hipStream_t st);
+// fm_batch_sample_pairs_hard's: the same outputs, each positive's negatives the n_neg of its n_draw draws
+// (launch_pair_sample's draws j = 0 .. n_draw - 1) that come first under (larger key, then smaller j), in
+// ascending j; the keys are score_row's (fm_device.h) of the context and the drawn row, from the summaries su
+// / sc.  1 <= n_neg <= n_draw <= 1024.
+void launch_pair_sample_hard(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, int32_t n_draw,
+                             const int64_t* excl_ptr, const int32_t* excl_rows, double pos_label, double neg_label,
+                             uint64_t seed, const BatchDev& contexts, const BatchDev& candidates, const RankSide& su,
+                             const RankSide& sc, int kp, double w0, int32_t* pair_ctx, int32_t* pair_cand, double* label,
+                             uint32_t* len, int64_t* row_ptr, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total,
+                             hipStream_t st);
 
 // ---------------------------------------------------------------- resident row lists (fm_lists.hip)
 // fm_lists_from_pairs' device side, in two halves around the one read-back (ptr: it sizes rows).  Both take

@@ -3,6 +3,8 @@
 //                  contexts followed by those of row pair_cand[s] of the candidates
 //   k_pair_sample  the sampled call's pairs: each positive, then its n_neg drawn candidate rows, with
 //                  every output row's label and length
+//   k_pair_sample_hard  fm_batch_sample_pairs_hard's pairs: n_draw draws per positive scored against a
+//                  summary snapshot, the best n_neg kept (a wave per positive; its comment below)
 //   k_pair_chunk_sum / k_pair_scan_chunks / k_pair_scan_rows
 //                  the exclusive scan of those lengths into the result's row_ptr, in the three phases
 //                  of fm_update.hip's split: chunk totals, a one-block scan of the totals (in rounds),
@@ -14,7 +16,9 @@
 // labels, lengths, row_ptr and the scan's chunk arrays) belongs to the context and is touched on the
 // context's copy stream alone: the uploads, these kernels, the read-back of the total and the gather
 // that reads the pairs are all enqueued there, so a call's writes queue behind the previous call's
-// gather (copy-stream order) and no event or host wait protects the scratch between calls.
+// gather (copy-stream order) and no event or host wait protects the scratch between calls.  The one
+// exception is the score-aware call's summary snapshot (PairWork::snap_*): written on the main stream by a
+// refreshing call, read on the copy stream, and ordered by the two events fm_capi.hip records around it.
 #include <algorithm>
 
 #include "fm_device.h"
@@ -100,6 +104,162 @@ __global__ __launch_bounds__(kBlock) void k_pair_sample(const int32_t* __restric
     pair_cand[r] = (int32_t)c;
     lab[r] = jj == 0 ? pos_label : neg_label;
     len[r] = (uint32_t)((u_rp[u + 1] - u_rp[u]) + (c_rp[c + 1] - c_rp[c]));
+  }
+}
+
+// ---- fm_batch_sample_pairs_hard: score-aware negatives.  Per positive i the n_draw candidate rows c_ij of
+// k_pair_sample's contract are scored against the context by score_row (fm_device.h: the ranking calls'
+// 64-bit keys, from the summary snapshot the call hands in) and the n_neg that come first under (larger key,
+// then smaller j) are emitted in ascending j.  The order is total, so the result is a function of (seed, i,
+// the list, C, the snapshot) alone; with n_neg == n_draw every draw is kept and the output is k_pair_sample's.
+//
+// One wave per positive, grid-stride, kHardWaves or kHardWavesWide waves per block; a wave owns a slice of
+// the block's dynamic LDS and never meets another wave, so there is no block barrier, only wave_lds_sync.
+//   stage   S_u (kp doubles) into the slice; w0 + a_u and "u has a learned entry" into registers
+//   draw    lane l takes the draws j = l, l + 64, ...: the hash, the binary search over the exclude list, then
+//           the kp-long fp64 fma chain over the candidate's summary row (score_row)
+//   select  n_draw <= 64: a draw per lane, all in registers.  Each lane counts the draws that come before
+//           its own -- n_draw broadcasts of a (key, j) pair -- and is kept when that rank is below n_neg: the
+//           flags come out in j order, so nothing is permuted and nothing goes through LDS.  (A register
+//           bitonic sort takes 21 exchange stages of three shuffles each whatever n_draw is, and its result
+//           has to be un-permuted back into j order; the count takes n_draw broadcasts, 16 at the usual size.)
+//           n_draw > 64: (key, j) pairs into the slice, padded to the next power of two P with (kWorstKey,
+//           0xFFFFFFFF), a wave-level bitonic sort (descending), then the first n_neg entries flag bit 31 of
+//           their draw's slot in the slice's candidate array (indexed by j, never permuted; c < 2^31)
+//   emit    in rounds of 64 draws in j order: ballot of the flags, popcount of the lanes below = the slot
+//           among the positive's negatives; pair_ctx, pair_cand, lab, len of row i (1 + n_neg) + 1 + slot.
+//           Lane 0 writes the positive's own row.
+// LDS per wave: 8 kp bytes, and 16 P bytes beyond 64 draws; P <= 512 runs four waves per block (40 KiB at
+// most), P = 1024 two (36 KiB), so no launch needs more than the default 64 KiB of dynamic LDS.
+// Integers and fp64 only, no atomics, one writer per slot.
+constexpr int kHardMaxDraw = 1024;   // n_draw, at most
+constexpr int kHardWaves = 4;        // waves per block ...
+constexpr int kHardWavesWide = 2;    // ... and once a slice holds more than 512 draws
+static_assert(kHardWaves * 64 <= kBlock && kHardMaxDraw % 64 == 0, "whole rounds of 64 draws; a block of at most kBlock");
+
+// draw j of positive i (k_pair_sample's arithmetic): the d-th row, ascending, of [0, C) without the list
+// excl_rows[x0, x0 + L)
+__device__ __forceinline__ int64_t pair_draw(uint64_t seed, int64_t i, int64_t j, const int32_t* __restrict__ excl_rows,
+                                             int64_t x0, int64_t L, int64_t C) {
+  const uint64_t E = (uint64_t)(C - L);
+  const uint64_t h = splitmix64(seed ^ splitmix64(((uint64_t)i << 20) | (uint64_t)j));
+  const int64_t d = (int64_t)(((h >> 32) * E) >> 32);
+  int64_t lo = 0, hi = L;  // the first t with excl[t] - t > d
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) / 2;
+    if ((int64_t)excl_rows[x0 + mid] - mid <= d) lo = mid + 1;
+    else hi = mid;
+  }
+  return d + lo;
+}
+
+// the summary snapshot and the two sources' row offsets, as the kernel reads them
+struct HardSources {
+  const double* sum_u;
+  const double* bias_u;
+  const uint32_t* cnt_u;
+  const double* sum_c;
+  const double* bias_c;
+  const uint32_t* cnt_c;
+  const int64_t* u_rp;
+  const int64_t* c_rp;
+};
+
+// kWide: n_draw > 64 (a kernel each: together they spill SGPRs)
+template <int kWaves, bool kWide>
+__global__ __launch_bounds__(kWaves * 64) void k_pair_sample_hard(
+    const int32_t* __restrict__ pos_ctx, const int32_t* __restrict__ pos_cand, int64_t n_pos, int32_t n_neg, int32_t n_draw,
+    int32_t P, const int64_t* __restrict__ excl_ptr, const int32_t* __restrict__ excl_rows, int64_t C, double pos_label,
+    double neg_label, uint64_t seed, HardSources s, int kp, double w0, int32_t* __restrict__ pair_ctx,
+    int32_t* __restrict__ pair_cand, double* __restrict__ lab, uint32_t* __restrict__ len) {
+  extern __shared__ __align__(16) unsigned char hard_lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr bool wide = kWide;
+  const size_t slice = sizeof(double) * (size_t)kp + (wide ? (size_t)16 * P : 0);
+  double* su = reinterpret_cast<double*>(hard_lds + slice * wave);
+  uint64_t* key = reinterpret_cast<uint64_t*>(su + kp);                 // [P]
+  uint32_t* idx = reinterpret_cast<uint32_t*>(key + (wide ? P : 0));    // [P]: the draw j of a sorted entry
+  uint32_t* cand = idx + (wide ? P : 0);                                // [P]: c of draw j; bit 31 = kept
+  const uint64_t below = (1ull << lane) - 1;
+  const int64_t per = (int64_t)n_neg + 1;
+  for (int64_t i = (int64_t)blockIdx.x * kWaves + wave; i < n_pos; i += (int64_t)gridDim.x * kWaves) {
+    wave_lds_sync();  // the slice's previous positive has been read
+    const int64_t u = pos_ctx[i];
+    for (int f = lane; f < kp; f += 64) su[f] = s.sum_u[u * kp + f];
+    const RankContext x = {w0 + s.bias_u[u], s.cnt_u[u] != 0, 0, 0};
+    const int64_t x0 = excl_ptr ? excl_ptr[u] : 0, L = excl_ptr ? excl_ptr[u + 1] - x0 : 0;
+    const int64_t lu = s.u_rp[u + 1] - s.u_rp[u];
+    const int64_t r0 = i * per;
+    if (lane == 0) {
+      const int64_t c = pos_cand[i];
+      pair_ctx[r0] = (int32_t)u;
+      pair_cand[r0] = (int32_t)c;
+      lab[r0] = pos_label;
+      len[r0] = (uint32_t)(lu + (s.c_rp[c + 1] - s.c_rp[c]));
+    }
+    wave_lds_sync();  // S_u is staged
+    // one round of the emit: this lane's draw (row c, kept or not) -> its slot behind the `done` kept before
+    auto emit = [&](bool kept, int64_t c, int done) {
+      const uint64_t m = __ballot(kept);
+      if (kept) {
+        const int64_t r = r0 + 1 + done + __popcll(m & below);
+        pair_ctx[r] = (int32_t)u;
+        pair_cand[r] = (int32_t)c;
+        lab[r] = neg_label;
+        len[r] = (uint32_t)(lu + (s.c_rp[c + 1] - s.c_rp[c]));
+      }
+      return done + (int)__popcll(m);
+    };
+    if constexpr (!wide) {
+      uint64_t k = kWorstKey;
+      int64_t c = 0;
+      if (lane < n_draw) {
+        c = pair_draw(seed, i, lane, excl_rows, x0, L, C);
+        k = score_row(su, x, s.sum_c, s.bias_c, s.cnt_c, c, kp, w0);
+      }
+      int rank = 0;  // the draws that come before this lane's
+      for (int j = 0; j < n_draw; ++j) rank += before(__shfl(k, j), (uint32_t)j, k, (uint32_t)lane) ? 1 : 0;
+      emit(lane < n_draw && rank < n_neg, c, 0);
+      continue;
+    }
+    for (int j = lane; j < P; j += 64) {
+      uint64_t k = kWorstKey;
+      uint32_t c = 0;
+      if (j < n_draw) {
+        c = (uint32_t)pair_draw(seed, i, j, excl_rows, x0, L, C);
+        k = score_row(su, x, s.sum_c, s.bias_c, s.cnt_c, c, kp, w0);
+      }
+      key[j] = k;
+      idx[j] = j < n_draw ? (uint32_t)j : 0xFFFFFFFFu;
+      cand[j] = c;
+    }
+    wave_lds_sync();
+    // bitonic sort of (key, idx), descending: partner distance d inside blocks of kk (fm_rank.hip's bitonic_stage,
+    // a wave's worth)
+    for (int kk = 2; kk <= P; kk <<= 1) {
+      for (int d = kk >> 1; d > 0; d >>= 1) {
+        for (int t = lane; t < P / 2; t += 64) {
+          const int a = ((t & ~(d - 1)) << 1) | (t & (d - 1));
+          const int b = a | d;
+          const uint64_t ka = key[a], kb = key[b];
+          const uint32_t ia = idx[a], ib = idx[b];
+          const bool desc = (a & kk) == 0;
+          if (before(kb, ib, ka, ia) == desc) {
+            key[a] = kb; idx[a] = ib;
+            key[b] = ka; idx[b] = ia;
+          }
+        }
+        wave_lds_sync();
+      }
+    }
+    for (int t = lane; t < n_neg; t += 64) cand[idx[t]] |= 0x80000000u;  // distinct j: one writer per slot
+    wave_lds_sync();
+    int done = 0;
+    for (int j0 = 0; j0 < n_draw; j0 += 64) {
+      const int j = j0 + lane;
+      const uint32_t cj = j < n_draw ? cand[j] : 0;
+      done = emit((cj >> 31) != 0, (int64_t)(cj & 0x7FFFFFFFu), done);
+    }
   }
 }
 
@@ -217,6 +377,34 @@ void launch_pair_sample(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t
   hipLaunchKernelGGL(k_pair_sample, dim3(grid_for(B, kBlock)), dim3(kBlock), 0, st, pos_ctx, pos_cand, B, n_neg, excl_ptr,
                      excl_rows, candidates.n_rows, pos_label, neg_label, seed, contexts.row_ptr.as<int64_t>(),
                      candidates.row_ptr.as<int64_t>(), pair_ctx, pair_cand, label, len);
+  launch_len_scan(len, B, row_ptr, chunk_tot, chunk_off, total, st);
+}
+
+void launch_pair_sample_hard(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, int32_t n_draw,
+                             const int64_t* excl_ptr, const int32_t* excl_rows, double pos_label, double neg_label,
+                             uint64_t seed, const BatchDev& contexts, const BatchDev& candidates, const RankSide& su,
+                             const RankSide& sc, int kp, double w0, int32_t* pair_ctx, int32_t* pair_cand, double* label,
+                             uint32_t* len, int64_t* row_ptr, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total,
+                             hipStream_t st) {
+  const int64_t B = n_pos * ((int64_t)n_neg + 1);
+  if (B <= 0) {
+    launch_len_scan(len, 0, row_ptr, chunk_tot, chunk_off, total, st);
+    return;
+  }
+  int P = 64;  // the slice's sorted entries: the power of two that holds n_draw (not read up to 64 draws)
+  while (P < n_draw) P <<= 1;
+  const HardSources s = {su.sum, su.bias, su.cnt, sc.sum, sc.bias, sc.cnt, contexts.row_ptr.as<int64_t>(),
+                         candidates.row_ptr.as<int64_t>()};
+  const size_t slice = sizeof(double) * (size_t)kp + (n_draw > 64 ? (size_t)16 * P : 0);
+  const auto launch = [&](auto kern, int waves) {
+    const int64_t blocks = (n_pos + waves - 1) / waves;
+    hipLaunchKernelGGL(kern, dim3(grid_for(blocks * waves * 64, waves * 64, 256 * 8)), dim3(waves * 64), slice * waves, st,
+                       pos_ctx, pos_cand, n_pos, n_neg, n_draw, P, excl_ptr, excl_rows, candidates.n_rows, pos_label, neg_label,
+                       seed, s, kp, w0, pair_ctx, pair_cand, label, len);
+  };
+  if (n_draw <= 64) launch(k_pair_sample_hard<kHardWaves, false>, kHardWaves);
+  else if (P <= 512) launch(k_pair_sample_hard<kHardWaves, true>, kHardWaves);
+  else launch(k_pair_sample_hard<kHardWavesWide, true>, kHardWavesWide);
   launch_len_scan(len, B, row_ptr, chunk_tot, chunk_off, total, st);
 }
 

@@ -527,11 +527,18 @@ class FMContext:
 
     def batch_sample_pairs(self, contexts: DeviceBatch, candidates: DeviceBatch, pos_ctx, pos_cand, n_neg: int, *,
                            exclude=None, pos_label: float = 1.0, neg_label: float = 0.0, seed: int = 0,
-                           into: DeviceBatch | None = None, want_sampled: bool = False):
+                           into: DeviceBatch | None = None, want_sampled: bool = False, n_draw: int | None = None,
+                           refresh: bool = True):
         """The implicit-feedback mini-batch of the positives (pos_ctx[i], pos_cand[i]), each followed by
         n_neg negatives drawn on the device uniformly over the candidate rows its context's ``exclude``
         list does not hold (fm_batch_sample_pairs; the lists as rank(exclude=) takes them).  Returns the
-        batch, or (batch, sampled [n_pos, n_neg] int32 candidate rows) with want_sampled."""
+        batch, or (batch, sampled [n_pos, n_neg] int32 candidate rows) with want_sampled.
+
+        ``n_draw`` (n_neg .. 1024): score-aware negatives (fm_batch_sample_pairs_hard) -- n_draw rows are
+        drawn per positive and the n_neg the model scores highest are kept, in draw order.  ``refresh``
+        recomputes the scores' snapshot behind every queued step; refresh=False scores against the
+        snapshot of the last refreshing call (same contexts and candidates: only their row counts are
+        checked) and does not wait for the step in flight.  None: the uniform call."""
         if exclude is None:
             ex = (None, None)
         elif isinstance(exclude, RowLists):
@@ -539,12 +546,13 @@ class FMContext:
         else:
             ex = normalize_row_lists(exclude, contexts.n_rows)
         return self._sample_pairs(contexts, candidates, pos_ctx, pos_cand, n_neg, ex, pos_label, neg_label, seed, into,
-                                  want_sampled)
+                                  want_sampled, n_draw, refresh)
 
     def _sample_pairs(self, contexts, candidates, pos_ctx, pos_cand, n_neg, ex, pos_label, neg_label, seed, into,
-                      want_sampled):
+                      want_sampled, n_draw=None, refresh=True):
         """batch_sample_pairs with the exclude lists already normalised: ex = (ptr, rows), (None, None) or a
-        RowLists (fm_batch_sample_pairs_lists) -- a loop normalises its lists once, or makes them resident."""
+        RowLists (fm_batch_sample_pairs_lists) -- a loop normalises its lists once, or makes them resident.
+        n_draw not None: the _hard symbols, with n_draw and refresh behind n_neg."""
         pc = np.ascontiguousarray(pos_ctx, dtype=np.int32)
         pd = np.ascontiguousarray(pos_cand, dtype=np.int32)
         if not (pc.ndim == pd.ndim == 1 and len(pc) == len(pd)):
@@ -556,12 +564,16 @@ class FMContext:
         head = (self.handle, contexts.handle, candidates.handle, N.ptr(pc, C.c_int32), N.ptr(pd, C.c_int32), len(pc), n_neg)
         tail = (float(pos_label), float(neg_label), int(seed) & (2**64 - 1), C.byref(h),
                 N.ptr(sampled, C.c_int32) if want_sampled else None)
+        name = "fm_batch_sample_pairs"
+        if n_draw is not None:
+            name += "_hard"
+            head += (int(n_draw), 1 if refresh else 0)
         if isinstance(ex, RowLists):
-            N.check(self._lib.fm_batch_sample_pairs_lists(*head, ex.handle, *tail), "fm_batch_sample_pairs_lists")
+            N.check(getattr(self._lib, name + "_lists")(*head, ex.handle, *tail), name + "_lists")
         else:
-            N.check(self._lib.fm_batch_sample_pairs(
+            N.check(getattr(self._lib, name)(
                 *head, None if ex[0] is None else N.ptr(ex[0], C.c_int64),
-                None if ex[1] is None else N.ptr(ex[1], C.c_int32), *tail), "fm_batch_sample_pairs")
+                None if ex[1] is None else N.ptr(ex[1], C.c_int32), *tail), name)
         self._pair_batch(b, h, contexts, candidates)
         return (b, sampled[: len(pc) * n_neg].reshape(len(pc), n_neg)) if want_sampled else b
 

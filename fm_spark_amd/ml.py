@@ -407,6 +407,10 @@ class FactorizationMachinesSGD:
         "binaryValidationData": None,
         # not in the reference: negatives drawn per positive by fitInteractions
         "negativesPerPositive": 4,
+        # score-aware negatives (fm_batch_sample_pairs_hard): the draws per positive, None = uniform; and the
+        # iterations between two refreshes of the scores' snapshot
+        "negativeCandidates": None,
+        "negativeRefreshEvery": 1,
         # not in the reference (its loss is the squared error, SGD.scala:134-146): the step's objective
         "loss": "squared",
         # not in the reference (one rate stepSize / sqrt(t) for every row): the row update and, for "adagrad",
@@ -510,6 +514,22 @@ class FactorizationMachinesSGD:
             raise ValueError("negativesPerPositive must be an integer in [0, 1024]")
         return self._set("negativesPerPositive", int(n))
 
+    def setNegativeCandidates(self, n):
+        """Score-aware negatives: fitInteractions draws n candidate rows per positive (1 .. 1024, at least
+        negativesPerPositive at the fit) and keeps the negativesPerPositive the current model scores highest
+        (fm_batch_sample_pairs_hard).  None (default): uniform negatives, today's calls and bits."""
+        if n is not None and (isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= 1024):
+            raise ValueError("negativeCandidates must be None or an integer in [1, 1024]")
+        return self._set("negativeCandidates", None if n is None else int(n))
+
+    def setNegativeRefreshEvery(self, r: int):
+        """With negativeCandidates set: the scores' snapshot is recomputed at the iterations t = 1 (mod r)
+        (default 1: at every one); the iterations between score their draws against the last snapshot and
+        do not wait for the step in flight."""
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or int(r) < 1:
+            raise ValueError("negativeRefreshEvery must be an integer >= 1")
+        return self._set("negativeRefreshEvery", int(r))
+
     def setLoss(self, loss: str):
         """The objective each step descends (fm_config.loss): "squared" (default, the reference's),
         "logistic" -- log loss of sigma(score) against labels in [0, 1], for click / binary labels and for
@@ -564,6 +584,8 @@ class FactorizationMachinesSGD:
     def getInitialAccumulator(self): return self._params["initialAccumulator"]
     def getLoss(self): return self._params["loss"]
     def getNegativesPerPositive(self): return self._params["negativesPerPositive"]
+    def getNegativeCandidates(self): return self._params["negativeCandidates"]
+    def getNegativeRefreshEvery(self): return self._params["negativeRefreshEvery"]
     def getDimFactorization(self): return self._params["dimFactorization"]
     def getMaxIter(self): return self._params["maxIter"]
     def getMiniBatchFraction(self): return self._params["miniBatchFraction"]
@@ -742,12 +764,18 @@ class FactorizationMachinesSGD:
         perm[((t - 1) * m + arange(m)) % n] in that order with the draw seed splitmix64(seed) ^ t, into
         one of two batches in turn, sorted on the side stream while the previous iteration steps; the
         steps only enqueue and the loss lines are written after the loop, as the pipelined fit's.
+        With negativeCandidates = d set, iteration t draws d rows per positive with the same seed and keeps
+        the negativesPerPositive the model scores highest (fm_batch_sample_pairs_hard_lists, n_draw = d),
+        refreshing the scores' snapshot when (t - 1) % negativeRefreshEvery == 0; the loop is otherwise the same.
         ``initial_tables`` = (ids, w, V) replaces the seeded draw over every id of either frame.  A
         multi-GPU estimator (setParallel) and a set validationData raise ValueError: not built yet."""
         p = self._params
         self._check_loss()
         if p["loss"] == "bpr" and p["negativesPerPositive"] < 1:
             raise ValueError('loss "bpr" needs negativesPerPositive >= 1: a positive is ranked against its negatives')
+        n_draw, refresh_every = p["negativeCandidates"], p["negativeRefreshEvery"]
+        if n_draw is not None and n_draw < p["negativesPerPositive"]:
+            raise ValueError("negativeCandidates must be at least negativesPerPositive: the negatives are chosen among them")
         if p["parallel"] is not None:
             raise ValueError("fitInteractions runs on one GPU: a multi-GPU estimator (setParallel) is not supported yet")
         if p["validationData"] is not None:
@@ -801,7 +829,7 @@ class FactorizationMachinesSGD:
         def sample(t):
             take = perm[((t - 1) * m + np.arange(m)) % n]
             bufs[t % 2] = ctx._sample_pairs(bu, bc, pos_ctx[take], pos_cand[take], n_neg, ex, 1.0, 0.0, seed0 ^ t,
-                                            bufs[t % 2], False)
+                                            bufs[t % 2], False, n_draw, (t - 1) % refresh_every == 0)
             bufs[t % 2].prepare()
 
         e0 = ctx.epoch

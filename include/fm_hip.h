@@ -274,7 +274,8 @@ int fm_sync(fm_ctx* ctx);
  * scratch of fm_rank_positions / fm_rank_positions_batch: the same row summaries, the device copies of
  * its target and exclude lists and its results, 12 bytes per target; nor the scratch of
  * fm_batch_sample_pairs: the device copies of its lists, the drawn pairs with their labels, lengths and
- * row_ptr (28 bytes per result row) and the scan's per-chunk sums, sized by the largest call.  The
+ * row_ptr (28 bytes per result row) and the scan's per-chunk sums, sized by the largest call; nor the
+ * summary snapshot of fm_batch_sample_pairs_hard, sized by its two row sets at a refreshing call.  The
  * _lists forms of these calls (fm_rank_batch_select_lists, fm_rank_positions_batch_lists,
  * fm_batch_sample_pairs_lists) keep no list copies in the context's scratch: they read the fm_lists'
  * own buffers, and the rest of their scratch is the host-list forms'.  Nor is the scratch of
@@ -409,6 +410,41 @@ int fm_batch_sample_pairs(fm_ctx* ctx, const fm_batch* contexts, const fm_batch*
                           const int64_t* excl_ptr, const int32_t* excl_rows,
                           double pos_label, double neg_label, uint64_t seed,
                           fm_batch** out, int32_t* sampled);
+/* fm_batch_sample_pairs with score-aware ("hard") negatives, selected on the device: per positive i the
+ * n_draw candidate rows c_ij, j = 0 .. n_draw - 1, of the contract above (same hash, same exclude-list
+ * arithmetic, same E >= 1 rule) are scored against context pos_ctx[i], and the n_neg that come first under
+ * (larger key, then smaller j) are kept and emitted in ascending j.  The key of a draw is the ranking calls'
+ * 64-bit key of the pair: the unclamped yhat of the concatenated row, ((w0 + a_u) + a_c) + <S_u, S_c> summed
+ * in fm_rank_batch's order, w0 for a pair without a learned entry on either side -- the bits fm_rank_batch
+ * sorts.  The order is total, so the result does not depend on the launch, on n_pos or on the other
+ * positives.  Draws are independent as above: a row drawn twice may be kept twice, and a positive's own
+ * candidate is a draw like any other unless it is on its context's list.  Layout, labels, fm_batch_group
+ * (1 + n_neg) and sampled as fm_batch_sample_pairs; with n_draw == n_neg every draw is kept and the call is
+ * fm_batch_sample_pairs bit for bit.  0 <= n_neg <= n_draw <= 1024 (FM_ERR_ARG); n_neg == 0 behaves as the
+ * uniform call (nothing is scored, no snapshot is taken or needed).  Everything else is checked as
+ * fm_batch_sample_pairs checks it, before anything is enqueued; a refused call changes nothing on the
+ * device.  A multi-GPU context and shard_count > 1 are FM_ERR_ARG (the message names the call).
+ * The scores are read from a snapshot of both row sets' summaries, kept in the context's pair scratch
+ * (not the ranking calls' scratch: a ranking call between two sampling calls leaves it alone):
+ *   refresh != 0 : the snapshot is recomputed on the main stream, behind every step enqueued before the
+ *           call (and behind the copy stream's last selection that read the old one); the copy stream
+ *           waits for it.  The scores are those of the table after every step enqueued before the call,
+ *           and the call's one host wait therefore covers those steps too.
+ *   refresh == 0 : the draws are scored against the snapshot the last refreshing call left; the main stream
+ *           is not touched, and the one host wait is the copy stream's, as the uniform call's: it overlaps
+ *           the step in flight.  FM_ERR_STATE without a snapshot, or with one taken of batches with other
+ *           row counts than these sources'.  The snapshot remembers only those two counts: passing other
+ *           batches of the same row counts scores these draws with the old batches' rows -- the
+ *           caller's responsibility.
+ * Two equal sequences of calls give equal bits.  The snapshot ((U + C) (k' + 3) doubles and a count per
+ * row) is counted by fm_device_bytes_live and grows to the largest call: two equal calls leave the live
+ * counters equal.  Profile: "pair_snapshot" (main stream), "pair_draw" (copy stream: draw, score, select,
+ * scan). */
+int fm_batch_sample_pairs_hard(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates,
+                               const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
+                               int32_t n_draw, int32_t refresh, const int64_t* excl_ptr, const int32_t* excl_rows,
+                               double pos_label, double neg_label, uint64_t seed,
+                               fm_batch** out, int32_t* sampled);
 /* A training dataset laid out split after split, made resident once: the rows of csr are the
  * randomSplit splits of the cached dfData concatenated in iteration order (FactorizationMachinesSGD
  * .scala:93, 111-112), split s = rows [split_rows[s], split_rows[s + 1]) (split_rows [n_splits + 1],
@@ -763,6 +799,12 @@ int fm_batch_sample_pairs_lists(fm_ctx* ctx, const fm_batch* contexts, const fm_
                                 const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
                                 const fm_lists* excl, double pos_label, double neg_label, uint64_t seed,
                                 fm_batch** out, int32_t* sampled);
+/* fm_batch_sample_pairs_hard with its exclude lists resident, as fm_batch_sample_pairs_lists is to
+ * fm_batch_sample_pairs: the same path and the same bits. */
+int fm_batch_sample_pairs_hard_lists(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates,
+                                     const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
+                                     int32_t n_draw, int32_t refresh, const fm_lists* excl, double pos_label,
+                                     double neg_label, uint64_t seed, fm_batch** out, int32_t* sampled);
 /* calcLossGrad (Model.scala:135-234), per active entry e in CSR order:
  * pred[e] = yhat of its row (unclamped), loss[e] = (yhat - y)^2, delta_w[e] = x,
  * delta_v[e*k + f] = vfxiSum_f * x - (v_f * x) * x.  Any output may be NULL.
