@@ -176,6 +176,13 @@ SIGNATURES = {
                                              _I32P, C.c_double, C.c_double, C.c_uint64, C.POINTER(_P), _I32P]),
     "fm_batch_sample_pairs_hard_lists": (C.c_int, [_P, _P, _P, _I32P, _I32P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P,
                                                    C.c_double, C.c_double, C.c_uint64, C.POINTER(_P), _I32P]),
+    "fm_row_weights_create": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(_P)]),
+    "fm_row_weights_destroy": (None, [_P]),
+    "fm_row_weights_candidates": (C.c_int64, [_P]),
+    "fm_row_weights_total": (C.c_int64, [_P]),
+    "fm_row_weights_bind": (C.c_int, [_P, _P, _P]),
+    "fm_batch_sample_pairs_weighted": (C.c_int, [_P, _P, _P, _I32P, _I32P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                                 C.c_double, C.c_double, C.c_uint64, C.POINTER(_P), _I32P]),
     "fm_init_from_batch": (C.c_int, [_P, _P, _I64P]),
     "fm_loss_grad": (C.c_int, [_P, C.POINTER(fm_csr), _DP, _DP, _DP, _DP]),
     "fm_calc_loss_grad": (C.c_int, [_P, C.POINTER(fm_csr), C.c_double, C.c_uint64, _DP, _DP, _DP, _DP]),

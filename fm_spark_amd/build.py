@@ -17,7 +17,7 @@ ARCH = os.environ.get("FM_HIP_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["fm_forward.hip", "fm_objective.hip", "fm_update.hip", "fm_adagrad.hip", "fm_ftrl.hip", "fm_table.hip", "fm_batch.hip", "fm_sort.hip", "fm_capi.hip",
-           "fm_rank.hip", "fm_pairs.hip", "fm_lists.hip", "fm_binary.hip", "fm_shard.hip", "fm_group.hip", "fm_sampler.cpp", "fm_libsvm.cpp"]
+           "fm_rank.hip", "fm_pairs.hip", "fm_weights.hip", "fm_lists.hip", "fm_binary.hip", "fm_shard.hip", "fm_group.hip", "fm_sampler.cpp", "fm_libsvm.cpp"]
 HEADERS = ["fm_internal.h", "fm_device.h", "fm_context.h", "fm_hostpool.h"]
 
 # sources compiled without packed fp32 arithmetic (v_pk_add/mul/fma_f32): some forms of these instructions have

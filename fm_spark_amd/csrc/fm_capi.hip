@@ -1708,7 +1708,9 @@ static void lists_args_check(const fm_ctx* ctx, int64_t U, int64_t C, fm_lists**
 }
 
 static std::unique_ptr<fm_lists> new_lists(fm_ctx* ctx, int64_t U, int64_t C) {
+  static std::atomic<uint64_t> next_serial{1};
   std::unique_ptr<fm_lists> l(new fm_lists());
+  l->serial = next_serial.fetch_add(1);
   l->owner = ctx;
   l->device = ctx->cfg.device;
   l->U = U;
@@ -1968,17 +1970,29 @@ static int sample_pairs_call(fm_ctx* ctx, const fm_batch* contexts, const fm_bat
                              const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, const int64_t* excl_ptr,
                              const int32_t* excl_rows, bool resident, const fm_lists* rex, double pos_label, double neg_label,
                              uint64_t seed, fm_batch** out, int32_t* sampled, const char* call = "fm_batch_sample_pairs",
-                             bool hard = false, int32_t n_draw = 0, int32_t refresh = 0) {
+                             bool hard = false, int32_t n_draw = 0, int32_t refresh = 0, const fm_row_weights* rw = nullptr) {
   return guarded(ctx, [&]() -> int {
     pair_args_check(ctx, contexts, candidates, out, pos_ctx, pos_cand, n_pos, call);
+    // rw: fm_batch_sample_pairs_weighted -- the weighted draw in the uniform one's place; its draws are scored
+    // and selected only where n_draw > n_neg
+    const bool scored = rw ? n_draw > n_neg : hard;
     if (!hard) {
       FM_REQUIRE(n_neg >= 0 && n_neg <= 1024, "n_neg must be in [0, 1024], got " + std::to_string(n_neg));
     } else {
       FM_REQUIRE(n_neg >= 0 && n_neg <= n_draw && n_draw <= 1024,
                  "0 <= n_neg <= n_draw <= 1024 must hold, got n_neg " + std::to_string(n_neg) + ", n_draw " +
                      std::to_string(n_draw));
-      FM_REQUIRE(ctx->cfg.shard_count == 1, std::string(call) + " scores its draws against the whole table on one device "
-                                                                "(shard_count == 1): a row-sharded table is not sampled yet");
+      FM_REQUIRE(!scored || ctx->cfg.shard_count == 1,
+                 std::string(call) + " scores its draws against the whole table on one device "
+                                     "(shard_count == 1): a row-sharded table is not sampled yet");
+    }
+    if (rw) {
+      FM_REQUIRE(rw->owner == ctx, "weights: the weights belong to another context");
+      FM_REQUIRE(rw->C == candidates->dev.n_rows, "weights: weights of " + std::to_string(rw->C) +
+                                                      " candidate rows for candidates of " +
+                                                      std::to_string(candidates->dev.n_rows) + " rows");
+      FM_REQUIRE(!rex || (rw->bound == rex && rw->bound_serial == rex->serial),
+                 "weights: the weights are not bound to these exclude lists (fm_row_weights_bind binds one fm_lists at a time)");
     }
     const int64_t per = (int64_t)n_neg + 1, B = n_pos * per;
     FM_REQUIRE(B < (int64_t(1) << 31), "n_pos * (1 + n_neg) must be < 2^31");
@@ -1998,13 +2012,21 @@ static int sample_pairs_call(fm_ctx* ctx, const fm_batch* contexts, const fm_bat
       const int64_t u = pos_ctx[i], c = pos_cand[i];
       FM_REQUIRE(u >= 0 && u < U, "pos_ctx index out of [0, rows of contexts)");
       FM_REQUIRE(c >= 0 && c < Cn, "pos_cand index out of [0, rows of candidates)");
+      if (rw) {
+        // the binding's host copy of E_w (fm_row_weights_bind read it back): nothing is waited for here
+        const uint64_t Ew = rex ? (uint64_t)rw->host_ew[(size_t)u] : rw->W;
+        FM_REQUIRE(Ew >= 1, "context " + std::to_string(u) + " (positive " + std::to_string(i) +
+                                ") has no eligible candidate row: its exclude list holds every row of non-zero weight "
+                                "(eligible weight 0)");
+        continue;
+      }
       const int64_t L = ex.ptr ? ex.ptr[u + 1] - ex.ptr[u] : 0;
       FM_REQUIRE(Cn - L >= 1, "context " + std::to_string(u) + " (positive " + std::to_string(i) +
                                   ") has no eligible candidate row: its exclude list holds every row");
     }
     PairWork& w = ctx->pairs;
     // score-aware: the draws are scored and selected (n_neg == 0 or no positive: nothing to select, the uniform path)
-    const bool select = hard && n_neg >= 1 && n_pos > 0;
+    const bool select = scored && n_neg >= 1 && n_pos > 0;
     if (select && !refresh) {
       if (w.snap_U < 0) throw ::fmhip::Error{FM_ERR_STATE, std::string(call) + " with refresh == 0 needs the snapshot of an earlier refreshing call"};
       if (w.snap_U != U || w.snap_C != Cn)
@@ -2092,17 +2114,32 @@ static int sample_pairs_call(fm_ctx* ctx, const fm_batch* contexts, const fm_bat
     const int32_t* d_pd = reinterpret_cast<const int32_t*>(dl + (o_pd - o_ptr));
     const int64_t* d_xp = ex.dev_ptr ? ex.dev_ptr : excl_ptr ? reinterpret_cast<const int64_t*>(dl) : nullptr;
     const int32_t* d_xr = ex.dev_ptr ? ex.dev_rows : reinterpret_cast<const int32_t*>(dl + (o_ex - o_ptr));
+    // the weighted draw's inputs: the cdf and, with lists, their binding (checked above to be of rex)
+    const WeightedDraw wd = rw ? WeightedDraw{rw->cdf.as<int64_t>(), rex ? rw->keys.as<uint2>() : nullptr,
+                                              rex ? rw->ew.as<uint32_t>() : nullptr, rw->W}
+                               : WeightedDraw{};
     if (select) {
       // the selection reads the snapshot: behind its last refresh, and the next refresh behind this read
       FM_HIP_CHECK(hipStreamWaitEvent(gs, w.snap_ready, 0));
-      launch_pair_sample_hard(d_pc, d_pd, n_pos, n_neg, n_draw, d_xp, d_xr, pos_label, neg_label, seed, contexts->dev,
-                              candidates->dev,
-                              RankSide{w.snap_sum_u.as<double>(), w.snap_bias_u.as<double>(), w.snap_cnt_u.as<uint32_t>(), U},
-                              RankSide{w.snap_sum_c.as<double>(), w.snap_bias_c.as<double>(), w.snap_cnt_c.as<uint32_t>(), Cn},
-                              kp, ctx->cfg.w0, w.pair_ctx.as<int32_t>(), w.pair_cand.as<int32_t>(), w.label.as<double>(),
-                              w.len.as<uint32_t>(), w.row_ptr.as<int64_t>(), w.chunk_tot.as<int64_t>(),
-                              w.chunk_off.as<int64_t>(), w.total.as<int64_t>(), gs);
+      const RankSide su{w.snap_sum_u.as<double>(), w.snap_bias_u.as<double>(), w.snap_cnt_u.as<uint32_t>(), U};
+      const RankSide sc{w.snap_sum_c.as<double>(), w.snap_bias_c.as<double>(), w.snap_cnt_c.as<uint32_t>(), Cn};
+      if (rw)
+        launch_pair_sample_hard_weighted(d_pc, d_pd, n_pos, n_neg, n_draw, d_xp, wd, pos_label, neg_label, seed, contexts->dev,
+                                         candidates->dev, su, sc, kp, ctx->cfg.w0, w.pair_ctx.as<int32_t>(),
+                                         w.pair_cand.as<int32_t>(), w.label.as<double>(), w.len.as<uint32_t>(),
+                                         w.row_ptr.as<int64_t>(), w.chunk_tot.as<int64_t>(), w.chunk_off.as<int64_t>(),
+                                         w.total.as<int64_t>(), gs);
+      else
+        launch_pair_sample_hard(d_pc, d_pd, n_pos, n_neg, n_draw, d_xp, d_xr, pos_label, neg_label, seed, contexts->dev,
+                                candidates->dev, su, sc, kp, ctx->cfg.w0, w.pair_ctx.as<int32_t>(), w.pair_cand.as<int32_t>(),
+                                w.label.as<double>(), w.len.as<uint32_t>(), w.row_ptr.as<int64_t>(), w.chunk_tot.as<int64_t>(),
+                                w.chunk_off.as<int64_t>(), w.total.as<int64_t>(), gs);
       FM_HIP_CHECK(hipEventRecord(w.snap_read, gs));
+    } else if (rw) {
+      launch_pair_sample_weighted(d_pc, d_pd, n_pos, n_neg, d_xp, wd, pos_label, neg_label, seed, contexts->dev,
+                                  candidates->dev, w.pair_ctx.as<int32_t>(), w.pair_cand.as<int32_t>(), w.label.as<double>(),
+                                  w.len.as<uint32_t>(), w.row_ptr.as<int64_t>(), w.chunk_tot.as<int64_t>(),
+                                  w.chunk_off.as<int64_t>(), w.total.as<int64_t>(), gs);
     } else {
       launch_pair_sample(d_pc, d_pd,
                        n_pos, n_neg, d_xp,
@@ -2171,6 +2208,111 @@ int fm_batch_sample_pairs_hard_lists(fm_ctx* ctx, const fm_batch* contexts, cons
                                      fm_batch** out, int32_t* sampled) {
   return sample_pairs_call(ctx, contexts, candidates, pos_ctx, pos_cand, n_pos, n_neg, nullptr, nullptr, true, excl, pos_label,
                            neg_label, seed, out, sampled, "fm_batch_sample_pairs_hard_lists", true, n_draw, refresh);
+}
+
+// ---- popularity-weighted negatives (fm_row_weights_*, fm_batch_sample_pairs_weighted; fm_weights.hip) ----
+int fm_row_weights_create(fm_ctx* ctx, int64_t C, const uint32_t* weight, fm_row_weights** out) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(out != nullptr, "null out");
+    FM_REQUIRE(!ctx->group, "fm_row_weights_create needs a context of one device: a multi-GPU context's batches are cut over "
+                            "its ranks, and the call that draws by these weights refuses it");
+    FM_REQUIRE(C >= 0 && C < (int64_t(1) << 31), "row weights: C must be in [0, 2^31), got " + std::to_string(C));
+    FM_REQUIRE(C == 0 || weight != nullptr, "row weights: null weight");
+    uint64_t W = 0;  // (C < 2^31 weights below 2^32: no overflow)
+    for (int64_t c = 0; c < C; ++c) W += weight[c];
+    FM_REQUIRE(W >= 1, "row weights: every weight is 0 (W = 0): at least one candidate row needs a weight >= 1");
+    FM_REQUIRE(W < (uint64_t(1) << 32), "row weights: the weights sum to W = " + std::to_string(W) + ", W must be below 2^32");
+    std::unique_ptr<fm_row_weights> w(new fm_row_weights());
+    w->owner = ctx;
+    w->device = ctx->cfg.device;
+    w->C = C;
+    w->W = W;
+    w->weight.ensure(sizeof(uint32_t) * (size_t)C);
+    w->cdf.ensure(sizeof(int64_t) * ((size_t)C + 1));
+    FM_HIP_CHECK(hipMemcpy(w->weight.p, weight, sizeof(uint32_t) * (size_t)C, hipMemcpyHostToDevice));
+    {
+      // cdf = the weights' exclusive scan, cdf[C] = W: the pair batches' three-phase scan, its scratch the call's own
+      DevBuf ctot, coff, total;
+      const size_t nchunks = (size_t)pair_scan_chunks(C);
+      ctot.ensure(sizeof(int64_t) * nchunks);
+      coff.ensure(sizeof(int64_t) * nchunks);
+      total.ensure(sizeof(int64_t));
+      hipStream_t st = ctx->stream;
+      hipEvent_t e0 = ctx->prof_begin(st);
+      launch_len_scan(w->weight.as<uint32_t>(), C, w->cdf.as<int64_t>(), ctot.as<int64_t>(), coff.as<int64_t>(),
+                      total.as<int64_t>(), st);
+      ctx->prof_end("weights_cdf", e0, st);
+      FM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    *out = w.release();
+    return FM_OK;
+  });
+}
+
+void fm_row_weights_destroy(fm_row_weights* w) {
+  if (!w) return;
+  try {
+    delete w;
+  } catch (...) {
+  }
+}
+
+int64_t fm_row_weights_candidates(const fm_row_weights* w) { return w ? w->C : -1; }
+int64_t fm_row_weights_total(const fm_row_weights* w) { return w ? (int64_t)w->W : -1; }
+
+int fm_row_weights_bind(fm_ctx* ctx, fm_row_weights* w, const fm_lists* excl) {
+  return guarded(ctx, [&]() -> int {
+    FM_REQUIRE(w != nullptr && w->owner == ctx, "weights: the weights belong to another context");
+    if (!excl) {  // nothing excluded: E_w = W for every context, no keys
+      w->bound = nullptr;
+      w->bound_serial = 0;
+      w->keys.release();
+      w->ew.release();
+      w->host_ew.clear();
+      return FM_OK;
+    }
+    FM_REQUIRE(excl->owner == ctx, "excl: the lists belong to another context");
+    FM_REQUIRE(excl->C == w->C, "excl: lists over " + std::to_string(excl->C) + " candidate rows for weights of " +
+                                    std::to_string(w->C) + " rows");
+    if (w->bound == excl && w->bound_serial == excl->serial) return FM_OK;  // bound already
+    const int64_t U = excl->U;
+    w->bound = nullptr;
+    w->bound_serial = 0;
+    std::vector<int32_t> long_ctx;  // the contexts the block-per-list kernel takes
+    for (int64_t u = 0; u < U; ++u)
+      if (excl->host_ptr[u + 1] - excl->host_ptr[u] > kBindShort) long_ctx.push_back((int32_t)u);
+    w->keys.ensure(sizeof(uint2) * (size_t)excl->total());
+    w->ew.ensure(sizeof(uint32_t) * (size_t)U);
+    w->host_ew.assign((size_t)U, 0);
+    if (U > 0) {
+      DevBuf dlong;  // the call's own, freed behind the wait below
+      if (!long_ctx.empty()) {
+        dlong.ensure(sizeof(int32_t) * long_ctx.size());
+        FM_HIP_CHECK(hipMemcpy(dlong.p, long_ctx.data(), sizeof(int32_t) * long_ctx.size(), hipMemcpyHostToDevice));
+      }
+      hipStream_t st = ctx->stream;
+      hipEvent_t e0 = ctx->prof_begin(st);
+      launch_weights_bind(w->weight.as<uint32_t>(), w->cdf.as<int64_t>(), w->W, excl->ptr.as<int64_t>(),
+                          excl->rows.as<int32_t>(), U, dlong.as<int32_t>(), (int64_t)long_ctx.size(), w->keys.as<uint2>(),
+                          w->ew.as<uint32_t>(), st);
+      ctx->prof_end("weights_bind", e0, st);
+      // the one read-back: E_w per context, for the sampling calls' "no eligible candidate row" rule
+      FM_HIP_CHECK(hipMemcpyAsync(w->host_ew.data(), w->ew.p, sizeof(uint32_t) * (size_t)U, hipMemcpyDeviceToHost, st));
+      FM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    w->bound = excl;
+    w->bound_serial = excl->serial;
+    return FM_OK;
+  });
+}
+
+int fm_batch_sample_pairs_weighted(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates, const int32_t* pos_ctx,
+                                   const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, int32_t n_draw, int32_t refresh,
+                                   const fm_row_weights* weights, const fm_lists* excl, double pos_label, double neg_label,
+                                   uint64_t seed, fm_batch** out, int32_t* sampled) {
+  if (!weights) return guarded(ctx, [&]() -> int { FM_REQUIRE(false, "fm_batch_sample_pairs_weighted: null weights"); return FM_OK; });
+  return sample_pairs_call(ctx, contexts, candidates, pos_ctx, pos_cand, n_pos, n_neg, nullptr, nullptr, true, excl, pos_label,
+                           neg_label, seed, out, sampled, "fm_batch_sample_pairs_weighted", true, n_draw, refresh, weights);
 }
 
 int fm_init_from_batch(fm_ctx* ctx, fm_batch* b, int64_t* n_present) {

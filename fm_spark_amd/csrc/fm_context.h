@@ -180,12 +180,37 @@ struct fm_lists {
   int64_t longest = 0;            // the longest list
   DevBuf ptr, rows;               // int64 [U + 1] offsets, int32 [ptr[U]] candidate rows
   std::vector<int64_t> host_ptr;  // the offsets again: sizes and the per-context lengths without a device read
+  uint64_t serial = 0;            // unique per object of the process: what an fm_row_weights binding remembers
   int64_t total() const { return host_ptr.empty() ? 0 : host_ptr.back(); }
   ~fm_lists() {
     // (each DevBuf frees itself; released here only for the order: on the lists' device)
     (void)hipSetDevice(device);
     rows.release();
     ptr.release();
+  }
+};
+
+// Candidate-row weights resident on the device (fm_row_weights_create) and their binding to one fm_lists
+// (fm_row_weights_bind; fm_weights.hip).  weight and cdf are read-only after construction; the binding is
+// replaced by the next bind.
+struct fm_row_weights {
+  fm_ctx* owner = nullptr;
+  int device = 0;
+  int64_t C = 0;
+  uint64_t W = 0;        // the weights summed, in [1, 2^32)
+  DevBuf weight, cdf;    // uint32 [C], int64 [C + 1]: cdf[c] = the weights before row c, cdf[C] = W
+  // the binding: per list entry {key = cdf[e_t] - X_t, X_{t + 1}} (uint2 [lists' total]) and E_w per context
+  // (uint32 [U]), of the fm_lists with this serial; bound_serial 0: none
+  uint64_t bound_serial = 0;
+  const fm_lists* bound = nullptr;
+  DevBuf keys, ew;
+  std::vector<uint32_t> host_ew;  // E_w again: the "no eligible candidate row" rule without a device read
+  ~fm_row_weights() {
+    (void)hipSetDevice(device);
+    ew.release();
+    keys.release();
+    cdf.release();
+    weight.release();
   }
 };
 

@@ -289,6 +289,63 @@ __device__ __forceinline__ float gauss_draw(uint64_t seed, int64_t id, int f, do
   return (float)(g * sd);
 }
 
+// inclusive scan of v over the block's threads (NW waves; ws: NW int64 of LDS); *total = the block's sum
+template <int NW>
+__device__ __forceinline__ int64_t block_scan_incl(int64_t v, int64_t* ws, int64_t* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int64_t t = __shfl_up(v, o);
+    if (lane >= o) v += t;
+  }
+  if (lane == 63) ws[wave] = v;
+  __syncthreads();
+  int64_t wpre = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    wpre += w < wave ? ws[w] : 0;
+    tot += ws[w];
+  }
+  __syncthreads();  // ws is free for the next call
+  *total = tot;
+  return v + wpre;
+}
+
+// ---- the weighted pair draw (fm_batch_sample_pairs_weighted; the contract in include/fm_hip.h).  Both halves
+// are used by k_pair_sample_weighted (fm_weights.hip, which finds the cdf search's bracket in its LDS pivot
+// table first) and by the weighted k_pair_sample_hard (fm_pairs.hip, the whole cdf as bracket).
+// r of draw (i, j) for a context of eligible weight E, then t* by binary search over the context's bound
+// entries kx[x0, x0 + L) = {key_t, X_{t + 1}} (keys non-decreasing): the search's last probe that went
+// right is entry t* - 1, so its second word is X_{t*} and the target v = r + X_{t*} costs no further load.
+__device__ __forceinline__ uint64_t weighted_target(uint64_t seed, int64_t i, int64_t j, const uint2* __restrict__ kx,
+                                                    int64_t x0, int64_t L, uint64_t E) {
+  const uint64_t h = splitmix64(seed ^ splitmix64(((uint64_t)i << 20) | (uint64_t)j));
+  const uint64_t r = ((h >> 32) * E) >> 32;
+  uint64_t xacc = 0;
+  int64_t lo = 0, hi = L;  // the first t with key_t > r
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) / 2;
+    const uint2 e = kx[x0 + mid];
+    if ((uint64_t)e.x <= r) {
+      lo = mid + 1;
+      xacc = e.y;
+    } else {
+      hi = mid;
+    }
+  }
+  return r + xacc;
+}
+// the row c with cdf[c] <= v < cdf[c + 1], given a bracket lo <= c + 1 <= hi with cdf[lo - 1] <= v < cdf[hi]:
+// the first p in [lo, hi] with cdf[p] > v, less one.  Reads cdf[lo .. hi - 1] at most.
+__device__ __forceinline__ int64_t weighted_row(const int64_t* __restrict__ cdf, uint64_t v, int64_t lo, int64_t hi) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) / 2;
+    if ((uint64_t)cdf[mid] <= v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo - 1;
+}
+
 // ---- a (context, candidate) pair's score as an ordered key: what the ranking kernels (fm_rank.hip) and the
 // score-aware pair sampler (fm_pairs.hip) both sort.
 constexpr uint64_t kWorstKey = 0;  // below every finite score's key

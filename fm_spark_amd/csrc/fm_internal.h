@@ -572,6 +572,38 @@ void launch_pair_sample_hard(const int32_t* pos_ctx, const int32_t* pos_cand, in
                              uint32_t* len, int64_t* row_ptr, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total,
                              hipStream_t st);
 
+// ---------------------------------------------------------------- weighted negatives (fm_weights.hip)
+// What the weighted draw reads on the device: cdf [C + 1] (cdf[C] = W) and, bound to the call's exclude lists,
+// kx [the lists' total] = {key_t = cdf[e_t] - X_t, X_{t + 1}} per list entry and ew [U] = E_w per context;
+// kx and ew null without lists (E_w = W for every context).
+struct WeightedDraw {
+  const int64_t* cdf;
+  const uint2* kx;
+  const uint32_t* ew;
+  uint64_t W;
+};
+constexpr int kBindShort = 64;    // lists of at most this many rows are scanned by a team of a wave's lanes ...
+constexpr int kBindTile = 1024;   // ... longer ones by a block each, in tiles of this many rows
+// fm_row_weights_bind's device side: the segmented exclusive scan of weight[e_t] over every context's list
+// into kx and ew (above).  long_ctx [n_long] (device): the contexts whose lists are longer than kBindShort,
+// ascending, found by the host from its copy of the offsets.  No atomics, one writer per slot.
+void launch_weights_bind(const uint32_t* weight, const int64_t* cdf, uint64_t W, const int64_t* excl_ptr,
+                         const int32_t* excl_rows, int64_t U, const int32_t* long_ctx, int64_t n_long, uint2* kx,
+                         uint32_t* ew, hipStream_t st);
+// launch_pair_sample with the weighted draw (excl_ptr: the bound lists' offsets, null with d.kx)
+void launch_pair_sample_weighted(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
+                                 const int64_t* excl_ptr, const WeightedDraw& d, double pos_label, double neg_label,
+                                 uint64_t seed, const BatchDev& contexts, const BatchDev& candidates, int32_t* pair_ctx,
+                                 int32_t* pair_cand, double* label, uint32_t* len, int64_t* row_ptr, int64_t* chunk_tot,
+                                 int64_t* chunk_off, int64_t* total, hipStream_t st);
+// launch_pair_sample_hard with the weighted draw: the same kernel, its draw the weighted one
+void launch_pair_sample_hard_weighted(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
+                                      int32_t n_draw, const int64_t* excl_ptr, const WeightedDraw& d, double pos_label,
+                                      double neg_label, uint64_t seed, const BatchDev& contexts, const BatchDev& candidates,
+                                      const RankSide& su, const RankSide& sc, int kp, double w0, int32_t* pair_ctx,
+                                      int32_t* pair_cand, double* label, uint32_t* len, int64_t* row_ptr,
+                                      int64_t* chunk_tot, int64_t* chunk_off, int64_t* total, hipStream_t st);
+
 // ---------------------------------------------------------------- resident row lists (fm_lists.hip)
 // fm_lists_from_pairs' device side, in two halves around the one read-back (ptr: it sizes rows).  Both take
 // the n pairs sorted by (context, candidate) -- sctx / scand, device, as two stable radix sorts leave them.

@@ -4,7 +4,8 @@
 //   k_pair_sample  the sampled call's pairs: each positive, then its n_neg drawn candidate rows, with
 //                  every output row's label and length
 //   k_pair_sample_hard  fm_batch_sample_pairs_hard's pairs: n_draw draws per positive scored against a
-//                  summary snapshot, the best n_neg kept (a wave per positive; its comment below)
+//                  summary snapshot, the best n_neg kept (a wave per positive; its comment below).  The draw
+//                  is its parameter: the uniform one, or fm_batch_sample_pairs_weighted's (fm_weights.hip)
 //   k_pair_chunk_sum / k_pair_scan_chunks / k_pair_scan_rows
 //                  the exclusive scan of those lengths into the result's row_ptr, in the three phases
 //                  of fm_update.hip's split: chunk totals, a one-block scan of the totals (in rounds),
@@ -153,6 +154,26 @@ __device__ __forceinline__ int64_t pair_draw(uint64_t seed, int64_t i, int64_t j
   return d + lo;
 }
 
+// The draw as k_pair_sample_hard's parameter: draw j of positive i with context u, whose list is entries
+// [x0, x0 + L) of the call's lists.  UniformPairDraw is pair_draw; WeightedPairDraw the weighted contract's
+// (fm_device.h: two binary searches, the second over the whole cdf -- a wave per positive has no block-wide
+// pivot table, and its draws are a small part of a selection that scores every one of them).
+struct UniformPairDraw {
+  const int32_t* excl_rows;
+  int64_t C;
+  __device__ __forceinline__ int64_t operator()(uint64_t seed, int64_t i, int64_t j, int64_t u, int64_t x0, int64_t L) const {
+    return pair_draw(seed, i, j, excl_rows, x0, L, C);
+  }
+};
+struct WeightedPairDraw {
+  WeightedDraw d;
+  int64_t C;
+  __device__ __forceinline__ int64_t operator()(uint64_t seed, int64_t i, int64_t j, int64_t u, int64_t x0, int64_t L) const {
+    const uint64_t v = weighted_target(seed, i, j, d.kx, x0, L, d.ew ? (uint64_t)d.ew[u] : d.W);
+    return weighted_row(d.cdf, v, 1, C);
+  }
+};
+
 // the summary snapshot and the two sources' row offsets, as the kernel reads them
 struct HardSources {
   const double* sum_u;
@@ -165,11 +186,11 @@ struct HardSources {
   const int64_t* c_rp;
 };
 
-// kWide: n_draw > 64 (a kernel each: together they spill SGPRs)
-template <int kWaves, bool kWide>
+// kWide: n_draw > 64 (a kernel each: together they spill SGPRs); Draw: UniformPairDraw or WeightedPairDraw
+template <int kWaves, bool kWide, class Draw>
 __global__ __launch_bounds__(kWaves * 64) void k_pair_sample_hard(
     const int32_t* __restrict__ pos_ctx, const int32_t* __restrict__ pos_cand, int64_t n_pos, int32_t n_neg, int32_t n_draw,
-    int32_t P, const int64_t* __restrict__ excl_ptr, const int32_t* __restrict__ excl_rows, int64_t C, double pos_label,
+    int32_t P, const int64_t* __restrict__ excl_ptr, Draw draw, double pos_label,
     double neg_label, uint64_t seed, HardSources s, int kp, double w0, int32_t* __restrict__ pair_ctx,
     int32_t* __restrict__ pair_cand, double* __restrict__ lab, uint32_t* __restrict__ len) {
   extern __shared__ __align__(16) unsigned char hard_lds[];
@@ -214,7 +235,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_pair_sample_hard(
       uint64_t k = kWorstKey;
       int64_t c = 0;
       if (lane < n_draw) {
-        c = pair_draw(seed, i, lane, excl_rows, x0, L, C);
+        c = draw(seed, i, lane, u, x0, L);
         k = score_row(su, x, s.sum_c, s.bias_c, s.cnt_c, c, kp, w0);
       }
       int rank = 0;  // the draws that come before this lane's
@@ -226,7 +247,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_pair_sample_hard(
       uint64_t k = kWorstKey;
       uint32_t c = 0;
       if (j < n_draw) {
-        c = (uint32_t)pair_draw(seed, i, j, excl_rows, x0, L, C);
+        c = (uint32_t)draw(seed, i, j, u, x0, L);
         k = score_row(su, x, s.sum_c, s.bias_c, s.cnt_c, c, kp, w0);
       }
       key[j] = k;
@@ -275,27 +296,7 @@ static_assert(kPairScanNT <= 1024 && kPairScanPer >= 1, "one block scans a round
 // a round takes kPairScanNT * kPairScanPer = 1024 chunks = 262 144 rows: the step's batch in one round
 static_assert((int64_t)kPairScanNT * kPairScanPer * kPairChunk == 262144, "rows per round of the chunk-total scan (tests/test_gpu_pairs.py)");
 
-// inclusive scan of v over the block's threads (NW waves; ws: NW int64 of LDS); *total = the block's sum
-template <int NW>
-__device__ __forceinline__ int64_t block_scan_incl(int64_t v, int64_t* ws, int64_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  if (lane == 63) ws[wave] = v;
-  __syncthreads();
-  int64_t wpre = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    wpre += w < wave ? ws[w] : 0;
-    tot += ws[w];
-  }
-  __syncthreads();  // ws is free for the next call
-  *total = tot;
-  return v + wpre;
-}
+// (block_scan_incl: fm_device.h, shared with fm_weights.hip's tile scan)
 
 // phase 1: tot[c] = the lengths of chunk c summed
 __global__ __launch_bounds__(kBlock) void k_pair_chunk_sum(const uint32_t* __restrict__ len, int64_t B, int64_t nchunks,
@@ -380,12 +381,13 @@ void launch_pair_sample(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t
   launch_len_scan(len, B, row_ptr, chunk_tot, chunk_off, total, st);
 }
 
-void launch_pair_sample_hard(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, int32_t n_draw,
-                             const int64_t* excl_ptr, const int32_t* excl_rows, double pos_label, double neg_label,
-                             uint64_t seed, const BatchDev& contexts, const BatchDev& candidates, const RankSide& su,
-                             const RankSide& sc, int kp, double w0, int32_t* pair_ctx, int32_t* pair_cand, double* label,
-                             uint32_t* len, int64_t* row_ptr, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total,
-                             hipStream_t st) {
+// both draws' launch: the kernel by n_draw, then the lengths' scan
+template <class Draw>
+static void launch_hard(const Draw& draw, const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
+                        int32_t n_draw, const int64_t* excl_ptr, double pos_label, double neg_label, uint64_t seed,
+                        const BatchDev& contexts, const BatchDev& candidates, const RankSide& su, const RankSide& sc, int kp,
+                        double w0, int32_t* pair_ctx, int32_t* pair_cand, double* label, uint32_t* len, int64_t* row_ptr,
+                        int64_t* chunk_tot, int64_t* chunk_off, int64_t* total, hipStream_t st) {
   const int64_t B = n_pos * ((int64_t)n_neg + 1);
   if (B <= 0) {
     launch_len_scan(len, 0, row_ptr, chunk_tot, chunk_off, total, st);
@@ -399,13 +401,35 @@ void launch_pair_sample_hard(const int32_t* pos_ctx, const int32_t* pos_cand, in
   const auto launch = [&](auto kern, int waves) {
     const int64_t blocks = (n_pos + waves - 1) / waves;
     hipLaunchKernelGGL(kern, dim3(grid_for(blocks * waves * 64, waves * 64, 256 * 8)), dim3(waves * 64), slice * waves, st,
-                       pos_ctx, pos_cand, n_pos, n_neg, n_draw, P, excl_ptr, excl_rows, candidates.n_rows, pos_label, neg_label,
+                       pos_ctx, pos_cand, n_pos, n_neg, n_draw, P, excl_ptr, draw, pos_label, neg_label,
                        seed, s, kp, w0, pair_ctx, pair_cand, label, len);
   };
-  if (n_draw <= 64) launch(k_pair_sample_hard<kHardWaves, false>, kHardWaves);
-  else if (P <= 512) launch(k_pair_sample_hard<kHardWaves, true>, kHardWaves);
-  else launch(k_pair_sample_hard<kHardWavesWide, true>, kHardWavesWide);
+  if (n_draw <= 64) launch(k_pair_sample_hard<kHardWaves, false, Draw>, kHardWaves);
+  else if (P <= 512) launch(k_pair_sample_hard<kHardWaves, true, Draw>, kHardWaves);
+  else launch(k_pair_sample_hard<kHardWavesWide, true, Draw>, kHardWavesWide);
   launch_len_scan(len, B, row_ptr, chunk_tot, chunk_off, total, st);
+}
+
+void launch_pair_sample_hard(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg, int32_t n_draw,
+                             const int64_t* excl_ptr, const int32_t* excl_rows, double pos_label, double neg_label,
+                             uint64_t seed, const BatchDev& contexts, const BatchDev& candidates, const RankSide& su,
+                             const RankSide& sc, int kp, double w0, int32_t* pair_ctx, int32_t* pair_cand, double* label,
+                             uint32_t* len, int64_t* row_ptr, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total,
+                             hipStream_t st) {
+  launch_hard(UniformPairDraw{excl_rows, candidates.n_rows}, pos_ctx, pos_cand, n_pos, n_neg, n_draw, excl_ptr, pos_label,
+              neg_label, seed, contexts, candidates, su, sc, kp, w0, pair_ctx, pair_cand, label, len, row_ptr, chunk_tot,
+              chunk_off, total, st);
+}
+
+void launch_pair_sample_hard_weighted(const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
+                                      int32_t n_draw, const int64_t* excl_ptr, const WeightedDraw& d, double pos_label,
+                                      double neg_label, uint64_t seed, const BatchDev& contexts, const BatchDev& candidates,
+                                      const RankSide& su, const RankSide& sc, int kp, double w0, int32_t* pair_ctx,
+                                      int32_t* pair_cand, double* label, uint32_t* len, int64_t* row_ptr,
+                                      int64_t* chunk_tot, int64_t* chunk_off, int64_t* total, hipStream_t st) {
+  launch_hard(WeightedPairDraw{d, candidates.n_rows}, pos_ctx, pos_cand, n_pos, n_neg, n_draw, excl_ptr, pos_label,
+              neg_label, seed, contexts, candidates, su, sc, kp, w0, pair_ctx, pair_cand, label, len, row_ptr, chunk_tot,
+              chunk_off, total, st);
 }
 
 void launch_len_scan(const uint32_t* len, int64_t B, int64_t* off, int64_t* chunk_tot, int64_t* chunk_off, int64_t* total,

@@ -221,6 +221,39 @@ class RowLists:
             pass
 
 
+class RowWeights:
+    """Candidate-row weights resident in HBM (fm_row_weights_create): the base distribution of
+    batch_sample_pairs(weights=).  ``bind`` ties them to one RowLists of exclude lists at a time
+    (fm_row_weights_bind: the per-entry search keys and every context's eligible weight, built on the
+    device once); batch_sample_pairs binds on first use, and a loop that changes its lists binds again."""
+
+    def __init__(self, ctx: "FMContext", handle):
+        self._lib = N.load()
+        self.ctx = ctx
+        self.handle = handle
+        self.n_candidates = int(self._lib.fm_row_weights_candidates(handle))
+        self.total = int(self._lib.fm_row_weights_total(handle))
+        self.bound = None  # the RowLists bound (kept alive with the binding); None: no binding
+
+    def bind(self, lists: "RowLists | None"):
+        N.check(self._lib.fm_row_weights_bind(self.ctx.handle, self.handle, lists.handle if lists is not None else None),
+                "fm_row_weights_bind")
+        self.bound = lists
+        return self
+
+    def close(self):
+        if self.handle:
+            self._lib.fm_row_weights_destroy(self.handle)
+            self.handle = None
+            self.bound = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def comm_unique_id() -> bytes:
     """RCCL unique id (128 bytes) that process 0 of a multi-process job hands to the others
     (fm_comm_unique_id)."""
@@ -508,6 +541,19 @@ class FMContext:
                                               N.ptr(pd, C.c_int32), len(pc), C.byref(h)), "fm_lists_from_pairs")
         return RowLists(self, h)
 
+    def row_weights(self, weights) -> RowWeights:
+        """One non-negative integer weight per candidate row (their sum in [1, 2^32)), made resident with its
+        cumulative sums (fm_row_weights_create): batch_sample_pairs(weights=) draws by them."""
+        w = np.asarray(weights)
+        if w.ndim != 1 or (w.size and w.dtype.kind not in "iu"):
+            raise ValueError("weights must be a flat sequence of integers")
+        if w.size and (int(w.min()) < 0 or int(w.max()) >= 2**32):
+            raise ValueError("a weight must be in [0, 2^32)")
+        w = np.ascontiguousarray(w, dtype=np.uint32)
+        h = C.c_void_p()
+        N.check(self._lib.fm_row_weights_create(self.handle, len(w), N.ptr(w, C.c_uint32), C.byref(h)), "fm_row_weights_create")
+        return RowWeights(self, h)
+
     def batch_from_pairs(self, contexts: DeviceBatch, candidates: DeviceBatch, pair_ctx, pair_cand, labels,
                          into: DeviceBatch | None = None) -> DeviceBatch:
         """The mini-batch whose row i is row pair_ctx[i] of `contexts` followed by row pair_cand[i] of
@@ -528,7 +574,7 @@ class FMContext:
     def batch_sample_pairs(self, contexts: DeviceBatch, candidates: DeviceBatch, pos_ctx, pos_cand, n_neg: int, *,
                            exclude=None, pos_label: float = 1.0, neg_label: float = 0.0, seed: int = 0,
                            into: DeviceBatch | None = None, want_sampled: bool = False, n_draw: int | None = None,
-                           refresh: bool = True):
+                           refresh: bool = True, weights: RowWeights | None = None):
         """The implicit-feedback mini-batch of the positives (pos_ctx[i], pos_cand[i]), each followed by
         n_neg negatives drawn on the device uniformly over the candidate rows its context's ``exclude``
         list does not hold (fm_batch_sample_pairs; the lists as rank(exclude=) takes them).  Returns the
@@ -538,7 +584,21 @@ class FMContext:
         drawn per positive and the n_neg the model scores highest are kept, in draw order.  ``refresh``
         recomputes the scores' snapshot behind every queued step; refresh=False scores against the
         snapshot of the last refreshing call (same contexts and candidates: only their row counts are
-        checked) and does not wait for the step in flight.  None: the uniform call."""
+        checked) and does not wait for the step in flight.  None: the uniform call.
+
+        ``weights`` (a RowWeights of this context, row_weights): the negatives follow the weights instead --
+        a row is drawn with probability proportional to its weight among the context's eligible rows
+        (fm_batch_sample_pairs_weighted); n_draw then selects among weighted draws.  Host exclude lists are
+        made resident and bound for the call; a RowLists is bound on the weights' first use, and must
+        afterwards be the one bound (RowWeights.bind changes it)."""
+        if weights is not None:
+            if exclude is not None and not isinstance(exclude, RowLists):
+                weights.bind(self._row_lists(normalize_row_lists(exclude, contexts.n_rows), candidates.n_rows))
+                exclude = weights.bound
+            elif exclude is not None and weights.bound is None:
+                weights.bind(exclude)
+            return self._sample_pairs(contexts, candidates, pos_ctx, pos_cand, n_neg, exclude, pos_label, neg_label, seed,
+                                      into, want_sampled, n_neg if n_draw is None else n_draw, refresh, weights)
         if exclude is None:
             ex = (None, None)
         elif isinstance(exclude, RowLists):
@@ -549,10 +609,11 @@ class FMContext:
                                   want_sampled, n_draw, refresh)
 
     def _sample_pairs(self, contexts, candidates, pos_ctx, pos_cand, n_neg, ex, pos_label, neg_label, seed, into,
-                      want_sampled, n_draw=None, refresh=True):
+                      want_sampled, n_draw=None, refresh=True, weights=None):
         """batch_sample_pairs with the exclude lists already normalised: ex = (ptr, rows), (None, None) or a
         RowLists (fm_batch_sample_pairs_lists) -- a loop normalises its lists once, or makes them resident.
-        n_draw not None: the _hard symbols, with n_draw and refresh behind n_neg."""
+        n_draw not None: the _hard symbols, with n_draw and refresh behind n_neg.  weights (a RowWeights):
+        fm_batch_sample_pairs_weighted, ex a RowLists (bound to the weights) or None, n_draw given."""
         pc = np.ascontiguousarray(pos_ctx, dtype=np.int32)
         pd = np.ascontiguousarray(pos_cand, dtype=np.int32)
         if not (pc.ndim == pd.ndim == 1 and len(pc) == len(pd)):
@@ -565,6 +626,11 @@ class FMContext:
         tail = (float(pos_label), float(neg_label), int(seed) & (2**64 - 1), C.byref(h),
                 N.ptr(sampled, C.c_int32) if want_sampled else None)
         name = "fm_batch_sample_pairs"
+        if weights is not None:
+            N.check(self._lib.fm_batch_sample_pairs_weighted(*head, int(n_draw), 1 if refresh else 0, weights.handle,
+                                                             ex.handle if ex is not None else None, *tail), name + "_weighted")
+            self._pair_batch(b, h, contexts, candidates)
+            return (b, sampled[: len(pc) * n_neg].reshape(len(pc), n_neg)) if want_sampled else b
         if n_draw is not None:
             name += "_hard"
             head += (int(n_draw), 1 if refresh else 0)

@@ -123,6 +123,21 @@ def _sigmoid(z):
     return np.where(z >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
 
 
+def popularity_weights(counts, power: float = 0.75) -> np.ndarray:
+    """The integer weights of negativeSampling "popularity" for candidate rows interacted counts[c] times:
+        raw[c]    = float64(counts[c] + 1) ** power                      add-one smoothing
+        S         = min(2**20, (2**32 - 1) // len(counts))               the heaviest row's weight
+        weight[c] = max(1, floor(S * raw[c] / raw.max()))                uint32
+    Every row keeps a weight >= 1, so a context the uniform sampler accepts is accepted, and the weights
+    sum to at most len(counts) * S < 2^32.  A function of the counts and the power alone."""
+    counts = np.asarray(counts, dtype=np.int64)
+    if counts.size == 0:
+        return np.zeros(0, np.uint32)
+    raw = np.power((counts + 1).astype(np.float64), float(power))
+    S = min(2**20, (2**32 - 1) // counts.size)
+    return np.maximum(1, np.floor(S * raw / raw.max())).astype(np.uint32)
+
+
 def _check_schema(df: DataFrame, features_col: str, label_col: str | None):
     """validateAndTransformSchema (FactorizationMachines.scala:33-37): features must be
     vectors (VectorUDT), the label a double."""
@@ -411,6 +426,10 @@ class FactorizationMachinesSGD:
         # iterations between two refreshes of the scores' snapshot
         "negativeCandidates": None,
         "negativeRefreshEvery": 1,
+        # the negatives' base distribution: "uniform", or "popularity" (fm_batch_sample_pairs_weighted) by
+        # popularity_weights of the interactions' candidate counts at this power
+        "negativeSampling": "uniform",
+        "negativePopularityPower": 0.75,
         # not in the reference (its loss is the squared error, SGD.scala:134-146): the step's objective
         "loss": "squared",
         # not in the reference (one rate stepSize / sqrt(t) for every row): the row update and, for "adagrad",
@@ -530,6 +549,20 @@ class FactorizationMachinesSGD:
             raise ValueError("negativeRefreshEvery must be an integer >= 1")
         return self._set("negativeRefreshEvery", int(r))
 
+    def setNegativeSampling(self, how: str):
+        """The distribution fitInteractions draws negatives from: "uniform" (default: every eligible row alike,
+        today's calls and bits) or "popularity" -- proportional to popularity_weights of the rows' interaction
+        counts (word2vec's smoothed unigram distribution), on the device (fm_batch_sample_pairs_weighted)."""
+        if how not in ("uniform", "popularity"):
+            raise ValueError('negativeSampling must be "uniform" or "popularity"')
+        return self._set("negativeSampling", how)
+
+    def setNegativePopularityPower(self, power: float):
+        """The exponent of negativeSampling "popularity" (default 0.75; 0: uniform weights, 1: raw counts)."""
+        if isinstance(power, bool) or not isinstance(power, (int, float, np.integer, np.floating)) or not 0.0 <= power <= 4.0:
+            raise ValueError("negativePopularityPower must be a number in [0, 4]")
+        return self._set("negativePopularityPower", float(power))
+
     def setLoss(self, loss: str):
         """The objective each step descends (fm_config.loss): "squared" (default, the reference's),
         "logistic" -- log loss of sigma(score) against labels in [0, 1], for click / binary labels and for
@@ -586,6 +619,8 @@ class FactorizationMachinesSGD:
     def getNegativesPerPositive(self): return self._params["negativesPerPositive"]
     def getNegativeCandidates(self): return self._params["negativeCandidates"]
     def getNegativeRefreshEvery(self): return self._params["negativeRefreshEvery"]
+    def getNegativeSampling(self): return self._params["negativeSampling"]
+    def getNegativePopularityPower(self): return self._params["negativePopularityPower"]
     def getDimFactorization(self): return self._params["dimFactorization"]
     def getMaxIter(self): return self._params["maxIter"]
     def getMiniBatchFraction(self): return self._params["miniBatchFraction"]
@@ -767,6 +802,10 @@ class FactorizationMachinesSGD:
         With negativeCandidates = d set, iteration t draws d rows per positive with the same seed and keeps
         the negativesPerPositive the model scores highest (fm_batch_sample_pairs_hard_lists, n_draw = d),
         refreshing the scores' snapshot when (t - 1) % negativeRefreshEvery == 0; the loop is otherwise the same.
+        With negativeSampling "popularity" the draws follow popularity_weights(bincount of the interactions'
+        candidate column, negativePopularityPower) among each context's eligible rows instead of being uniform
+        (fm_batch_sample_pairs_weighted; the weights are counted once, resident, and bound to the exclude
+        lists); negativeCandidates then selects among those draws.
         ``initial_tables`` = (ids, w, V) replaces the seeded draw over every id of either frame.  A
         multi-GPU estimator (setParallel) and a set validationData raise ValueError: not built yet."""
         p = self._params
@@ -813,6 +852,13 @@ class FactorizationMachinesSGD:
             ex = ctx._row_lists(exclude, n_cand)
         else:
             ex = ctx.row_lists_from_pairs(pos_ctx, pos_cand, n_ctx, n_cand)
+        # "popularity": the candidate rows' weights from the interactions, counted once, resident and bound to ex
+        weights = None
+        if p["negativeSampling"] == "popularity" and n_cand:
+            counts = np.bincount(pos_cand, minlength=n_cand)
+            weights = ctx.row_weights(popularity_weights(counts, p["negativePopularityPower"])).bind(ex)
+            if n_draw is None:
+                n_draw = p["negativesPerPositive"]  # every draw kept, nothing scored
         if initial_tables is not None:
             ctx.load_tables(*initial_tables)
         else:
@@ -829,7 +875,7 @@ class FactorizationMachinesSGD:
         def sample(t):
             take = perm[((t - 1) * m + np.arange(m)) % n]
             bufs[t % 2] = ctx._sample_pairs(bu, bc, pos_ctx[take], pos_cand[take], n_neg, ex, 1.0, 0.0, seed0 ^ t,
-                                            bufs[t % 2], False, n_draw, (t - 1) % refresh_every == 0)
+                                            bufs[t % 2], False, n_draw, (t - 1) % refresh_every == 0, weights)
             bufs[t % 2].prepare()
 
         e0 = ctx.epoch
@@ -842,7 +888,7 @@ class FactorizationMachinesSGD:
                 sample(t + 1)  # drawn, gathered and sorted while step t runs (the batch step t - 1 read)
         ctx.sync()
         _log_losses(ctx, e0, work, n_iter, n_iter)
-        for b in (*bufs, bu, bc, ex):
+        for b in (*bufs, bu, bc, weights, ex):
             if b is not None:
                 b.close()
         model = FactorizationMachinesModel(self.uid, k, 0.0, ctx=ctx)

@@ -805,6 +805,61 @@ int fm_batch_sample_pairs_hard_lists(fm_ctx* ctx, const fm_batch* contexts, cons
                                      const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
                                      int32_t n_draw, int32_t refresh, const fm_lists* excl, double pos_label,
                                      double neg_label, uint64_t seed, fm_batch** out, int32_t* sampled);
+/* ---- Popularity-weighted negatives: the sampled pair batch with a weighted base distribution.
+ * Every candidate row c in [0, C) has a weight[c] (uint32; 0: never drawn), W = sum of the weights in
+ * [1, 2^32), cdf[c] = the weights before row c, cdf[C] = W.  Context u's exclude list e_0 < ... < e_{L-1}
+ * (an fm_lists, under its rules) has X_t = the weights of e_0 .. e_{t-1} summed and the eligible weight
+ * E_w(u) = W - X_L.  Draw (i, j) of positive i with context u -- integers only, exact, part of the contract:
+ *   h    = splitmix64(seed ^ splitmix64(((uint64)i << 20) | j))     fm_batch_sample_pairs' hash
+ *   r    = ((h >> 32) * E_w(u)) >> 32                               64-bit arithmetic
+ *   t*   = #{ t : cdf[e_t] - X_t <= r }                             the keys cdf[e_t] - X_t do not decrease in t
+ *   c_ij = the row c with cdf[c] <= r + X_{t*} < cdf[c + 1]
+ * so that
+ *   (a) an excluded row is never drawn, and neither is a row of weight 0;
+ *   (b) with every weight 1 the formulas are fm_batch_sample_pairs' (cdf[c] = c, X_t = t, E_w = C - L): the
+ *       call returns that call's batch bit for bit;
+ *   (c) c_ij is element r of the ascending list of u's eligible rows with each row repeated weight[c] times:
+ *       a row is drawn with probability proportional to its weight among the eligible rows.
+ * The draws depend on (seed, i, j), the weights and the context's list alone.
+ *   fm_row_weights_create : the weights of C candidate rows made resident: uploaded, and cdf [C + 1] built on
+ *           the device by the pair batches' three-phase scan.  Checked on the host first (FM_ERR_ARG, *out as it
+ *           was, nothing allocated that stays): W = 0 ("every weight is 0 (W = 0)": at least one weight must be
+ *           non-zero) and W >= 2^32 (the message gives W).  0 <= C < 2^31.  Synchronous, main stream.  A
+ *           multi-GPU context refuses it.  The object's device memory (weight, cdf, and a binding's two
+ *           arrays) counts in fm_device_bytes_live / fm_device_allocs_live and is freed by _destroy, which
+ *           frees at once (every sampling call has finished reading the object when it returns).
+ *   fm_row_weights_candidates / _total : C and W (-1 for NULL).
+ *   fm_row_weights_bind : binds the weights to one fm_lists (same context, same C: FM_ERR_ARG otherwise), one
+ *           binding at a time, replacing the one before: per list entry the key cdf[e_t] - X_t and X_{t+1}
+ *           (8 bytes), per context E_w(u) (4 bytes) -- a segmented exclusive scan of weight[e_t] over every
+ *           list, on the main stream, no atomics -- and E_w read back to the host, the call's one
+ *           synchronisation.  Binding the lists already bound does nothing.  excl == NULL drops the binding
+ *           (nothing is excluded: no keys, E_w = W).  The lists must outlive the binding's use.
+ *           Profile: "weights_bind".
+ *   fm_batch_sample_pairs_weighted : fm_batch_sample_pairs_lists with the draw above.  excl may be NULL
+ *           (no list, no binding needed); otherwise it must be the fm_lists the weights are bound to
+ *           (FM_ERR_ARG "... not bound to these exclude lists").  Weights of another C than the candidates'
+ *           rows, or of another context: FM_ERR_ARG.  Every context in pos_ctx needs E_w >= 1 (FM_ERR_ARG,
+ *           "... no eligible candidate row"), decided from the binding's host copy of E_w before anything is
+ *           enqueued: the call reads nothing back for it and waits for nothing but its own 8-byte total on
+ *           the copy stream.  0 <= n_neg <= n_draw <= 1024.  n_draw == n_neg keeps every draw and scores
+ *           nothing (refresh is ignored, no snapshot is needed).  n_draw > n_neg hands the n_draw weighted
+ *           draws to fm_batch_sample_pairs_hard's selection -- same keys, same total order, same snapshot
+ *           and refresh rules, same FM_ERR_STATE cases, shard_count == 1 -- and with every weight 1 is
+ *           fm_batch_sample_pairs_hard_lists bit for bit.  Layout, labels, fm_batch_group, sampled, streams,
+ *           the one host wait, refusals that change nothing and leave *out as it was, the multi-GPU refusal:
+ *           as fm_batch_sample_pairs_lists. */
+typedef struct fm_row_weights fm_row_weights;
+int fm_row_weights_create(fm_ctx* ctx, int64_t C, const uint32_t* weight, fm_row_weights** out);
+void fm_row_weights_destroy(fm_row_weights* weights);
+int64_t fm_row_weights_candidates(const fm_row_weights* weights);
+int64_t fm_row_weights_total(const fm_row_weights* weights);
+int fm_row_weights_bind(fm_ctx* ctx, fm_row_weights* weights, const fm_lists* excl);
+int fm_batch_sample_pairs_weighted(fm_ctx* ctx, const fm_batch* contexts, const fm_batch* candidates,
+                                   const int32_t* pos_ctx, const int32_t* pos_cand, int64_t n_pos, int32_t n_neg,
+                                   int32_t n_draw, int32_t refresh, const fm_row_weights* weights,
+                                   const fm_lists* excl, double pos_label, double neg_label, uint64_t seed,
+                                   fm_batch** out, int32_t* sampled);
 /* calcLossGrad (Model.scala:135-234), per active entry e in CSR order:
  * pred[e] = yhat of its row (unclamped), loss[e] = (yhat - y)^2, delta_w[e] = x,
  * delta_v[e*k + f] = vfxiSum_f * x - (v_f * x) * x.  Any output may be NULL.
