@@ -6,7 +6,10 @@ touched coordinate with gradient sum g, gh = g / m:  G' = G + gh^2,  v' = S_lam(
 G <- fp32(G'), as the device stores it.  The model's rows are current (the device thresholds lazily).
 
 Budget of a checked value: RTOL |ref| + ATOL (the suite's) + over the steps that touched it
-eta 2^-22 T / sqrt(G'), T = sum_e |term_e| / m: the fp32 rounding of S, r and yh carried through the step.
+eta 2^-22 T / sqrt(G'), T = sum_e |term_e|' / m: the fp32 rounding of S, r and yh carried through the step, where
+|term_e|' takes a term's parts apart, (|S x| + |v| x^2) |r| and |x - 1| |yh| + |r|: the device forms A = sum S (x r) and
+b = sum x^2 r on their own and subtracts once, so the inputs' rounding does not cancel where S x and v x^2 do
+(tests/test_gpu_optimizer_edges.py met this: an entry alone in its row has a term of exactly 0).
 
 variant "stale" divides by sqrt(G), "sgd" drops the accumulator: what the sensitivity test swaps in.
 """
@@ -45,8 +48,11 @@ class AdaRef:
         gw, gV, Tw, TV = np.zeros_like(self.Gw), np.zeros_like(self.GV), np.zeros_like(self.Gw), np.zeros_like(self.GV)
         np.add.at(gw, ids, term_w)
         np.add.at(gV, ids, term_V)
-        np.add.at(Tw, ids, np.abs(term_w))
-        np.add.at(TV, ids, np.abs(term_V))
+        # the parts of a term taken apart: the device sums S (x r) and x^2 r on their own and forms A - v b once, so
+        # the fp32 rounding of S, r and yh scales with |S x r| + |v x^2 r|, not with their difference (an entry alone
+        # in its row has S x = v x^2: a term of exactly 0 whose parts are not small)
+        np.add.at(Tw, ids, np.abs(x - 1.0) * np.abs(yh[rows]) + np.abs(r[rows]))
+        np.add.at(TV, ids, (np.abs(S[rows] * x[:, None]) + np.abs(model.V[ids]) * (x * x)[:, None]) * np.abs(r[rows])[:, None])
         u = np.unique(ids)
         for G, g, T, val, extra in ((self.Gw, gw, Tw, model.w, self.xw), (self.GV, gV, TV, model.V, self.xV)):
             gh = g[u] / m

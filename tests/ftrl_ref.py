@@ -9,7 +9,8 @@ gh = g / m, alpha = step size as given, lambda1 = reg_param (include/fm_hip.h, F
 z and n are stored through f32, as the device stores them.  Untouched rows do not move.
 
 Budget of a checked value: RTOL |ref| + ATOL (the suite's) + over the steps that touched it
-(2^-22 (T / m) (1 + |v| / alpha) + 2^-24 (|z'| + |v| sqrt(n') / alpha)) / den,  T = sum_e |term_e|:
+(2^-22 (T / m) (1 + |v| / alpha) + 2^-24 (|z'| + |v| sqrt(n') / alpha)) / den,  T = sum_e |term_e|' (a term's parts taken apart, as
+tests/adagrad_ref.py explains: (|S x| + |v| x^2) |r| and |x - 1| |yh| + |r|):
 the fp32 rounding of S, r, yh and of the stored state, pushed through the update's derivative.
 
 variant "z0" leaves z = 0 at the first touch, "nosigma" drops the sigma v term: what the sensitivity test swaps in.
@@ -46,8 +47,11 @@ class FtrlRef:
         gw, gV, Tw, TV = np.zeros_like(self.zw), np.zeros_like(self.zV), np.zeros_like(self.zw), np.zeros_like(self.zV)
         np.add.at(gw, ids, term_w)
         np.add.at(gV, ids, term_V)
-        np.add.at(Tw, ids, np.abs(term_w))
-        np.add.at(TV, ids, np.abs(term_V))
+        # the parts of a term taken apart: the device sums S (x r) and x^2 r on their own and forms A - v b once, so
+        # the fp32 rounding of S, r and yh scales with |S x r| + |v x^2 r|, not with their difference (an entry alone
+        # in its row has S x = v x^2: a term of exactly 0 whose parts are not small)
+        np.add.at(Tw, ids, np.abs(x - 1.0) * np.abs(yh[rows]) + np.abs(r[rows]))
+        np.add.at(TV, ids, (np.abs(S[rows] * x[:, None]) + np.abs(model.V[ids]) * (x * x)[:, None]) * np.abs(r[rows])[:, None])
         u = np.unique(ids)
         for z, n, g, T, val, extra, last in ((self.zw, self.nw, gw, Tw, model.w, self.xw, self.lw),
                                              (self.zV, self.nV, gV, TV, model.V, self.xV, self.lV)):

@@ -65,10 +65,15 @@ def test_three_steps_against_the_reference(gpu, k, loss, prepare):
     ctx.close()
 
 
+def geometry_lengths(L):
+    """test_run_geometry's runs (shared with tests/test_gpu_optimizer_edges.py, which runs them at other k)."""
+    return [1, 2, L - 1, L, L + 1, 2 * L, 3 * L + 1, 1, 16 * L + 5, 3, 1]
+
+
 @pytest.mark.parametrize("k", [16, 20])
 def test_run_geometry(gpu, k):
     L = piece()
-    lengths = [1, 2, L - 1, L, L + 1, 2 * L, 3 * L + 1, 1, 16 * L + 5, 3, 1]
+    lengths = geometry_lengths(L)
     F = len(lengths) + 2
     csr, ids, w, V = runs.make_runs(11 + k, lengths, F, k)
     model = R.Model.empty(F, k)

@@ -67,6 +67,11 @@ def test_three_steps_against_the_reference(gpu, k, loss, prepare):
     ctx.close()
 
 
+def geometry_lengths(W, g, lead):
+    """test_run_geometry's runs (shared with tests/test_gpu_optimizer_edges.py, which runs them at other k)."""
+    return [lead] * (lead > 0) + [1, 2, g - 1, g, g + 1, W - 1, W, W + 1, 2 * W, 3 * W + 1, 1, 16 * W + 5, 3, 1]
+
+
 @pytest.mark.parametrize("k", [16, 20])
 @pytest.mark.parametrize("lead", [0, 7])
 def test_run_geometry(gpu, k, lead):
@@ -75,7 +80,7 @@ def test_run_geometry(gpu, k, lead):
     lib = N.load()
     W, g = int(lib.fm_seam_ftrl_window()) & 0xFFFF, int(lib.fm_seam_ftrl_stretch(k))
     assert int(lib.fm_seam_ftrl_window()) >> 16 == int(lib.fm_seam_ftrl_stretch(16))
-    lengths = [lead] * (lead > 0) + [1, 2, g - 1, g, g + 1, W - 1, W, W + 1, 2 * W, 3 * W + 1, 1, 16 * W + 5, 3, 1]
+    lengths = geometry_lengths(W, g, lead)
     F = len(lengths) + 2
     csr, ids, w, V = runs.make_runs(11 + k, lengths, F, k)
     model = R.Model.empty(F, k)
