@@ -22,7 +22,7 @@ FM_MAX_LOCAL = 16
 FM_FUSE_DEFAULT, FM_FUSE_ON, FM_FUSE_OFF = 0, 1, -1
 FM_WIRE_FP32, FM_WIRE_FP64 = 0, 1
 FM_LOSS_SQUARED, FM_LOSS_LOGISTIC, FM_LOSS_BPR = 0, 1, 2
-FM_OPT_SGD, FM_OPT_ADAGRAD, FM_OPT_FTRL = 0, 1, 2
+FM_OPT_SGD, FM_OPT_ADAGRAD, FM_OPT_FTRL, FM_OPT_ADAM = 0, 1, 2, 3
 FM_RANK_MAX_TOP = 1024
 FM_RANK_SELECT_ALL, FM_RANK_SELECT_ONLY, FM_RANK_SELECT_EXCEPT = 0, 1, 2
 
@@ -53,6 +53,8 @@ class fm_config(C.Structure):
         ("wire", C.c_int32),
         ("opt_init", C.c_double),
         ("opt_l2", C.c_double),
+        ("opt_beta1", C.c_double),
+        ("opt_beta2", C.c_double),
         ("optimizer", C.c_int32),
         ("loss", C.c_int32),
     ]

@@ -251,11 +251,18 @@ static const char* loss_name(int32_t loss) {
   return loss == FM_LOSS_LOGISTIC ? "FM_LOSS_LOGISTIC" : loss == FM_LOSS_BPR ? "FM_LOSS_BPR" : "FM_LOSS_SQUARED";
 }
 
+static const char* opt_name(int32_t opt) {
+  return opt == FM_OPT_ADAM ? "FM_OPT_ADAM" : opt == FM_OPT_FTRL ? "FM_OPT_FTRL" : "FM_OPT_ADAGRAD";
+}
+
+// the optimizers that keep their state rows in fm_ctx::ftrl_state and run on the window stage (fm_window.h)
+static bool window_opt(int32_t opt) { return opt == FM_OPT_FTRL || opt == FM_OPT_ADAM; }
+
 void require_squared(const fm_ctx* ctx, const char* call) {
   FM_REQUIRE(ctx->cfg.loss == FM_LOSS_SQUARED, std::string(call) + " runs the squared step only: this context's loss is " +
                                                    loss_name(ctx->cfg.loss));
   FM_REQUIRE(ctx->cfg.optimizer == FM_OPT_SGD, std::string(call) + " runs the SGD update only: this context's optimizer is " +
-                                                   (ctx->cfg.optimizer == FM_OPT_FTRL ? "FM_OPT_FTRL" : "FM_OPT_ADAGRAD"));
+                                                   opt_name(ctx->cfg.optimizer));
 }
 
 static bool fuse_on(const fm_ctx* ctx) { return ctx->cfg.shard_count == 1 && fuse_rule(ctx); }
@@ -352,7 +359,7 @@ void reserve_work(fm_ctx* ctx, int64_t B, int64_t N) {
   w.ucnt.ensure_slack(sizeof(uint32_t) * (size_t)std::max<int64_t>((N + 1023) / 1024, 1));
   w.loss_part.ensure(sizeof(double2) * kLossPartBlocks);
   if (ctx->cfg.optimizer == FM_OPT_ADAGRAD) ctx->ada.ensure(N, ctx->kp);
-  if (ctx->cfg.optimizer == FM_OPT_FTRL) ctx->ftrl.ensure(N, ctx->kp);
+  if (window_opt(ctx->cfg.optimizer)) ctx->ftrl.ensure(N, ctx->kp);
 }
 
 }  // namespace fmhip
@@ -450,7 +457,7 @@ int step_impl(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_
   if (!fused) FM_HIP_CHECK(hipStreamWaitEvent(ctx->stream, prepared ? b->ready : ctx->ev_join, 0));
   e0 = ctx->prof_begin(ctx->stream);
   double* stats = ctx->loss_hist.as<double>() + 3 * (int64_t)ctx->epoch;
-  const bool adagrad = ctx->cfg.optimizer == FM_OPT_ADAGRAD;
+  const bool adagrad = ctx->cfg.optimizer == FM_OPT_ADAGRAD, adam = ctx->cfg.optimizer == FM_OPT_ADAM;
   if (adagrad) {
     // the AdaGrad stage in the segmented update's place (fm_adagrad.hip): it closes the step as well
     FM_REQUIRE(!fused && !emit, "the fused and the replicated step are the SGD update's: this context's optimizer is "
@@ -462,6 +469,14 @@ int step_impl(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_
                                 "FM_OPT_FTRL");
     const FtrlHyper hy{reg_param, ctx->cfg.opt_init, ctx->cfg.opt_l2};
     launch_ftrl(T, ctx->ftrl_state.as<float>(), N, ctx->work, ctx->ftrl, p, hy, skeys, sents, nfwd, stats, ctx->stream);
+  } else if (adam) {
+    // the lazy AdamW rule on the same stage (fm_adam.hip): this step is the context's tau-th since its last reset
+    FM_REQUIRE(!fused && !emit, "the fused and the replicated step are the SGD update's: this context's optimizer is "
+                                "FM_OPT_ADAM");
+    const fm_config& c = ctx->cfg;
+    const AdamHyper hy{c.opt_beta1 != 0.0 ? c.opt_beta1 : 0.9, c.opt_beta2 != 0.0 ? c.opt_beta2 : 0.999, c.opt_init, c.opt_l2,
+                       ctx->opt_tau + 1};
+    launch_adam(T, ctx->ftrl_state.as<float>(), N, ctx->work, ctx->ftrl, p, hy, skeys, sents, nfwd, stats, ctx->stream);
   } else {
     launch_segment_update(T, b->dev, ctx->work, p, skeys, sents, nfwd, stats, ctx->stream, emit,
                           fused ? b->split_n.as<int64_t>() : nullptr);
@@ -472,9 +487,10 @@ int step_impl(fm_ctx* ctx, fm_batch* b, int32_t t, double step_size, double reg_
   // the last read of the batch (its next fm_batch_prepare or fm_batch_from_rows refill waits for it)
   if (b->last_use) FM_HIP_CHECK(hipEventRecord(b->last_use, ctx->stream));
   b->prepared = false;
-  ctx->prof_end(adagrad ? "adagrad" : ftrl ? "ftrl" : "update", e0, ctx->stream);
+  ctx->prof_end(adagrad ? "adagrad" : ftrl ? "ftrl" : adam ? "adam" : "update", e0, ctx->stream);
   if (emit) return FM_OK;
   ctx->epoch += 1;
+  ctx->opt_tau += 1;
   ctx->cum_host.push_back(p.cum_next);
   if (out) {
     ctx->pinned.ensure(64);
@@ -512,8 +528,25 @@ int fm_create(const fm_config* cfg, fm_ctx** out) {
                  "loss = " + nm + " cannot take fuse_single = FM_FUSE_ON: the fused forward applies singleton rows with the "
                  "squared residual");
     }
-    FM_REQUIRE(cfg->optimizer == FM_OPT_SGD || cfg->optimizer == FM_OPT_ADAGRAD || cfg->optimizer == FM_OPT_FTRL,
-               "optimizer must be FM_OPT_SGD, FM_OPT_ADAGRAD or FM_OPT_FTRL");
+    FM_REQUIRE(cfg->optimizer == FM_OPT_SGD || cfg->optimizer == FM_OPT_ADAGRAD || cfg->optimizer == FM_OPT_FTRL ||
+                   cfg->optimizer == FM_OPT_ADAM,
+               "optimizer must be FM_OPT_SGD, FM_OPT_ADAGRAD, FM_OPT_FTRL or FM_OPT_ADAM");
+    if (cfg->optimizer == FM_OPT_ADAM) {
+      FM_REQUIRE(std::isfinite(cfg->opt_init) && cfg->opt_init > 0.0,
+                 "optimizer = FM_OPT_ADAM needs a finite opt_init > 0 (eps of the normalised step)");
+      FM_REQUIRE(std::isfinite(cfg->opt_l2) && cfg->opt_l2 >= 0.0,
+                 "optimizer = FM_OPT_ADAM needs a finite opt_l2 >= 0 (the decoupled weight decay)");
+      FM_REQUIRE(cfg->opt_beta1 == 0.0 || (std::isfinite(cfg->opt_beta1) && cfg->opt_beta1 > 0.0 && cfg->opt_beta1 < 1.0),
+                 "optimizer = FM_OPT_ADAM needs opt_beta1 in (0, 1), or 0 for the default 0.9");
+      FM_REQUIRE(cfg->opt_beta2 == 0.0 || (std::isfinite(cfg->opt_beta2) && cfg->opt_beta2 > 0.0 && cfg->opt_beta2 < 1.0),
+                 "optimizer = FM_OPT_ADAM needs opt_beta2 in (0, 1), or 0 for the default 0.999");
+      FM_REQUIRE(cfg->parallel == FM_PARALLEL_NONE,
+                 "optimizer = FM_OPT_ADAM needs parallel == FM_PARALLEL_NONE: the multi-GPU steps run the SGD update");
+      FM_REQUIRE(cfg->shard_count == 1, "optimizer = FM_OPT_ADAM needs shard_count == 1: the sharded step runs the SGD update");
+      FM_REQUIRE(cfg->fuse_single != FM_FUSE_ON,
+                 "optimizer = FM_OPT_ADAM cannot take fuse_single = FM_FUSE_ON: the fused forward applies singleton rows "
+                 "with the SGD update");
+    }
     if (cfg->optimizer == FM_OPT_FTRL) {
       FM_REQUIRE(std::isfinite(cfg->opt_init) && cfg->opt_init > 0.0,
                  "optimizer = FM_OPT_FTRL needs a finite opt_init > 0 (beta of the per-coordinate rate)");
@@ -572,7 +605,7 @@ int fm_create(const fm_config* cfg, fm_ctx** out) {
       c->accum.ensure(sizeof(float) * (size_t)std::max<int64_t>(c->rows, 1) * (c->kp + 4));
       launch_ada_fill(c->accum_view(), c->rows, c->kp, cfg->opt_init, c->stream);
     }
-    if (cfg->optimizer == FM_OPT_FTRL) {
+    if (window_opt(cfg->optimizer)) {
       c->ftrl_state.ensure(sizeof(float) * (size_t)std::max<int64_t>(c->rows, 1) * 2 * (c->kp + 4));
       launch_ftrl_zero(c->ftrl_state.as<float>(), c->rows, c->kp, c->stream);
     }
@@ -650,7 +683,8 @@ int fm_optimizer_reset(fm_ctx* ctx) {
     FM_REQUIRE(!ctx->group, "fm_optimizer_reset on a multi-GPU context: it keeps no optimizer state");
     if (ctx->cfg.optimizer == FM_OPT_ADAGRAD)
       launch_ada_fill(ctx->accum_view(), ctx->rows, ctx->kp, ctx->cfg.opt_init, ctx->stream);
-    if (ctx->cfg.optimizer == FM_OPT_FTRL) launch_ftrl_zero(ctx->ftrl_state.as<float>(), ctx->rows, ctx->kp, ctx->stream);
+    if (window_opt(ctx->cfg.optimizer)) launch_ftrl_zero(ctx->ftrl_state.as<float>(), ctx->rows, ctx->kp, ctx->stream);
+    ctx->opt_tau = 0;  // FM_OPT_ADAM's step count: the next step is a first step
     return FM_OK;
   });
 }

@@ -234,9 +234,12 @@ struct fm_ctx {
   AdaWork ada;
   float* accum_view() const { return accum.as<float>(); }
   // FM_OPT_FTRL contexts only: the state rows [rows][2 (kp + 4)] = {z_V[kp], z_w, 0, 0, 0, n_V[kp], n_w, 0, 0, 0}
-  // (fm_ftrl.hip), zero at fm_create and after fm_optimizer_reset; and the stage's scratch
+  // (fm_ftrl.hip), zero at fm_create and after fm_optimizer_reset; and the stage's scratch.  An FM_OPT_ADAM context
+  // keeps its rows {m_V[kp], m_w, last, 0, 0, v_V[kp], v_w, 0, 0, 0} in the same buffer and runs on the same scratch
+  // (fm_adam.hip), and counts the steps executed since fm_create or the last fm_optimizer_reset in opt_tau
   DevBuf ftrl_state;
   FtrlWork ftrl;
+  int32_t opt_tau = 0;
   std::vector<double> cum_host{0.0};  // cum[e] = sum of lambda over executed steps 1..e
   int32_t epoch = 0;
   DevBuf loss_hist;  // [hist_cap][3] double {loss, n_loss, n_unique}
@@ -533,7 +536,7 @@ inline int bits_for(int64_t max_value) {
 bool fuse_rule(const fm_ctx* ctx);
 // the manual multi-GPU phases (fm_shard_*, fm_repl_*) are the squared step's: FM_ERR_ARG on a context
 // with another fm_config.loss
-// ... nor with another fm_config.optimizer than FM_OPT_SGD (the message names it: FM_OPT_ADAGRAD or FM_OPT_FTRL)
+// ... nor with another fm_config.optimizer than FM_OPT_SGD (the message names it: FM_OPT_ADAGRAD, FM_OPT_FTRL or FM_OPT_ADAM)
 void require_squared(const fm_ctx* ctx, const char* call);
 // stream st waits until a batch refilled by fm_batch_from_rows has been gathered (copy stream)
 void wait_built(const fm_batch* b, hipStream_t st);

@@ -342,6 +342,16 @@ void launch_ftrl(const TableView& T, float* Z, int64_t N, const StepWork& w, Ftr
                  hipStream_t st);
 // every word of Z[rows][2 (kp + 4)] = 0
 void launch_ftrl_zero(float* Z, int64_t rows, int kp, hipStream_t st);
+// The lazy AdamW rule on the same stage (fm_adam.hip; the stage itself is fm_window.h), on a context whose
+// optimizer is FM_OPT_ADAM: the same inputs, state array, scratch and zeroing as launch_ftrl; the state rows are
+// {m_V[kp], m_w, last, 0, 0, v_V[kp], v_w, 0, 0, 0}.  eta and lam are p's own, as for the SGD update.
+struct AdamHyper {
+  double b1, b2, eps, wd;  // fm_config.opt_beta1 / opt_beta2 with their defaults resolved, opt_init, opt_l2
+  int32_t tau;             // the step being executed, counted from fm_create or the last fm_optimizer_reset (>= 1)
+};
+void launch_adam(const TableView& T, float* Z, int64_t N, const StepWork& w, FtrlWork& fw, const StepParams& p,
+                 const AdamHyper& h, const uint32_t* skeys, const uint2* sents, int64_t n_loss_blocks, double* stats_out,
+                 hipStream_t st);
 // Seams for the suite (tests/test_gpu_ftrl.py), as fm_seam_adagrad_piece: the window W in the low 16 bits with the
 // kp <= 16 lane groups' stretch in the high 16, and the stretch of the lane groups that serve a given kp.
 extern "C" int32_t fm_seam_ftrl_window(void);

@@ -311,25 +311,28 @@ class FMContext:
     threshold stays unscaled.  "ftrl" is FTRL-Proximal: two state words per coordinate, alpha = the step's
     step_size as given, lambda1 = its reg_param, beta = ``opt_init`` (> 0), lambda2 = ``opt_l2`` (>= 0); its L1
     is part of the closed-form update, so coordinates come out exactly 0 and untouched rows do not move.
-    Single GPU, never fused; each serves every loss."""
+    "adam" is lazy AdamW: first and second moments per coordinate with rates ``opt_beta1`` / ``opt_beta2`` (0 = the
+    defaults 0.9 / 0.999, else in (0, 1)), eps = ``opt_init``, decoupled weight decay ``opt_l2``; a row's moments are
+    decayed on touch for the steps it sat out, and eta = step_size / sqrt(t) as for "sgd".  ``opt_init`` None = 0.1,
+    or 1e-8 under "adam".  Single GPU, never fused; each serves every loss."""
 
     _PAR = {None: N.FM_PARALLEL_NONE, "none": N.FM_PARALLEL_NONE, "sharded": N.FM_PARALLEL_SHARDED,
             "replicated": N.FM_PARALLEL_REPLICATED}
     _TR = {"auto": N.FM_TRANSPORT_AUTO, "rccl": N.FM_TRANSPORT_RCCL, "copy": N.FM_TRANSPORT_COPY}
     _WIRE = {"fp32": N.FM_WIRE_FP32, "fp64": N.FM_WIRE_FP64}
     _LOSS = {"squared": N.FM_LOSS_SQUARED, "logistic": N.FM_LOSS_LOGISTIC, "bpr": N.FM_LOSS_BPR}
-    _OPT = {"sgd": N.FM_OPT_SGD, "adagrad": N.FM_OPT_ADAGRAD, "ftrl": N.FM_OPT_FTRL}
+    _OPT = {"sgd": N.FM_OPT_SGD, "adagrad": N.FM_OPT_ADAGRAD, "ftrl": N.FM_OPT_FTRL, "adam": N.FM_OPT_ADAM}
 
     def __init__(self, num_features: int, k: int, *, device: int = 0, seed: int = 0, init_sd: float = 0.01,
                  w0: float = 0.0, shard_index: int = 0, shard_count: int = 1, parallel: str | None = None,
                  n_gpus: int = 1, devices=None, transport: str = "auto", n_procs: int = 1, proc_rank: int = 0,
                  comm_id: bytes | None = None, fuse: bool | None = None, xchg_chunks: int = 0, wire: str = "fp32",
-                 loss: str = "squared", optimizer: str = "sgd", opt_init: float = 0.1,
-                 opt_l2: float = 0.0):
+                 loss: str = "squared", optimizer: str = "sgd", opt_init: float | None = None,
+                 opt_l2: float = 0.0, opt_beta1: float = 0.0, opt_beta2: float = 0.0):
         if loss not in self._LOSS:
             raise ValueError('loss must be "squared", "logistic" or "bpr"')
         if optimizer not in self._OPT:
-            raise ValueError('optimizer must be "sgd", "adagrad" or "ftrl"')
+            raise ValueError('optimizer must be "sgd", "adagrad", "ftrl" or "adam"')
         self._lib = N.load()
         if wire not in self._WIRE:
             raise ValueError('wire must be "fp32" or "fp64"')
@@ -351,8 +354,10 @@ class FMContext:
         cfg.wire = self._WIRE[wire]
         cfg.loss = self._LOSS[loss]
         cfg.optimizer = self._OPT[optimizer]
-        cfg.opt_init = float(opt_init)
+        cfg.opt_init = float(opt_init) if opt_init is not None else (1e-8 if optimizer == "adam" else 0.1)
         cfg.opt_l2 = float(opt_l2)
+        cfg.opt_beta1 = float(opt_beta1)
+        cfg.opt_beta2 = float(opt_beta2)
         cfg.n_procs = int(n_procs)
         cfg.proc_rank = int(proc_rank)
         if comm_id is not None:
@@ -403,8 +408,8 @@ class FMContext:
         N.check(self._lib.fm_reserve(self.handle, int(max_rows), int(max_nnz)), "fm_reserve")
 
     def optimizer_reset(self):
-        """Refill an "adagrad" context's accumulators with opt_init, or zero an "ftrl" context's z and n
-        (fm_optimizer_reset; enqueued on the main stream, the table untouched).  Nothing to do on an "sgd" context."""
+        """Refill an "adagrad" context's accumulators with opt_init, zero an "ftrl" context's z and n, or zero an
+        "adam" context's moments and step count (fm_optimizer_reset; enqueued on the main stream, the table untouched).  Nothing to do on an "sgd" context."""
         N.check(self._lib.fm_optimizer_reset(self.handle), "fm_optimizer_reset")
 
     # --------------------------------------------------------------------- tables

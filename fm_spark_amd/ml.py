@@ -436,8 +436,12 @@ class FactorizationMachinesSGD:
         # the accumulators' starting value
         "optimizer": "sgd",
         "initialAccumulator": 0.1,
-        # "ftrl" only: lambda2 of its closed-form update
+        # "ftrl": lambda2 of its closed-form update; "adam": the decoupled weight decay
         "l2": 0.0,
+        # "adam" only: the moments' decay rates and the eps of the normalised step
+        "beta1": 0.9,
+        "beta2": 0.999,
+        "epsilon": 1e-8,
     }
 
     def __init__(self, uid: str | None = None):
@@ -591,10 +595,15 @@ class FactorizationMachinesSGD:
         rows one.  regParam's soft threshold is not scaled by the adaptive rate.  "ftrl" is FTRL-Proximal
         (McMahan et al., 2013), the choice when the model must come out sparse: alpha = stepSize as given (no
         1 / sqrt(t)), lambda1 = regParam, beta = initialAccumulator, lambda2 = setL2; the L1 is part of its closed
-        form, so coordinates are exactly 0 while |z| <= lambda1 and untouched rows do not move.  Each serves every
-        loss, through fit and fitInteractions; one GPU (ValueError with setParallel), never fused."""
-        if optimizer not in ("sgd", "adagrad", "ftrl"):
-            raise ValueError('optimizer must be "sgd", "adagrad" or "ftrl"')
+        form, so coordinates are exactly 0 while |z| <= lambda1 and untouched rows do not move.  "adam" is lazy
+        AdamW, the solver Spark 3's own FMRegressor / FMClassifier default to: first and second moments per
+        coordinate (setBeta1, setBeta2), the step stepSize / sqrt(t) * mhat / (sqrt(vhat) + setEpsilon) with both
+        moments bias-corrected, setL2 as the decoupled weight decay; the moments of a row that sat out d - 1 steps
+        are decayed by beta^d when it is touched again, and the row itself does not move in between.  regParam's
+        soft threshold is as under "sgd".  Each serves every loss, through fit and fitInteractions; one GPU
+        (ValueError with setParallel), never fused."""
+        if optimizer not in ("sgd", "adagrad", "ftrl", "adam"):
+            raise ValueError('optimizer must be "sgd", "adagrad", "ftrl" or "adam"')
         if optimizer != "sgd" and self._params["parallel"] not in (None, "none"):
             raise ValueError(f'optimizer "{optimizer}" trains on one GPU: the multi-GPU steps run the SGD update')
         return self._set("optimizer", optimizer)
@@ -607,11 +616,34 @@ class FactorizationMachinesSGD:
         return self._set("initialAccumulator", float(value))
 
     def setL2(self, value: float):
-        """lambda2 of the "ftrl" update (finite, >= 0; default 0); the other optimizers ignore it."""
+        """lambda2 of the "ftrl" update, the decoupled weight decay of "adam" (finite, >= 0; default 0); the other
+        optimizers ignore it."""
         if isinstance(value, bool) or not np.isfinite(value) or not float(value) >= 0.0:
             raise ValueError("l2 must be finite and >= 0")
         return self._set("l2", float(value))
 
+    def _set_rate(self, name, value):
+        if isinstance(value, bool) or not np.isfinite(value) or not 0.0 < float(value) < 1.0:
+            raise ValueError(f"{name} must be finite and in (0, 1)")
+        return self._set(name, float(value))
+
+    def setBeta1(self, value: float):
+        """The first moment's decay rate under "adam" (in (0, 1); default 0.9); the other optimizers ignore it."""
+        return self._set_rate("beta1", value)
+
+    def setBeta2(self, value: float):
+        """The second moment's decay rate under "adam" (in (0, 1); default 0.999); the other optimizers ignore it."""
+        return self._set_rate("beta2", value)
+
+    def setEpsilon(self, value: float):
+        """eps of the "adam" step mhat / (sqrt(vhat) + eps) (finite, > 0; default 1e-8)."""
+        if isinstance(value, bool) or not np.isfinite(value) or not float(value) > 0.0:
+            raise ValueError("epsilon must be finite and > 0")
+        return self._set("epsilon", float(value))
+
+    def getBeta1(self): return self._params["beta1"]
+    def getBeta2(self): return self._params["beta2"]
+    def getEpsilon(self): return self._params["epsilon"]
     def getL2(self): return self._params["l2"]
     def getOptimizer(self): return self._params["optimizer"]
     def getInitialAccumulator(self): return self._params["initialAccumulator"]
@@ -661,14 +693,27 @@ class FactorizationMachinesSGD:
             if p["parallel"] not in (None, "none"):
                 raise ValueError("binaryValidationData needs a single-GPU estimator: the binary evaluation is not multi-GPU")
         # setOptimizer's and setInitialAccumulator's rules
-        if p["optimizer"] not in ("sgd", "adagrad", "ftrl"):
-            raise ValueError('optimizer must be "sgd", "adagrad" or "ftrl"')
-        if p["optimizer"] == "ftrl" and not (np.isfinite(p["l2"]) and p["l2"] >= 0.0):
+        if p["optimizer"] not in ("sgd", "adagrad", "ftrl", "adam"):
+            raise ValueError('optimizer must be "sgd", "adagrad", "ftrl" or "adam"')
+        if p["optimizer"] in ("ftrl", "adam") and not (np.isfinite(p["l2"]) and p["l2"] >= 0.0):
             raise ValueError("l2 must be finite and >= 0")
+        if p["optimizer"] == "adam":
+            for name in ("beta1", "beta2"):
+                if not (np.isfinite(p[name]) and 0.0 < p[name] < 1.0):
+                    raise ValueError(f"{name} must be finite and in (0, 1)")
+            if not (np.isfinite(p["epsilon"]) and p["epsilon"] > 0.0):
+                raise ValueError("epsilon must be finite and > 0")
         if p["optimizer"] != "sgd" and p["parallel"] not in (None, "none"):
             raise ValueError(f'optimizer "{p["optimizer"]}" trains on one GPU: the multi-GPU steps run the SGD update')
-        if p["optimizer"] != "sgd" and not (np.isfinite(p["initialAccumulator"]) and p["initialAccumulator"] > 0.0):
+        if p["optimizer"] in ("adagrad", "ftrl") and not (np.isfinite(p["initialAccumulator"]) and p["initialAccumulator"] > 0.0):
             raise ValueError("initialAccumulator must be finite and > 0")
+
+    def _optimizer_kwargs(self):
+        """FMContext's optimizer arguments: opt_init carries initialAccumulator, or epsilon under "adam"."""
+        p = self._params
+        adam = p["optimizer"] == "adam"
+        return dict(optimizer=p["optimizer"], opt_init=p["epsilon"] if adam else p["initialAccumulator"], opt_l2=p["l2"],
+                    opt_beta1=p["beta1"] if adam else 0.0, opt_beta2=p["beta2"] if adam else 0.0)
 
     # fit (SGD.scala:76-216) --------------------------------------------------------------
     def fit(self, dataset: DataFrame, initial_tables=None, pipelined: bool | None = None) -> FactorizationMachinesModel:
@@ -695,8 +740,7 @@ class FactorizationMachinesSGD:
         F = p["numFeatures"] or (int(col.max()) + 1 if len(col) else 1)
         ctx = FMContext(F, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0,
                         parallel=p["parallel"], n_gpus=p["nGpus"], devices=p["devices"], transport=p["transport"],
-                        wire=p["wire"], loss=p["loss"], optimizer=p["optimizer"], opt_init=p["initialAccumulator"],
-                        opt_l2=p["l2"])
+                        wire=p["wire"], loss=p["loss"], **self._optimizer_kwargs())
         if pipelined is None:
             pipelined = True
         # randomSplit(Array.fill(maxIter)(miniBatchFraction), 1234L) (:111-112)
@@ -843,8 +887,7 @@ class FactorizationMachinesSGD:
         k = p["dimFactorization"]
         top = max([int(col.max()) + 1 for _, col, _ in rows if len(col)], default=1)
         ctx = FMContext(p["numFeatures"] or top, k, device=p["device"], seed=p["seed"], init_sd=p["initialSd"], w0=0.0,
-                        loss=p["loss"], optimizer=p["optimizer"], opt_init=p["initialAccumulator"],
-                        opt_l2=p["l2"])
+                        loss=p["loss"], **self._optimizer_kwargs())
         bu, bc = (ctx.batch(N.CSRHost(rp, col, val, np.zeros(len(rp) - 1))) for rp, col, val in rows)
         # the exclude lists, resident for the whole loop: the given ones (normalised above, once), else what
         # the interactions say each context has seen, built on the device from the pairs themselves

@@ -58,6 +58,7 @@ extern "C" {
 #define FM_OPT_SGD 0     /* fm_config.optimizer: the reference's row update, one rate stepSize / sqrt(t) (default) */
 #define FM_OPT_ADAGRAD 1 /* per-coordinate AdaGrad on the touched rows (single tables) */
 #define FM_OPT_FTRL 2    /* FTRL-Proximal on the touched rows: L1 in the closed form, exact zeros (single tables) */
+#define FM_OPT_ADAM 3    /* lazy AdamW on the touched rows: stale moments decayed on touch, decoupled decay (single tables) */
 
 typedef struct fm_ctx fm_ctx;
 typedef struct fm_batch fm_batch;
@@ -187,9 +188,40 @@ typedef struct fm_lists fm_lists;
  *                on where a run lies in the sorted view.  Serves every loss.  Single tables only and never
  *                fused: the refusals are FM_OPT_ADAGRAD's, naming FM_OPT_FTRL.  A step on such a context needs
  *                stepSize > 0 and regParam >= 0.
+ *                FM_OPT_ADAM: lazy AdamW (Kingma & Ba, ICLR 2015; the decoupled decay of Loshchilov & Hutter, ICLR
+ *                2019), the update Spark 3's own FMRegressor / FMClassifier default to.  Every table coordinate
+ *                keeps two fp32 state words m and v and every state row one int32 word `last`, in one array of
+ *                FM_OPT_FTRL's shape, [rows][2 (kp + 4)] = {m_V[kp], m_w, last, 0, 0, v_V[kp], v_w, 0, 0, 0}; `last`
+ *                is stored as the integer's bits.  The context counts tau, the steps executed since fm_create or
+ *                the last fm_optimizer_reset: the step being executed has tau >= 1.  With g, gh = g / m and v_cur
+ *                as under FM_OPT_ADAGRAD (an absent row reads as zero, pending L1 is brought current first), eta
+ *                = stepSize / sqrt(t) and lam = eta * regParam exactly as under FM_OPT_SGD, b1 = opt_beta1, b2 =
+ *                opt_beta2, eps = opt_init, wd = opt_l2, and for a row the batch touches d = tau - last if last >
+ *                0, else 1 -- all in fp64, each stored word rounded once:
+ *                    m' = b1^d m + (1 - b1) gh
+ *                    v' = b2^d v + (1 - b2) gh*gh
+ *                    step = eta * ( (m' / (1 - b1^tau)) / (sqrt(v' / (1 - b2^tau)) + eps) + wd * v_cur )
+ *                    x' = S_lam(v_cur - step)
+ *                    last = tau
+ *                b^d is what dense Adam does to the moments of a coordinate whose gradient was zero for d - 1
+ *                steps, so a moment that has sat for 10 000 steps is not applied at full strength (unlike in a
+ *                SparseAdam that ignores the gap); the parameter itself does not move while the row is not
+ *                touched, which is the lazy part.  wd is the decoupled weight decay, the "W".  The bias factors
+ *                are per step (formed on the host), the decay factors per row (formed on the device as
+ *                exp2(d log2 b)).  The lazy L1, cum, the forward's catch-up, predict, rank and export are
+ *                untouched, as for FM_OPT_ADAGRAD; a row the batch does not touch keeps its state bytes.  The
+ *                state is allocated by FM_OPT_ADAM contexts only, counted by fm_device_bytes_live, all zero at
+ *                fm_create and after fm_optimizer_reset (which also sets tau to 0); fm_load_tables and fm_init_*
+ *                leave it alone; it is neither exported nor imported.  It runs on FM_OPT_FTRL's stage with a rule
+ *                of its own (fm_window.h, fm_adam.hip; profile name "adam"), so the same statements about bits
+ *                hold.  Serves every loss.  Single tables only and never fused: the refusals are FM_OPT_ADAGRAD's,
+ *                naming FM_OPT_ADAM.
  * opt_init     : FM_OPT_ADAGRAD: G0, the accumulators' starting value (fp64; stored as fp32).  FM_OPT_FTRL:
- *                beta.  Either: finite and > 0, else FM_ERR_ARG.  Ignored under FM_OPT_SGD.
- * opt_l2       : FM_OPT_FTRL's lambda2: finite and >= 0, else FM_ERR_ARG.  Ignored by the other optimizers.
+ *                beta.  FM_OPT_ADAM: eps.  Each: finite and > 0, else FM_ERR_ARG.  Ignored under FM_OPT_SGD.
+ * opt_l2       : FM_OPT_FTRL's lambda2, FM_OPT_ADAM's decoupled weight decay wd: finite and >= 0, else FM_ERR_ARG.
+ *                Ignored by the other optimizers.
+ * opt_beta1 / opt_beta2 : FM_OPT_ADAM's decay rates of the first and second moment.  0 selects the defaults 0.9 and
+ *                0.999; otherwise finite and in (0, 1), else FM_ERR_ARG.  Ignored by the other optimizers.
  * Zero-initialise the struct: every field's 0 is its default. */
 typedef struct fm_config {
   int64_t num_features;
@@ -214,6 +246,8 @@ typedef struct fm_config {
    * offset moved by 12 bytes against earlier headers -- callers are rebuilt against this header */
   double opt_init;
   double opt_l2; /* inserted after opt_init for the same reason */
+  double opt_beta1; /* and these two after opt_l2: loss moved by another 16 bytes */
+  double opt_beta2;
   int32_t optimizer;
   int32_t loss;
 } fm_config;
@@ -283,12 +317,12 @@ int fm_sync(fm_ctx* ctx);
  * payloads before and after the re-key, the flags and their scan (44 bytes per row, 52 with the labels), the per-block
  * partials and a sort workspace of the stage's own (24 bytes per row), sized by the largest call. */
 int fm_reserve(fm_ctx* ctx, int64_t max_rows, int64_t max_nnz);
-/* Zero-fill an FM_OPT_FTRL context's state rows, or
+/* Zero-fill an FM_OPT_FTRL or FM_OPT_ADAM context's state rows (the latter's step count tau goes back to 0 too), or
  * refill an FM_OPT_ADAGRAD context's accumulators with fm_config.opt_init (enqueued on the main stream;
  * the table is not touched): the next step behaves as a first step on the current table.  A no-op on an
  * FM_OPT_SGD context; FM_ERR_ARG on a multi-GPU context.  fm_reserve on an FM_OPT_ADAGRAD context also
  * sizes the stage's scratch (12 bytes per entry for the piece flags and their scan, a count per 256 entries,
- * and the partial sums of the runs longer than a piece); on an FM_OPT_FTRL context, the two partial sums per
+ * and the partial sums of the runs longer than a piece); on an FM_OPT_FTRL or FM_OPT_ADAM context, the two partial sums per
  * window of 256 entries and a count per 1024 entries. */
 int fm_optimizer_reset(fm_ctx* ctx);
 
